@@ -6,11 +6,15 @@ samples of the 3840x2160 bistro-like scene (the real Bistro a
 N > 1, the single gather of the packed radiance tiles to rank 0 (RCCL over xGMI). Scene, BVH, textures and light tables are
 resident in HBM before the timed region; nothing is uploaded inside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line. `value` = (extend + shadow rays of all ranks) / wall time of the K timed steps (max over ranks).
 The frame is fixed as N grows (pixel-tile sharding) => "scaling": "strong".
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds what the end-of-round record holds, after the
+timed region: the serial-kernel roofline steps, the realtime passes, the CPU baseline and the parity checks against the oracle and the reference text.
+--dump-outputs DIR writes what the last timed step left for a caller, rank 0's frame (a fixed, seeded sample of its pixels) and ray counts, as .npy.
 """
 import argparse
 import json
@@ -47,16 +51,20 @@ def main():
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--scale", type=float, default=1.0, help="triangle-count scale of the bistro-like generator (1.0 = 2.8 M triangles)")
     ap.add_argument("--tex", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline: roofline steps, realtime passes, CPU baseline and parity checks (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, under 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline leg and no oracle parity block")
     ap.add_argument("--fp32-lp-types", action="store_true", help="RTXPT_LP_TYPES_USE_16BIT_PRECISION 0 instead of the reference's default build (lp types in binary16)")
     ap.add_argument("--no-env-compression", action="store_true", help="sample the uncompressed RGBA16F environment cube (the reference on Vulkan) instead of the BC6H one (its D3D12 default)")
     ap.add_argument("--skip-roofline-steps", action="store_true", help="profiling runs (tools/profile_round.sh): only the timed steps, no extra serial / counter steps")
     ap.add_argument("--serial-kernels", action="store_true", help="run every step with PT_DEVICE_SERIAL_KERNELS semantics (for rocprofv3 kernel traces: launches never overlap)")
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="N > 1: 'rccl' = one rank per GPU, the frame gather is pt_gather over RCCL (the measurement). 'host' = REHEARSAL of the multi-rank code path on fewer GPUs than "
-                         "ranks: the ranks share the visible devices (rank % device count), the process group is gloo, the tiles travel through pt_gather_host (the library's own gather "
+                         "ranks: the ranks share the visible devices (rank %% device count), the process group is gloo, the tiles travel through pt_gather_host (the library's own gather "
                          "protocol over a host transport) — every line of the N > 1 branch runs, the timing is not a scaling number and the JSON line says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import rtxpt_amd as pt
@@ -170,6 +178,31 @@ def main():
         elapsed, rays_total = float(tmax.item()), float(rsum.item())
     else:
         rays_total = rays_local
+    if args.dump_outputs and rank == 0:      # before anything else renders: rank 0's frame is the last timed step's (after its gather for N > 1)
+        dump_outputs(args.dump_outputs, host_frame if host_transport else g.radiance(), stats[-1])
+
+    def headline(digest):
+        info = g.scene_info(); bvh = g.bvh_info()
+        return {
+            "metric": "Mrays/s at 4K 4spp 8-bounce bistro-like (extend + shadow rays / wall time of pt_render)",
+            "value": rays_total / elapsed / 1e6, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "C3 bistro-like street canyon, %d triangles, 64 materials, 32 textures %d^2, %d emissive-triangle + env-quad lights, %dx%d, %d spp, 8 bounces, NEE 5 candidates + RR, lp types %s, environment cube %s; BVH builder=%s, built on %s, buildMs %.1f (host part %.1f), %d wide nodes"
+                                   % (info["triangles"], args.tex, len(g.lights()["proxyCounters"]), W, H, SPP, "fp32" if args.fp32_lp_types else "binary16 (reference default)",
+                                      "RGBA16F" if args.no_env_compression else "2048 BC6H (reference default on D3D12)", bvh["builderName"], bvh["builtOn"], bvh["buildMs"], bvh["hostMs"], bvh["numWideNodes"]),
+                       "bvh": bvh,
+                       "parallelism": "pixel-tile shard x%d + 1 gather" % world, "gather": gather_mode, "gather_ms_per_step_rank0": (sum(gather_ms) / len(gather_ms)) if gather_ms else None, "transport": args.transport if world > 1 else "none",
+                       "rehearsal": bool(host_transport), "kernel_source_sha256": digest, "library_sha256": pt.library_digest(), "rays_per_step": rays_total / args.steps,
+                       "extend_rays_per_step": sum(s["extendRays"] for s in stats) / args.steps * (world if world > 1 else 1), "paths_per_step": W * H * SPP,
+                       "tail_kernel_launches_per_step": sum(s["tailLaunches"] for s in stats) / args.steps},
+        }
+
+    if not args.full and not args.skip_roofline_steps:
+        if rank == 0:
+            print(json.dumps(headline(pt.kernel_source_digest())))
+        if world > 1:
+            dist.barrier(); dist.destroy_process_group()
+        return
 
     # roofline of the dominant kernel (k_extend). In the timed region pt_render pipelines four sub-frame batches on four streams, so launches of
     # different kernels overlap and a per-launch HIP-event duration there measures "k_extend while sharing the GPU". The launch duration the
@@ -223,19 +256,8 @@ def main():
         valu["instructions_per_simd_cycle"] = vps
 
     if rank == 0:
-        info = g.scene_info(); bvh = g.bvh_info()
-        out = {
-            "metric": "Mrays/s at 4K 4spp 8-bounce bistro-like (extend + shadow rays / wall time of pt_render)",
-            "value": rays_total / elapsed / 1e6, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "C3 bistro-like street canyon, %d triangles, 64 materials, 32 textures %d^2, %d emissive-triangle + env-quad lights, %dx%d, %d spp, 8 bounces, NEE 5 candidates + RR, lp types %s, environment cube %s; BVH builder=%s, built on %s, buildMs %.1f (host part %.1f), %d wide nodes"
-                                   % (info["triangles"], args.tex, len(g.lights()["proxyCounters"]), W, H, SPP, "fp32" if args.fp32_lp_types else "binary16 (reference default)",
-                                      "RGBA16F" if args.no_env_compression else "2048 BC6H (reference default on D3D12)", bvh["builderName"], bvh["builtOn"], bvh["buildMs"], bvh["hostMs"], bvh["numWideNodes"]),
-                       "bvh": bvh,
-                       "parallelism": "pixel-tile shard x%d + 1 gather" % world, "gather": gather_mode, "gather_ms_per_step_rank0": (sum(gather_ms) / len(gather_ms)) if gather_ms else None, "transport": args.transport if world > 1 else "none",
-                       "rehearsal": bool(host_transport), "kernel_source_sha256": digest, "library_sha256": pt.library_digest(), "rays_per_step": rays_total / args.steps,
-                       "extend_rays_per_step": sum(s["extendRays"] for s in stats) / args.steps * (world if world > 1 else 1), "paths_per_step": W * H * SPP,
-                       "tail_kernel_launches_per_step": sum(s["tailLaunches"] for s in stats) / args.steps},
+        out = headline(digest)
+        out.update({
             # `frac` is the prescribed figure: algorithmic bytes / launch time / 8 TB/s. `bound` is what the counters say limits the kernel:
             # the BVH is served from L1/L2, HBM itself carries `hbm_counter_gbs`; the loop is bound by instruction issue and dependent-load latency together (`bound`: "issue").
             "roofline": {"bound": bound, "prescribed_bound": "hbm", "kernel": "k_extend", "achieved": ext_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ext_gbs / HBM_PEAK_GBS,
@@ -257,7 +279,7 @@ def main():
                                                                   [e / max(1, cst["waveItersExtend"]) for e in cst["extendEvents"]])),
                          "work_slots_per_quad_iteration": (cst["nodeVisitsExtend"] + cst["leafVisitsExtend"]) / max(1, 16 * cst["waveItersExtend"])},
             "build": g.build_stats(),
-        }
+        })
         if world == 1 and not args.skip_roofline_steps:
             # beyond the headline (after the timed region, not part of `value`): the realtime mode's two path-tracing passes on the same scene and frame size, one sub-sample
             try:
@@ -316,6 +338,20 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_PIXELS = 1 << 21      # of the 8.3 M pixels of the 4K frame: 32 MB of radiance + 16 MB of pixel indices
+
+
+def dump_outputs(d, frame, st):
+    """--dump-outputs: what the last timed step hands a caller — the RGBA32F radiance frame (a fixed, seeded sample of DUMP_PIXELS pixels when it has more,
+    with their row-major indices) and the ray counts pt_render returned. The same arguments give the same sample, so two builds compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    px = frame.reshape(-1, 4)
+    idx = np.arange(px.shape[0]) if px.shape[0] <= DUMP_PIXELS else np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_PIXELS, replace=False))
+    np.save(os.path.join(d, "radiance.npy"), np.ascontiguousarray(px[idx], np.float32))
+    np.save(os.path.join(d, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "rays.npy"), np.array([st["extendRays"], st["shadowRays"]], np.float64))
 
 
 def cpu_baseline(sc, cam, S, W, H, SPP):
