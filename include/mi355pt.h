@@ -359,6 +359,53 @@ int32_t pt_unpack_stable_plane_guides(pt_context* ctx, const void* deviceSrc, si
 /* copies the last pass's buffers to the host; any pointer may be NULL. planeCapacity in records (>= 3 x plane stride); the two RGBA16F targets as 4 binary16 bit patterns per pixel */
 int32_t pt_get_stable_planes(pt_context* ctx, uint32_t* header, PtStablePlane* planes, size_t planeCapacity, uint16_t* stableRadiance, float* depth, float* specularHitT,
                              uint16_t* motionVectors, uint32_t* throughput);
+/* ---- Denoiser inputs and the final merge of a realtime stable-plane frame (Rtxpt/ProcessingPasses/PostProcess.hlsl). All passes run on the device over the context's plane
+ * buffers in place, on the frame the last pt_build_stable_planes / pt_fill_stable_planes (/ pt_denoise_spec_hit_t) left. Allowed on an unsharded context, or on a sharded one once the
+ * whole frame's planes have arrived (pt_gather_stable_planes, pt_unpack_stable_planes): the NRD pass reads neighbours. Otherwise, and before a build pass, PT_ERROR_NOT_READY.
+ * The output colour is the context's RGBA32F radiance buffer (the reference's is RGBA16F; pt_map_radiance / pt_tonemap / pt_gather read it, it counts as one accumulated sample).
+ * The denoiser buffers are allocated, zeroed, by the first prepare call of a frame size; a pixel a pass does not write keeps its value, as a render target does. */
+typedef struct PtDenoiserParams {                 /* what the passes read of the frame's constants besides PtStablePlanesParams (Sample.cpp:1509-1540) */
+    float matWorldToView[16];                     /* PlanarViewConstants::matWorldToView (row vectors, row-major): the NRD viewZ */
+    float preExposedGrayLuminance;                /* ptConsts.preExposedGrayLuminance */
+    float denoiserRadianceClampK;                 /* ptConsts.denoiserRadianceClampK (UI default 8) */
+    float DLSSRRBrightnessClampK;                 /* already multiplied by the grey luminance, as Sample.cpp:1526 does (UI default 4096) */
+    float stablePlanesSuppressPrimaryIndirectSpecularK;   /* 0.6 when m_ui.StablePlanesSuppressPrimaryIndirectSpecular is on, else 0 (Sample.cpp:1536, SampleUI.h:217-218, 282-283) */
+} PtDenoiserParams;
+/* identity view matrix, preExposedGrayLuminance 1, denoiserRadianceClampK 8, DLSSRRBrightnessClampK 4096 x 1, suppression 0.6 */
+int32_t pt_denoiser_default_params(PtDenoiserParams* out);
+/* The denoiser buffers, each width x height in scan-line order. For pt_get_denoiser_inputs the pointers are host memory (tightly packed rows, NULL: skip, pitch ignored); from
+ * pt_denoiser_device_buffers they are the device buffers and pitch[i] the row pitch in bytes of the i-th pointer, in the order below. */
+typedef struct PtDenoiserBuffers {
+    void* rrDiffuseAlbedo;            /* uint32 R11G11B10F        (u_RRDiffuseAlbedo) */
+    void* rrSpecularAlbedo;           /* uint32 R11G11B10F        (u_RRSpecAlbedo) */
+    void* rrNormalRoughness;          /* 4 x binary16             (u_RRNormalsAndRoughness: normal, mixed roughness) */
+    void* rrSpecularMotionVectors;    /* 2 x binary16             (u_RRSpecMotionVectors) */
+    void* nrdViewZ;                   /* float                    (u_DenoiserViewspaceZ; FLT_MAX where the plane has no surface) */
+    void* nrdMotionVectors;           /* 4 x binary16             (u_DenoiserMotionVectors: the plane's, w = 0) */
+    void* nrdNormalRoughness;         /* 4 x float                (normal, finalRoughness: the arguments of NRD_FrontEnd_PackNormalAndRoughness) */
+    void* nrdDiffRadianceHitDist;     /* 4 x float                (demodulated clamped diffuse radiance, 0: RELAX_ / REBLUR_FrontEnd_PackRadiance...) */
+    void* nrdSpecRadianceHitDist;     /* 4 x float                (demodulated suppressed clamped specular radiance, specHitT) */
+    void* nrdRoughness;               /* float                    (the plane's raw roughness, REBLUR_FrontEnd_GetNormHitDist's last argument) */
+    void* nrdDisocclusionThresholdMix;    /* uint8 R8_UNORM */
+    void* nrdCombinedHistoryClampRelax;   /* uint8 R8_UNORM */
+    size_t pitch[12];
+} PtDenoiserBuffers;
+/* DENOISER_PREPARE_INPUTS with DENOISER_DLSS_RR (PostProcess.hlsl:198-440; Sample.cpp:2712-2719): main input colour (stable radiance + the noisy radiance of every plane that hit a
+ * surface, clamped by DLSSRRBrightnessClampK) into the radiance buffer; diffuse / specular albedo, normal and roughness from the throughput-weighted plane mix; specular motion vectors
+ * (ComputeSpecularMotionVector, :94-159) from the specular hit distance. */
+int32_t pt_denoiser_prepare_dlss_rr(pt_context* ctx, const PtStablePlanesParams* sp, const PtDenoiserParams* params);
+/* DENOISER_PREPARE_INPUTS for NRD, one plane (PostProcess.hlsl:442-573). Sample::Denoise (Sample.cpp:2561-2619, loop at :2589) calls it for planes activeCount - 1 down to 0 with
+ * initWithStableRadiance set on the first call only: that call writes the stable radiance to the output colour and clears CombinedHistoryClampRelax (the reference clears it once per
+ * frame, RenderTargets::Clear, Sample.cpp:2130). Plane p's viewZ uses the camera ray of sample index buildSampleIndex + p (Bridge::getSampleIndex with params.x = p). The R8_UNORM
+ * stores round clamp(x, 0, 1) x 255 to nearest, ties to even. */
+int32_t pt_denoiser_prepare_nrd(pt_context* ctx, const PtStablePlanesParams* sp, const PtDenoiserParams* params, uint32_t planeIndex, uint32_t initWithStableRadiance);
+/* DENOISER_FINAL_MERGE (PostProcess.hlsl:577-690) + DenoiserNRD::PostDenoiseProcess (DenoiserNRD.hlsli:24-48) after NRD's own unpack: diffDevice / specDevice are the host's UNPACKED
+ * denoised radiance of the plane, RGBA32F, width x height, device memory. Where viewZ is not the sky marker: output colour += max(0, diff x diffBSDFEstimate + spec x specBSDFEstimate). */
+int32_t pt_denoiser_merge_nrd(pt_context* ctx, uint32_t planeIndex, const float* diffDevice, const float* specDevice);
+/* copies the denoiser buffers to the host (NULL members are skipped) */
+int32_t pt_get_denoiser_inputs(pt_context* ctx, const PtDenoiserBuffers* host);
+/* the device pointers and row pitches of the denoiser buffers, for a denoiser on the same device that reads them in place */
+int32_t pt_denoiser_device_buffers(pt_context* ctx, PtDenoiserBuffers* out);
 int32_t pt_neeat_reset(pt_context* ctx);                                                      /* LightsBaker::BakeSettings::ResetFeedback */
 int32_t pt_get_neeat_tables(pt_context* ctx, uint32_t tilesXY[2], uint32_t jitterXY[2], uint32_t* table, uint32_t tableCapacityWords);
 /* Tile-sharded frames (PtDeviceDesc.shardCount > 1; no reference analogue): a rank traces and feeds back for its own pixels, the baker's passes read whole neighbourhoods, so

@@ -37,6 +37,7 @@ EXPORTS = [
     "pt_scene_import_directional_lights", "pt_scene_import_instances", "pt_scene_import_geometries", "pt_scene_import_materials", "pt_scene_import_vertices", "pt_set_scene_directional_lights", "pt_scene_import_apply", "pt_scene_import_settings", "pt_average_luminance",
     "pt_default_tone_mapping_parameters", "pt_tonemap_from_parameters", "pt_scene_import_tone_mapping",
     "pt_stable_planes_plane_stride", "pt_build_stable_planes", "pt_fill_stable_planes", "pt_denoise_spec_hit_t", "pt_stable_planes_merge", "pt_get_stable_planes",
+    "pt_denoiser_default_params", "pt_denoiser_prepare_dlss_rr", "pt_denoiser_prepare_nrd", "pt_denoiser_merge_nrd", "pt_get_denoiser_inputs", "pt_denoiser_device_buffers",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -647,6 +648,30 @@ def bridge_camera(width, height, pos, direction, up, fov_y, near_z=0.01, far_z=1
     return cam
 
 
+# PtDenoiserParams (include/mi355pt.h): what the denoiser passes read of the frame's constants besides PtStablePlanesParams
+DENOISER_PARAMS_DTYPE = np.dtype([("matWorldToView", "<f4", 16), ("preExposedGrayLuminance", "<f4"), ("denoiserRadianceClampK", "<f4"), ("DLSSRRBrightnessClampK", "<f4"),
+                                  ("stablePlanesSuppressPrimaryIndirectSpecularK", "<f4")])
+# PtDenoiserBuffers' members in order: (key, numpy dtype, values per pixel)
+DENOISER_BUFFERS = (("rr_diffuse_albedo", np.uint32, 1), ("rr_specular_albedo", np.uint32, 1), ("rr_normal_roughness", np.uint16, 4), ("rr_specular_motion_vectors", np.uint16, 2),
+                    ("nrd_view_z", np.float32, 1), ("nrd_motion_vectors", np.uint16, 4), ("nrd_normal_roughness", np.float32, 4), ("nrd_diff_radiance_hit_dist", np.float32, 4),
+                    ("nrd_spec_radiance_hit_dist", np.float32, 4), ("nrd_roughness", np.float32, 1), ("nrd_disocclusion_threshold_mix", np.uint8, 1),
+                    ("nrd_combined_history_clamp_relax", np.uint8, 1))
+
+
+class PtDenoiserBuffers(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k, _, _ in DENOISER_BUFFERS] + [("pitch", ctypes.c_size_t * 12)]
+
+
+def denoiser_default_params(lib=None):
+    """pt_denoiser_default_params: identity view matrix, grey luminance 1, radiance clamp 8, DLSS-RR brightness clamp 4096, suppression 0.6"""
+    L = lib or load_library()
+    out = np.zeros((), DENOISER_PARAMS_DTYPE)
+    f = L.pt_denoiser_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_denoiser_default_params")
+    return out
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -861,6 +886,42 @@ class PathTracer:
         g = self.L.pt_get_stable_planes; g.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t] + [ctypes.c_void_p] * 5; g.restype = ctypes.c_int32
         self._chk(g(self.h, None, None, 0, None, None, _p(out), None, None), "pt_get_stable_planes")
         return out
+
+    def denoiser_prepare_dlss_rr(self, sp_params, params):
+        """pt_denoiser_prepare_dlss_rr: PostProcess.hlsl DENOISER_PREPARE_INPUTS with DENOISER_DLSS_RR over the context's planes. sp_params: scenes.STABLE_PLANES_PARAMS_DTYPE,
+        params: DENOISER_PARAMS_DTYPE. The main input colour goes to the radiance buffer (radiance()); the guides: get_denoiser_inputs()."""
+        prm = np.ascontiguousarray(sp_params); dn = np.ascontiguousarray(params); assert prm.dtype.itemsize == 224 and dn.dtype == DENOISER_PARAMS_DTYPE
+        f = self.L.pt_denoiser_prepare_dlss_rr; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(prm), _p(dn)), "pt_denoiser_prepare_dlss_rr")
+
+    def denoiser_prepare_nrd(self, sp_params, params, plane_index, init_with_stable_radiance):
+        """pt_denoiser_prepare_nrd: PostProcess.hlsl DENOISER_PREPARE_INPUTS for NRD, one plane (Sample::Denoise calls planes active - 1 .. 0, init on the first call only)"""
+        prm = np.ascontiguousarray(sp_params); dn = np.ascontiguousarray(params); assert prm.dtype.itemsize == 224 and dn.dtype == DENOISER_PARAMS_DTYPE
+        f = self.L.pt_denoiser_prepare_nrd; f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(prm), _p(dn), int(plane_index), 1 if init_with_stable_radiance else 0), "pt_denoiser_prepare_nrd")
+
+    def denoiser_merge_nrd(self, plane_index, diff_device_ptr, spec_device_ptr):
+        """pt_denoiser_merge_nrd: DENOISER_FINAL_MERGE of one plane; the two arguments are device pointers (ints) to the host's unpacked denoised radiance, RGBA32F, h x w"""
+        f = self.L.pt_denoiser_merge_nrd; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, int(plane_index), ctypes.c_void_p(diff_device_ptr), ctypes.c_void_p(spec_device_ptr)), "pt_denoiser_merge_nrd")
+
+    def get_denoiser_inputs(self, keys=None):
+        """pt_get_denoiser_inputs: {key: array} for the keys of DENOISER_BUFFERS (all of them by default); [h, w] or [h, w, n]"""
+        h, w = self.height, self.width
+        out, b = {}, PtDenoiserBuffers()
+        for k, dt, n in DENOISER_BUFFERS:
+            if keys is not None and k not in keys: continue
+            out[k] = np.zeros((h, w) if n == 1 else (h, w, n), dt); setattr(b, k, out[k].ctypes.data)
+        f = self.L.pt_get_denoiser_inputs; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(b)), "pt_get_denoiser_inputs")
+        return out
+
+    def denoiser_device_buffers(self):
+        """pt_denoiser_device_buffers: {key: (device pointer, row pitch in bytes)}"""
+        b = PtDenoiserBuffers()
+        f = self.L.pt_denoiser_device_buffers; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(b)), "pt_denoiser_device_buffers")
+        return {k: (getattr(b, k), int(b.pitch[i])) for i, (k, _, _) in enumerate(DENOISER_BUFFERS)}
 
     def set_neeat(self, enable=True, global_feedback_weight=0.75, ratio=0.65, ssc_threshold=0.3, prefilter=True):
         """NEE-AT with the light baker in the loop (pt_set_neeat): every sample of render() becomes a frame — feedback passes, then the path tracer"""

@@ -8,6 +8,7 @@
 #endif
 #include "pt_wavefront.h"
 #include "pt_stableplanes_launch.h"
+#include "pt_denoiser.h"
 #include "pt_build.h"
 #include <rocprim/rocprim.hpp>
 #include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
@@ -169,6 +170,10 @@ struct pt_context {
     uint poolCapacity = 0; size_t shadowCapacity = 0;
     // stable planes (pt_build_stable_planes): the realtime mode's per-frame buffers (RenderTargets.cpp:60-141, 340-352) of the last pre-pass
     DevBuf<uint> dSpHeader, dSpThroughput; DevBuf<ptk::StablePlane> dSpPlanes; DevBuf<ptk::uint2> dSpRadiance, dSpMotion; DevBuf<float> dSpDepth, dSpHitT; uint spW = 0, spH = 0; DevBuf<ptk::uint4> dSpMark; DevBuf<ptk::float4> dSpNewL; DevBuf<float> dSpScratch; DevBuf<uint> dSpGatherSend, dSpGatherRecv, dSpGatherPixels; uint spGatherW = 0, spGatherH = 0; bool spGathered = false;      // (the last two: scratch of the fill passes)
+    // the denoiser buffers (pt_denoiser_prepare_dlss_rr / _nrd, pt_denoiser.h), allocated zeroed for a frame size by the first prepare call
+    DevBuf<uint> dDnRRDiff, dDnRRSpec, dDnRRSpecMV; DevBuf<ptk::uint2> dDnRRNormal, dDnMotion; DevBuf<float> dDnViewZ, dDnRoughness; DevBuf<ptk::float4> dDnNormal, dDnDiff, dDnSpec;
+    DevBuf<unsigned char> dDnDisocclusion, dDnHistoryClamp; uint dnW = 0, dnH = 0;
+    uint spSampleBase = 0;      // the sample index of the last build pass: Bridge::getSampleIndex's sampleBaseIndex for the NRD pass's camera rays
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels; std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
 };
@@ -769,6 +774,7 @@ int32_t pt_destroy(pt_context* c) {
     (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream);
     if (c->comm && g_rccl.lib) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
+    c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
     c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
     if (c->bvhAllocated) bvh_free(c->bvh);
@@ -1573,7 +1579,7 @@ int32_t pt_build_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStab
         c->spW = c->width; c->spH = c->height;
     }
     sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
-    c->spGathered = false;
+    c->spGathered = false; c->spSampleBase = sampleIndex;
     if (!numOwned) return PT_OK;
     PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
     PathPool pool{c->dS0.p, c->dS1.p, c->dS2.p, c->dS3.p, c->dS4.p, c->dHit.p};
@@ -1936,6 +1942,103 @@ int32_t pt_get_stable_planes(pt_context* c, uint32_t* header, PtStablePlane* pla
     if (specularHitT) PT_CHECK_HIP(c, hipMemcpy(specularHitT, c->dSpHitT.p, 4 * N, hipMemcpyDeviceToHost));
     if (motionVectors) PT_CHECK_HIP(c, hipMemcpy(motionVectors, c->dSpMotion.p, 8 * N, hipMemcpyDeviceToHost));
     if (throughput) PT_CHECK_HIP(c, hipMemcpy(throughput, c->dSpThroughput.p, 4 * N, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+// ---- the denoiser passes of a realtime frame (pt_denoiser.h / pt_denoiser.hip; PostProcess.hlsl DENOISER_PREPARE_INPUTS, DENOISER_FINAL_MERGE)
+static_assert(sizeof(::PtDenoiserParams) == sizeof(ptk::DenoiserParams), "denoiser ABI");
+int32_t pt_denoiser_default_params(PtDenoiserParams* out) {
+    if (!out) return PT_ERROR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    for (int i = 0; i < 4; i++) out->matWorldToView[i * 5] = 1.0f;
+    out->preExposedGrayLuminance = 1.0f; out->denoiserRadianceClampK = 8.0f; out->DLSSRRBrightnessClampK = 4096.0f * out->preExposedGrayLuminance;
+    out->stablePlanesSuppressPrimaryIndirectSpecularK = 0.6f;
+    return PT_OK;
+}
+// the planes of the whole frame must be here: an unsharded context, or a sharded one after pt_gather_stable_planes / pt_unpack_stable_planes (the NRD pass reads neighbours)
+static int32_t dn_ready(pt_context* c) {
+    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes, pt_fill_stable_planes");
+    if (c->shardCount > 1 && !c->spGathered) return fail(c, PT_ERROR_NOT_READY, "the denoiser passes read the whole frame's planes: pt_gather_stable_planes / pt_unpack_stable_planes first");
+    return PT_OK;
+}
+static ptk::DenoiserBuffers dn_buffers(pt_context* c) {
+    ptk::DenoiserBuffers D;
+    D.RRDiffuseAlbedo = c->dDnRRDiff.p; D.RRSpecAlbedo = c->dDnRRSpec.p; D.RRNormalsAndRoughness = c->dDnRRNormal.p; D.RRSpecMotionVectors = c->dDnRRSpecMV.p;
+    D.ViewZ = c->dDnViewZ.p; D.MotionVectors = c->dDnMotion.p; D.NormalRoughness = c->dDnNormal.p; D.DiffRadianceHitDist = c->dDnDiff.p; D.SpecRadianceHitDist = c->dDnSpec.p;
+    D.Roughness = c->dDnRoughness.p; D.DisocclusionThresholdMix = c->dDnDisocclusion.p; D.CombinedHistoryClampRelax = c->dDnHistoryClamp.p;
+    return D;
+}
+static int32_t dn_alloc(pt_context* c) {
+    if (c->dnW == c->width && c->dnH == c->height) return PT_OK;
+    const size_t N = (size_t)c->width * c->height;
+    PT_CHECK_HIP(c, c->dDnRRDiff.resize(N)); PT_CHECK_HIP(c, c->dDnRRSpec.resize(N)); PT_CHECK_HIP(c, c->dDnRRSpecMV.resize(N)); PT_CHECK_HIP(c, c->dDnRRNormal.resize(N));
+    PT_CHECK_HIP(c, c->dDnMotion.resize(N)); PT_CHECK_HIP(c, c->dDnViewZ.resize(N)); PT_CHECK_HIP(c, c->dDnRoughness.resize(N)); PT_CHECK_HIP(c, c->dDnNormal.resize(N));
+    PT_CHECK_HIP(c, c->dDnDiff.resize(N)); PT_CHECK_HIP(c, c->dDnSpec.resize(N)); PT_CHECK_HIP(c, c->dDnDisocclusion.resize(N)); PT_CHECK_HIP(c, c->dDnHistoryClamp.resize(N));
+    hipStream_t st = c->stream;
+    PT_CHECK_HIP(c, hipMemsetAsync(c->dDnRRDiff.p, 0, 4 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnRRSpec.p, 0, 4 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnRRSpecMV.p, 0, 4 * N, st));
+    PT_CHECK_HIP(c, hipMemsetAsync(c->dDnRRNormal.p, 0, 8 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnMotion.p, 0, 8 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnViewZ.p, 0, 4 * N, st));
+    PT_CHECK_HIP(c, hipMemsetAsync(c->dDnRoughness.p, 0, 4 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnNormal.p, 0, 16 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnDiff.p, 0, 16 * N, st));
+    PT_CHECK_HIP(c, hipMemsetAsync(c->dDnSpec.p, 0, 16 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnDisocclusion.p, 0, N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dDnHistoryClamp.p, 0, N, st));
+    c->dnW = c->width; c->dnH = c->height;
+    return PT_OK;
+}
+static StablePlanesContext dn_planes(pt_context* c, const PtStablePlanesParams* params) {
+    ptk::StablePlanesParams prm; memcpy(&prm, params, sizeof(prm));
+    StablePlanesContext sp; sp.C = ptk::SP_make_consts(prm, c->width, c->height, c->S.bounceCount); memset(&sp.B, 0, sizeof(sp.B));
+    sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
+    return sp;
+}
+int32_t pt_denoiser_prepare_dlss_rr(pt_context* c, const PtStablePlanesParams* spParams, const PtDenoiserParams* params) {
+    if (!c || !spParams || !params) return PT_ERROR_INVALID_ARGUMENT;
+    int32_t r = dn_ready(c); if (r != PT_OK) return r;
+    (void)hipSetDevice(c->device);
+    r = dn_alloc(c); if (r != PT_OK) return r;
+    ptk::DenoiserParams P; memcpy(&P, params, sizeof(P));
+    launch_dn_prepare_dlss_rr(dn_planes(c, spParams), P, dn_buffers(c), c->dAccum.p, c->stream);
+    c->accumCount = 1;      // the radiance buffer holds one finished frame (as after pt_stable_planes_merge)
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
+    return PT_OK;
+}
+int32_t pt_denoiser_prepare_nrd(pt_context* c, const PtStablePlanesParams* spParams, const PtDenoiserParams* params, uint32_t planeIndex, uint32_t initWithStableRadiance) {
+    if (!c || !spParams || !params) return PT_ERROR_INVALID_ARGUMENT;
+    if (planeIndex >= cStablePlaneCount) return fail(c, PT_ERROR_INVALID_ARGUMENT, "plane index out of range (0..2)");
+    int32_t r = dn_ready(c); if (r != PT_OK) return r;
+    (void)hipSetDevice(c->device);
+    r = dn_alloc(c); if (r != PT_OK) return r;
+    ptk::DenoiserParams P; memcpy(&P, params, sizeof(P));
+    PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
+    launch_dn_prepare_nrd(k, dn_planes(c, spParams), P, dn_buffers(c), planeIndex, initWithStableRadiance != 0u, c->spSampleBase, c->dAccum.p, c->stream);
+    if (initWithStableRadiance) c->accumCount = 1;
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
+    return PT_OK;
+}
+int32_t pt_denoiser_merge_nrd(pt_context* c, uint32_t planeIndex, const float* diffDevice, const float* specDevice) {
+    if (!c || !diffDevice || !specDevice) return PT_ERROR_INVALID_ARGUMENT;
+    if (planeIndex >= cStablePlaneCount) return fail(c, PT_ERROR_INVALID_ARGUMENT, "plane index out of range (0..2)");
+    int32_t r = dn_ready(c); if (r != PT_OK) return r;
+    if (c->dnW != c->width || c->dnH != c->height) return fail(c, PT_ERROR_NOT_READY, "the merge reads the NRD prepare pass's viewZ: pt_denoiser_prepare_nrd first");
+    (void)hipSetDevice(c->device);
+    launch_dn_merge_nrd(sp_buffers(c), dn_buffers(c), planeIndex, (const ptk::float4*)diffDevice, (const ptk::float4*)specDevice, c->dAccum.p, c->stream);
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
+    return PT_OK;
+}
+int32_t pt_get_denoiser_inputs(pt_context* c, const PtDenoiserBuffers* host) {
+    if (!c || !host) return PT_ERROR_INVALID_ARGUMENT;
+    if (!c->dnW || c->dnW != c->width || c->dnH != c->height) return fail(c, PT_ERROR_NOT_READY, "no denoiser inputs of this frame size yet: pt_denoiser_prepare_dlss_rr / pt_denoiser_prepare_nrd");
+    (void)hipSetDevice(c->device);
+    PtDenoiserBuffers dev; memset(&dev, 0, sizeof(dev)); (void)pt_denoiser_device_buffers(c, &dev);
+    void* const* d = &dev.rrDiffuseAlbedo; void* const* h = &host->rrDiffuseAlbedo;
+    for (int i = 0; i < 12; i++) if (h[i]) PT_CHECK_HIP(c, hipMemcpy(h[i], d[i], dev.pitch[i] * c->height, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+int32_t pt_denoiser_device_buffers(pt_context* c, PtDenoiserBuffers* out) {
+    if (!c || !out) return PT_ERROR_INVALID_ARGUMENT;
+    if (!c->dnW || c->dnW != c->width || c->dnH != c->height) return fail(c, PT_ERROR_NOT_READY, "no denoiser inputs of this frame size yet: pt_denoiser_prepare_dlss_rr / pt_denoiser_prepare_nrd");
+    const ptk::DenoiserBuffers D = dn_buffers(c);
+    void* p[12] = {D.RRDiffuseAlbedo, D.RRSpecAlbedo, D.RRNormalsAndRoughness, D.RRSpecMotionVectors, D.ViewZ, D.MotionVectors, D.NormalRoughness, D.DiffRadianceHitDist,
+                   D.SpecRadianceHitDist, D.Roughness, D.DisocclusionThresholdMix, D.CombinedHistoryClampRelax};
+    static const size_t bytes[12] = {4, 4, 8, 4, 4, 8, 16, 16, 16, 4, 1, 1};
+    void** o = &out->rrDiffuseAlbedo;
+    for (int i = 0; i < 12; i++) { o[i] = p[i]; out->pitch[i] = bytes[i] * c->width; }
     return PT_OK;
 }
 int32_t pt_map_radiance(pt_context* c, const float** rgba, size_t* pitch) {
