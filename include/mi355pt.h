@@ -130,6 +130,7 @@ typedef struct PtDeviceDesc {
 #define PT_DEVICE_HOST_SAH_BUILDER 4u       /* the fast-trace tree of round 2 instead: binned-SAH topology + insertion-based optimisation on the host's cores
                                                (1.8 s at 2.8 M triangles, the same trace speed within 0.2 %); bounds, collapse and refit on the device as always */
 
+/* pt_render fills every field; pt_build_stable_planes / pt_fill_stable_planes fill the same fields from the same counters (no tail launches, no per-launch times). */
 typedef struct PtFrameStats {
     uint64_t extendRays, shadowRays, hits;                  /* "rays" of the Mrays/s metric = extendRays + shadowRays */
     uint64_t nodeVisitsExtend, triTestsExtend, nodeVisitsShadow, triTestsShadow;   /* in-kernel BVH counters (when enabled) */
@@ -699,8 +700,10 @@ int32_t pt_set_tail_paths(pt_context* ctx, uint32_t maxPaths);
 /* Fused traversal launches: the visibility rays of path vertex k (Bridge::traceVisibilityRay, PathTracerNEE.hlsli:185-275) are traced in the same launch as the closest-hit rays of
    vertex k + 1 (Bridge::traceScatterRay) — blocks of either kind side by side, straggler rounds and resolve passes shared — instead of in a launch of their own; their contributions
    land before vertex k + 1 is shaded, as before, so the image does not depend on the mode (tests/test_gpu_fused_traversal.py). Launch composition only: it halves the traversal
-   launches of a bounce, which is what a small frame (one rank of a tile-sharded frame) is bound by. mode 0 = off, 1 = on, 2 = by the size of the pt_render call (default; environment
-   MI355PT_FUSED_TRAVERSAL overrides it at pt_create). Ignored for NEEFullSamples > 1, serial-kernel and counter frames. */
+   launches of a bounce, which is what a small frame (one rank of a tile-sharded frame) is bound by. mode 0 = off, 1 = on (default), 2 = by the size of the pt_render call
+   (environment MI355PT_FUSED_TRAVERSAL overrides it at pt_create). Ignored for NEEFullSamples > 1, serial-kernel and counter frames.
+   The same frames keep the live paths' state compacted by queue position from the second bounce on (on by default; environment MI355PT_COMPACT_POOL=0 switches it off at
+   pt_create; not with NEE-AT). It costs memory: five more uint4 arrays per path, 80 bytes on top of the pool's 96. */
 int32_t pt_set_fused_traversal(pt_context* ctx, uint32_t mode);
 
 #ifdef __cplusplus

@@ -1025,7 +1025,8 @@ class PathTracer:
         self._chk(self.L.pt_set_tail_paths(self.h, int(max_paths)), "pt_set_tail_paths")
 
     def set_fused_traversal(self, mode):
-        """pt_set_fused_traversal: 0 = visibility rays in launches of their own, 1 = in the next bounce's closest-hit launch (k_trace_pair), 2 = by the size of the call (default)."""
+        """pt_set_fused_traversal: 0 = visibility rays in launches of their own, 1 = in the next bounce's closest-hit launch (k_trace_pair), 2 = by the size of the call. Default 1.
+        The same frames keep the live paths compacted by queue position (environment MI355PT_COMPACT_POOL=0 at pt_create: off), at five more uint4 arrays per path."""
         self._chk(self.L.pt_set_fused_traversal(self.h, int(mode)), "pt_set_fused_traversal")
 
     def tonemap(self, params=None):

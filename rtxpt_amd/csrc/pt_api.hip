@@ -1,24 +1,18 @@
-// mi355pt — C-ABI implementation (include/mi355pt.h): context, scene upload, BVH build/refit orchestration, light baking,
-// the wavefront frame loop and read-back. Host side of the seam `Sample` implements in the reference
+// mi355pt — C-ABI implementation (include/mi355pt.h): context, scene upload, BVH build/refit orchestration, light baking and
+// read-back; the frame drivers (pt_render and the realtime passes) are in pt_frame.hip. Host side of the seam `Sample` implements in the reference
 // (Rtxpt/Sample.cpp:1891-2313 Render, :2438-2559 PathTrace, :1464-1556 UpdatePathTracerConstants, :2770-2778 accumulation).
 // There is NO CPU fallback: every entry point that needs the device fails with PT_ERROR_NO_DEVICE / PT_ERROR_HIP.
-#include "../../include/mi355pt.h"
+#include <cstring>
+#include <rocprim/rocprim.hpp>      // before pt_context.h: its `using namespace ptk` makes rocprim's own uint2 / uint4 ambiguous
+#include "pt_context.h"
 #ifdef MI355PT_TEST_HOOKS
 #include "../../include/mi355pt_testhooks.h"
 #endif
-#include "pt_wavefront.h"
-#include "pt_stableplanes_launch.h"
 #include "pt_denoiser.h"
-#include "pt_build.h"
-#include <rocprim/rocprim.hpp>
-#include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
 #include <dlfcn.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
 #include <chrono>
 
 using namespace ptk;
@@ -31,157 +25,6 @@ static_assert(sizeof(::PtInstanceDesc) == sizeof(ptk::InstanceDesc), "instance A
 static_assert(sizeof(::PolymorphicLightInfo) == sizeof(ptk::PolymorphicLightInfo), "light ABI");
 
 namespace {
-
-template <typename T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    hipError_t resize(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-        if (e == hipSuccess) n = count ? count : 1;
-        return e;
-    }
-    hipError_t upload(const T* src, size_t count, hipStream_t st) {
-        hipError_t e = resize(count); if (e != hipSuccess) return e;
-        if (!count) return hipSuccess;
-        return hipMemcpyAsync(p, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
-    }
-    hipError_t upload(const std::vector<T>& v, hipStream_t st) { return upload(v.data(), v.size(), st); }
-    void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-struct HostTexture { uint w, h, mipLevels; std::vector<std::vector<ptk::float4>> mips; };
-
-static const uint TILE = 32;
-static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per queue (2 queues per pipelined batch, 16 B each)
-#ifndef PT_SHARD_TILE_GROUP
-#define PT_SHARD_TILE_GROUP 1      // consecutive Morton-ordered 32x32 tiles dealt to the same rank (locality vs load balance)
-#endif
-#ifndef PT_PIPELINE_FULL_AT
-// paths per pt_render call from which all PT_PIPELINE_BATCHES are used (one rank of an 8-way sharded 4K frame has 4.1 M)
-#define PT_PIPELINE_FULL_AT (1u << 21)
-#endif
-#ifndef PT_PIPELINE_MID_BATCHES
-#define PT_PIPELINE_MID_BATCHES 2      // batches between 1 M paths and PT_PIPELINE_FULL_AT
-#endif
-#ifndef PT_CLASSIFY_FROM
-// passes with fewer paths skip k_classify (class-ordered shading pays through coherence, which a handful of waves do not have)
-#define PT_CLASSIFY_FROM 65536u
-#endif
-#ifndef PT_SP_FILL_CLASSES
-#define PT_SP_FILL_CLASSES 1     // the stable-plane fill pass shades in class order (k_classify), like reference mode; 0: queue order (A/B)
-#endif
-#ifndef PT_SP_FILL_RANGED
-// the fill pass's first traversal launch uses FirstHitFromVBuffer's narrowed ray interval (pt_stableplanes.h firstHitInterval); 0: the whole ray (A/B) — same
-// hits
-#define PT_SP_FILL_RANGED 1
-#endif
-#ifndef PT_TAIL_PATHS
-// a batch with at most this many live paths is finished by the tail kernel (pt_tail.hip, pt_set_tail_paths); 0: never. 32768 in rounds 4-5; with fused
-// traversal
-#define PT_TAIL_PATHS 4096u
-                                  // launches and free-running small passes (round 6) a pass of tens of thousands of paths is cheaper as a wavefront pass than
-                                  // in the tail kernel's under-filled GPU (rank of eight 12.56 -> 12.11 ms without it), while the chains of passes that hold a
-                                  // few hundred paths each — nested-dielectric re-traces: C5 runs 19 passes, twelve of them below 10 k paths at ~0.25 ms each —
-                                  // are what the kernel is for: 4096 takes C5's rank of eight 13.9 -> 13.2 ms, C3's 12.0 -> 11.8
-                                  // (profiles/r06o_tail_small_ab.txt)
-#endif
-#ifndef PT_FUSED_TRAVERSAL
-// pt_set_fused_traversal (default: on — it pays at every size, profiles/r06b_fused_traversal_ab.txt): 0 = every bounce traces its visibility rays in a launch
-// of their own, 1 = together with the closest-hit rays of the next bounce
-#define PT_FUSED_TRAVERSAL 1u
-#endif                              // (k_trace_pair, pt_wavefront.hip), 2 = by the size of the call (PT_FUSED_BELOW)
-#ifndef PT_FUSED_BELOW
-// mode 2: calls of fewer paths than this fuse (one rank of a 4- or 8-way sharded 4K frame, 1080p frames); a full 4K x 4 spp frame (33 M) keeps its own launches
-#define PT_FUSED_BELOW (12u << 20)
-#endif
-#ifndef PT_COMPACT_POOL
-#define PT_COMPACT_POOL 1      // pt_render keeps the live paths' state compacted by queue position (ptk::PathPool::home; environment MI355PT_COMPACT_POOL overrides)
-#endif
-#ifndef PT_FREE_RUN_BELOW
-// pt_render: once every live batch holds fewer paths than this, the batches stop advancing in lockstep (0: lockstep to the end)
-#define PT_FREE_RUN_BELOW (1u << 22)
-#endif
-#ifndef PT_PIPELINE_BATCHES
-#define PT_PIPELINE_BATCHES 4      // independent sub-frame batches pt_render keeps in flight on separate streams (A/B on C3 in DESIGN.md)
-#endif
-// a full task queue is reported as an error (pt_render), it does not silently disable splitting
-} // namespace
-
-struct pt_context {
-    int device = 0; hipStream_t stream = nullptr; uint shardRank = 0, shardCount = 1;
-    hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false; uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0;   // second half-frame batch (pt_render pipelines two batches)
-    std::string lastError;
-    // host copies of the scene (kept for re-bake / animation)
-    std::vector<uint> indices; std::vector<float> positions; std::vector<ptk::float2> uvs; std::vector<uint> normals, tangents;
-    std::vector<GeometryDesc> geometries; std::vector<MeshDesc> meshes; std::vector<InstanceDesc> instances;
-    std::vector<ptk::PTMaterialData> materials; std::vector<HostTexture> textures; HostTexture envTex; bool envEnabled = false;
-    float3x4 envToWorld, envToLocal; ptk::float3 envColorMul;
-    // sceneDirLights: world-space lights of the loaded scene (pt_set_scene_directional_lights), converted at bake time
-    uint envCubeDim = 2048; std::vector<ptk::EnvDirectionalLight> envDirLights, sceneDirLights; bool envCubeDirty = true;
-    ptk::EnvCube envCube;      // EnvMapBaker state (pt_set_environment_bake)
-    std::vector<PolymorphicLightInfoFull> analyticLights;
-    std::vector<SubInstanceData> subInstances; std::vector<ptk::uint2> subInstToInstGeom; std::vector<ptk::uint2> primInfo; std::vector<uint> subInstFirstPrim;
-    std::vector<ptk::PolymorphicLightInfo> lights; std::vector<ptk::PolymorphicLightInfoEx> lightsEx; std::vector<uint> envLookup; uint envLookupDim = 0; uint numProxies = 0, envLightsBaked = 0;      // (light weights / proxy table live on the device only)
-    DevBuf<float> dLightW; DevBuf<uint> dProxyOffsets; void* dScanTemp = nullptr; size_t scanTempBytes = 0;
-    // device
-    DevBuf<uint> dIndices, dNormals, dTangents, dProxyCounters, dProxyIndices, dEnvLookup, dOwned, dQueue[2], dEmissiveList, dEmissiveOffsets;
-    // pt_set_motion_history: the previous frame's pose; the (first, count) vertex ranges in which it differs from the current one
-    DevBuf<float> dPrevPositions; DevBuf<InstanceDesc> dPrevInstances; bool motionHistory = false, prevAllStale = false; std::vector<uint32_t> prevStaleRanges;
-    DevBuf<float> dPositions; DevBuf<ptk::float2> dUvs; DevBuf<GeometryDesc> dGeometries; DevBuf<InstanceDesc> dInstances; DevBuf<SubInstanceData> dSubInstances;
-    DevBuf<ptk::AlphaPlane> dAlphaPlanes; DevBuf<unsigned char> dAlphaPool; DevBuf<ptk::ShadeTri> dShadeTris; DevBuf<ptk::uint2> dSubInstToInstGeom, dPrimInfo; DevBuf<ptk::PTMaterialData> dMaterials; DevBuf<TexInfo> dTexInfos; DevBuf<ptk::float4> dTexels;
-    bool skyEnabled = false; ptk::ProceduralSkyContext sky; DevBuf<ptk::float4> dSkyTex[4]; DevBuf<ptk::ProceduralSkyContext> dSky; DevBuf<ptk::uint2> dSkyLowRes;      // pt_set_procedural_sky
-    // pt_set_environment_cube: the environment image as a cube map (RGBA16F), uploaded by the setter
-    DevBuf<ptk::uint2> dEnvImageCube; uint envImageCubeDim = 0;
-    // envCompression: EnvMapBaker's BC6U compression (0 off, 1 fast)
-    DevBuf<ptk::uint2> dEnvCube, dEnvCubeSource; DevBuf<ptk::EnvDirectionalLight> dEnvDirLights; uint envCompression = 0;
-    DevBuf<ptk::PolymorphicLightInfo> dLights; DevBuf<ptk::PolymorphicLightInfoEx> dLightsEx;
-    // NEE-AT (pt_set_local_light_sampling): the screen-tile local samplers as the host hands them in, and the feedback reservoirs of the last pt_render call
-    // (one plane per sample)
-    DevBuf<uint> dLocalTable; uint localResX = 0, localResY = 0, localJitterX = 0, localJitterY = 0, localMaxLight = 0; float localRatio = 0.f, sscThreshold = 0.f; bool feedbackRequired = false;
-    DevBuf<float> dFbWeight; DevBuf<uint> dFbCand; DevBuf<ptk::float4> dSq3; uint fbSamples = 0;
-    ptk::LightFrustumBoost lightBoost = {}; bool weightsDirty = false;      // pt_set_light_importance_boost: ImportanceBooster's frustum term (mul 0: off)
-    // NEE-AT with the baker in the loop (pt_set_neeat): what LightsBaker keeps between frames (LightsBaker.h:225-260) and the textures / buffers its feedback
-    // passes bind
-    struct NeeAt {
-        bool enabled = false; float globalFeedbackWeight = 0.75f, localRatio = 0.65f, sscThreshold = 0.3f, dropoff = 0.005f, intensityDeltaMul = 64.0f; bool preFilter = true;
-        uint updateCounter = 0; float jitterF[2] = {0, 0}; uint jitter[2] = {0, 0}, prevJitter[2] = {0, 0};
-        bool feedbackFilled = false, lastFeedbackAvailable = false; uint historicTotalLightCount = 0, W = 0, H = 0, nHist = 0;
-        // between UpdateBegin and UpdateEnd of a frame (realtime mode: the build pass runs in between)
-        bool frameOpen = false, frameFeedbackAvailable = false, frameLocalAvailable = false, exportDepth = true; uint framePrevLightCount = 0;
-        DevBuf<float> fbW, scW, blW, snapW, curW, histW; DevBuf<uint> fbC, scC, blC, snapC, local, counters;
-        // the exported depth of the last traced frame / of the one before; columns 2 and 3 of pt_set_view_projection's matrix
-        DevBuf<float> depth, histDepth; bool haveClip = false; float clipZ[4] = {0, 0, 0, 0}, clipW[4] = {0, 0, 0, 0};
-        // tile-sharded frames: the exchange of the owned pixels' reservoirs between frames
-        DevBuf<uint> xSend, xRecv; DevBuf<uint> xPixels; uint xW = 0, xH = 0;
-        void reset() { W = H = 0; updateCounter = 0; jitterF[0] = jitterF[1] = 0; jitter[0] = jitter[1] = prevJitter[0] = prevJitter[1] = 0; feedbackFilled = lastFeedbackAvailable = false; frameOpen = false; exportDepth = true; historicTotalLightCount = 0; W = H = 0; nHist = 0; }
-        void free() { fbW.free(); scW.free(); blW.free(); snapW.free(); curW.free(); histW.free(); fbC.free(); scC.free(); blC.free(); snapC.free(); local.free(); counters.free(); xSend.free(); xRecv.free(); xPixels.free(); depth.free(); histDepth.free(); }
-    } neeat;
-    DevBuf<ptk::uint4> dS0, dS1, dS2, dS3, dS4, dHit, dS0b, dS1b, dS3b, dS4b, dHitb /* ...b: the second array set of a compacted pool (pt_render) */; DevBuf<ptk::float4> dSq0, dSq1, dSq2, dAccum, dScratch4; DevBuf<WaveCounters> dCounters; DevBuf<ptk::uint2> dTravSpill; DevBuf<ptk::TravTask> dTaskQ; DevBuf<uint> dTravCounts, dResolveList, dResolveListSh; DevBuf<unsigned long long> dBestKey, dBestKeySh; DevBuf<ptk::TravTask> dTaskQSh;      // ...Sh: the visibility rays' own straggler state in a frame of fused traversal launches
-    std::vector<TexInfo> texInfos; TexInfo envTexInfo;
-    BvhBuildBuffers bvh; bool bvhAllocated = false; uint numTris = 0; uint bvhBuilder = BVH_BUILDER_SAH;
-    DeviceScene dsc;
-    // frame state
-    ptk::PtSettings S; ptk::PathTracerCameraData cam; uint width = 0, height = 0, accumCount = 0; std::vector<uint> owned; std::vector<std::vector<uint>> shardPixels;
-    std::vector<float> hostRadiance; bool countersEnabled = false;
-    bool geomDirty = true, lightsDirty = true, texDirty = true;
-    double buildMs = 0, refitMs = 0, lightBakeMs = 0;
-    uint poolCapacity = 0; size_t shadowCapacity = 0;
-    // stable planes (pt_build_stable_planes): the realtime mode's per-frame buffers (RenderTargets.cpp:60-141, 340-352) of the last pre-pass
-    DevBuf<uint> dSpHeader, dSpThroughput; DevBuf<ptk::StablePlane> dSpPlanes; DevBuf<ptk::uint2> dSpRadiance, dSpMotion; DevBuf<float> dSpDepth, dSpHitT; uint spW = 0, spH = 0; DevBuf<ptk::uint4> dSpMark; DevBuf<ptk::float4> dSpNewL; DevBuf<float> dSpScratch; DevBuf<uint> dSpGatherSend, dSpGatherRecv, dSpGatherPixels; uint spGatherW = 0, spGatherH = 0; bool spGathered = false;      // (the last two: scratch of the fill passes)
-    // the denoiser buffers (pt_denoiser_prepare_dlss_rr / _nrd, pt_denoiser.h), allocated zeroed for a frame size by the first prepare call
-    DevBuf<uint> dDnRRDiff, dDnRRSpec, dDnRRSpecMV; DevBuf<ptk::uint2> dDnRRNormal, dDnMotion; DevBuf<float> dDnViewZ, dDnRoughness; DevBuf<ptk::float4> dDnNormal, dDnDiff, dDnSpec;
-    DevBuf<unsigned char> dDnDisocclusion, dDnHistoryClamp; uint dnW = 0, dnH = 0;
-    uint spSampleBase = 0;      // the sample index of the last build pass: Bridge::getSampleIndex's sampleBaseIndex for the NRD pass's camera rays
-    // frame gather (pt_comm_init / pt_gather)
-    ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels; std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
-};
-
-namespace {
-
-int fail(pt_context* c, int code, const std::string& msg) { if (c) c->lastError = msg; return code; }
-#define PT_CHECK_HIP(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 void build_mips(HostTexture& t) {
     uint lv = 1; { uint m = std::max(t.w, t.h); while (m > 1) { m >>= 1; lv++; } }
@@ -601,6 +444,8 @@ int bake_env_cube(pt_context* c) {
     c->envCubeDirty = false; c->lightsDirty = true;
     return PT_OK;
 }
+} // namespace
+
 int prepare(pt_context* c) {
     if (c->texDirty) { int r = upload_textures(c); if (r != PT_OK) return r; refresh_scene_view(c); c->lightsDirty = true; c->envCubeDirty = true; }
     if (c->envEnabled && c->envCubeDirty) { int r = bake_env_cube(c); if (r != PT_OK) return r; }
@@ -613,19 +458,6 @@ int prepare(pt_context* c) {
         refresh_scene_view(c);
     }
     c->weightsDirty = false;
-    return PT_OK;
-}
-int ensure_pool(pt_context* c, uint n, uint shadowPerPath) {      // shadowPerPath: shadow-queue entries a path vertex may emit (NEEFullSamples)
-    if (n <= c->poolCapacity && (size_t)n * shadowPerPath <= c->shadowCapacity) return PT_OK;
-    if (n < c->poolCapacity) n = c->poolCapacity;
-    const size_t ns = (size_t)n * shadowPerPath;
-    if (ns > 0xF0000000ull) return fail(c, PT_ERROR_INVALID_ARGUMENT, "too many shadow-queue entries in one pt_render call (paths x NEEFullSamples)");
-    PT_CHECK_HIP(c, c->dS0.resize(n)); PT_CHECK_HIP(c, c->dS1.resize(n)); PT_CHECK_HIP(c, c->dS2.resize(n)); PT_CHECK_HIP(c, c->dS3.resize(n)); PT_CHECK_HIP(c, c->dS4.resize(n));
-    PT_CHECK_HIP(c, c->dHit.resize(n)); PT_CHECK_HIP(c, c->dQueue[0].resize(n)); PT_CHECK_HIP(c, c->dQueue[1].resize(n));
-    PT_CHECK_HIP(c, c->dSq0.resize(ns)); PT_CHECK_HIP(c, c->dSq1.resize(ns)); PT_CHECK_HIP(c, c->dSq2.resize(ns));
-    PT_CHECK_HIP(c, c->dBestKey.resize(ns)); PT_CHECK_HIP(c, c->dResolveList.resize(ns));
-    PT_CHECK_HIP(c, c->dTaskQ.resize((size_t)PT_PIPELINE_BATCHES * 2 * TASK_QUEUE_CAPACITY)); PT_CHECK_HIP(c, c->dTravCounts.resize(PT_PIPELINE_BATCHES * PASS_COUNTERS));
-    c->poolCapacity = n; c->shadowCapacity = ns;
     return PT_OK;
 }
 
@@ -665,8 +497,7 @@ int neeat_exchange_feedback(pt_context* c) {
 // tile tables and the jitter. phases: NEEAT_BEGIN = LightsBaker::UpdateBegin (before the frame's G-buffer), NEEAT_END = UpdateEnd (after it, on the frame's
 // depth and motion vectors: Sample.cpp:2491-2494; pt_realtime_frame), NEEAT_BOTH = reference mode: nothing happens in between, UpdateEnd reads the depth the
 // last traced frame exported (depth == nullptr) and the motion vectors are zero
-enum { NEEAT_BEGIN = 1, NEEAT_END = 2, NEEAT_BOTH = 3 };
-int neeat_frame(pt_context* c, int phases = NEEAT_BOTH, const float* depth = nullptr, const ptk::uint2* motion = nullptr) {
+int neeat_frame(pt_context* c, int phases, const float* depth, const ptk::uint2* motion) {
     pt_context::NeeAt& st = c->neeat;
     const uint N = (uint)c->lights.size();
     // nothing to sample (no lights, or all of them dark): NEE does not run (LightSampler::IsEmpty), the frame is traced without a local layer
@@ -729,8 +560,6 @@ int neeat_frame(pt_context* c, int phases = NEEAT_BOTH, const float* depth = nul
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
-
-} // namespace
 
 extern "C" {
 
@@ -1251,496 +1080,11 @@ int32_t pt_animate_normals(pt_context* c, const uint32_t* normals, const uint32_
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
-// every additive field of PtFrameStats (a call that traces its samples one frame at a time — NEE-AT — reports the sums; maxima stay maxima)
-static void add_frame_stats(PtFrameStats& t, const PtFrameStats& o) {
-    t.extendRays += o.extendRays; t.shadowRays += o.shadowRays; t.hits += o.hits;
-    t.nodeVisitsExtend += o.nodeVisitsExtend; t.triTestsExtend += o.triTestsExtend; t.nodeVisitsShadow += o.nodeVisitsShadow; t.triTestsShadow += o.triTestsShadow;
-    t.leafVisitsExtend += o.leafVisitsExtend; t.waveItersExtend += o.waveItersExtend; t.leafVisitsShadow += o.leafVisitsShadow; t.waveItersShadow += o.waveItersShadow;
-    for (int q = 0; q < 4; q++) t.extendPhaseCycles[q] += o.extendPhaseCycles[q];
-    t.leafBlocksExtend += o.leafBlocksExtend; if (o.waveItersMaxExtend > t.waveItersMaxExtend) t.waveItersMaxExtend = o.waveItersMaxExtend;
-    for (int q = 0; q < 16; q++) t.extendRayIterHist[q] += o.extendRayIterHist[q];
-    for (uint q = 0; q < o.longRayCount && q < 32u && t.longRayCount < 32u; q++) { memcpy(t.longRays[t.longRayCount], o.longRays[q], 32); t.longRayCount++; }
-    for (int q = 0; q < 8; q++) t.extendEvents[q] += o.extendEvents[q];
-    t.gpuMilliseconds += o.gpuMilliseconds; t.extendKernelMs += o.extendKernelMs; t.shadeKernelMs += o.shadeKernelMs; t.shadowKernelMs += o.shadowKernelMs;
-    t.extendLaunches += o.extendLaunches; if (o.iterations > t.iterations) t.iterations = o.iterations;
-    t.pathsTraced += o.pathsTraced; t.tailLaunches += o.tailLaunches;
-}
-int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* stats) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    if (!count) return PT_OK;
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    // NEE-AT with the baker in the loop: every sample is a frame — baker passes, then the path tracer
-    if (c->neeat.enabled && c->S.NEEEnabled && c->S.NEEFullSamples != 0u) {
-        if (count > 1) {
-            PtFrameStats total; memset(&total, 0, sizeof(total));
-            for (uint32_t s = 0; s < count; s++) {
-                PtFrameStats one; r = pt_render(c, first + s, 1, &one);
-                // (the samples before the failing one were accumulated: their counts are reported)
-                if (r != PT_OK) { if (stats) *stats = total; return r; }
-                add_frame_stats(total, one);
-            }
-            if (stats) *stats = total;
-            return PT_OK;
-        }
-        // (tile shards with a communicator; a host without one exchanges through pt_neeat_pack / unpack_feedback)
-        r = neeat_exchange_feedback(c); if (r != PT_OK) return r;
-        r = neeat_frame(c); if (r != PT_OK) return r;
-    }
-    uint numOwned = (uint)c->owned.size();
-    if ((unsigned long long)numOwned * count > 0xF0000000ull) return fail(c, PT_ERROR_INVALID_ARGUMENT, "too many paths in one pt_render call");
-    uint total = numOwned * count;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (total == 0) { c->accumCount += count; return PT_OK; }
-    // min(RTXPT_LIGHTING_MAX_SAMPLE_COUNT, NEEFullSamples), PathTracerNEE.hlsli:312
-    const uint neeSamples = c->S.NEEFullSamples < 63u ? c->S.NEEFullSamples : 63u;
-    // 0: one shadow-queue entry per path vertex, written by k_shade itself
-    const uint shadowGroup = (c->S.NEEEnabled && neeSamples > 1u) ? neeSamples : 0u;
-    const uint shadowPerPath = shadowGroup ? shadowGroup : 1u;
-    r = ensure_pool(c, total, shadowPerPath); if (r != PT_OK) return r;
-    if (c->localResX) {                     // NEE-AT local layer: every pixel's (jittered) tile must exist, and a table can only name lights that were baked
-        const uint TILE_PX = ptk::RTXPT_LIGHTING_SAMPLING_BUFFER_TILE_SIZE;
-        if ((c->width - 1u + c->localJitterX) / TILE_PX >= c->localResX || (c->height - 1u + c->localJitterY) / TILE_PX >= c->localResY) return fail(c, PT_ERROR_INVALID_ARGUMENT, "local sampling table smaller than the frame");
-        if (c->localMaxLight >= c->lights.size()) return fail(c, PT_ERROR_INVALID_ARGUMENT, "local sampling table names a light index beyond the baked light table");
-    }
-    const bool feedback = c->feedbackRequired && c->S.NEEEnabled && neeSamples != 0u;
-    c->fbSamples = 0;
-    if (feedback) {
-        if (shadowGroup) return fail(c, PT_ERROR_INVALID_ARGUMENT, "NEE-AT temporal feedback needs NEEFullSamples 1 (the reference's default): the feedback draw of one light sample shifts the random numbers of the next");
-        const size_t plane = (size_t)c->width * c->height;
-        PT_CHECK_HIP(c, c->dSq3.resize(c->shadowCapacity));
-        if (!c->neeat.enabled) {      // (with the baker in the loop the run's own reservoirs are the target: they carry what the Clear pass kept)
-            PT_CHECK_HIP(c, c->dFbWeight.resize(plane * count)); PT_CHECK_HIP(c, c->dFbCand.resize(plane * count));
-            PT_CHECK_HIP(c, hipMemsetAsync(c->dFbWeight.p, 0, 4 * plane * count, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(c->dFbCand.p, 0xFF, 4 * plane * count, c->stream));      // LightFeedbackReservoir::Clear
-        }
-        PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
-    // `applyNEE &= fullSamples > 0` (PathTracerNEE.hlsli:322): the vertices behave as without NEE; the light tables stay as baked
-    if (neeSamples == 0u) k.S.NEEEnabled = 0;
-
-    // The owned pixels are traced as up to PT_PIPELINE_BATCHES independent sub-frame batches, each on its own stream. Paths never interact, so this changes
-    // nothing in the result; it lets the k_shade of one batch (3 waves per SIMD, mostly waiting on memory) overlap the traversal of the others and hides the
-    // ~0.5 ms drain at the end of every launch (C3: 241 ms with one batch, 199 ms with four). The batches advance in lockstep (queue all, then service each as
-    // its counts arrive): an event-driven variant that re-queued each batch independently was 7 % slower. Small frames use fewer batches,
-    // PT_DEVICE_SERIAL_KERNELS one.
-    struct Batch {
-        uint pixFirst = 0, numPix = 0, total = 0, base = 0; hipStream_t st = nullptr; WaveCounters* wc = nullptr; WaveCounters* hwc = nullptr;
-        PathPool pool; ShadowQueue sq; uint* queue[2] = {nullptr, nullptr}; DeviceScene sc; PathKernelContext k; TravAux aux;
-        uint cur = 0, active = 0, iterations = 0, tailLaunches = 0; unsigned long long extendRays = 0, shadowRays = 0; bool waiting = false, afterTail = false, inTail = false; uint bound = 0, pendingShadow = 0; TravAux auxSh; PathPool poolSet[2]; uint set = 0; bool compact = false;      // poolSet / set / compact: the compacted pool (below)      // pendingShadow / auxSh: fused traversal launches (below)      // bound: wavefront passes so far (what maxIter limits; a tail launch is followed by one, so the loop ends)
-        std::vector<hipEvent_t> ev; struct Span { size_t a, b; int kind; uint items; }; std::vector<Span> spans; size_t t0 = 0, t1 = 0;
-        // per-launch HIP events: only when somebody reads them (serial-kernel steps, the pass log) — ten API calls per pass and batch otherwise
-        bool timed = false;
-        size_t mark() { if (!timed) return 0; hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); ev.push_back(e); return ev.size() - 1; }
-    };
-    uint numBatches = (c->serialKernels || total < (1u << 20)) ? 1u : ((total < PT_PIPELINE_FULL_AT) ? (uint)PT_PIPELINE_MID_BATCHES : PT_PIPELINE_BATCHES);
-    { static const uint batchesOverride = []() { const char* e = getenv("MI355PT_BATCHES"); return e ? (uint)strtoul(e, nullptr, 10) : 0u; }(); if (batchesOverride && !c->serialKernels) numBatches = batchesOverride < (uint)PT_PIPELINE_BATCHES ? batchesOverride : (uint)PT_PIPELINE_BATCHES; }      // developer A/B switch
-    Batch B[PT_PIPELINE_BATCHES];
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        t.pixFirst = (uint)((unsigned long long)numOwned * b / numBatches); t.numPix = (uint)((unsigned long long)numOwned * (b + 1) / numBatches) - t.pixFirst;
-        t.total = t.numPix * count; t.base = t.pixFirst * count; t.st = c->streams[b]; t.wc = c->dCounters.p + b; t.hwc = c->hostCounters + b;
-        t.pool = PathPool{c->dS0.p + t.base, c->dS1.p + t.base, c->dS2.p + t.base, c->dS3.p + t.base, c->dS4.p + t.base, c->dHit.p + t.base};
-        const size_t sbase = (size_t)t.base * shadowPerPath;
-        t.sq = ShadowQueue{c->dSq0.p + sbase, c->dSq1.p + sbase, c->dSq2.p + sbase, shadowGroup, nullptr, nullptr, nullptr, 0u, 0u, 0u};
-        if (feedback) { t.sq.q3 = c->dSq3.p + sbase; t.sq.fbTotalWeight = c->neeat.enabled ? c->neeat.fbW.p : c->dFbWeight.p; t.sq.fbCandidates = c->neeat.enabled ? c->neeat.fbC.p : c->dFbCand.p; t.sq.fbWidth = c->width; t.sq.fbPlane = c->width * c->height; t.sq.fbSampleFirst = first; }
-        t.queue[0] = c->dQueue[0].p + t.base; t.queue[1] = c->dQueue[1].p + t.base;
-        t.sc = c->dsc; t.sc.travSpill = c->dsc.travSpill + (size_t)b * T8_MAX_BLOCKS * T8_GROUPS_PER_BLOCK * T8_SPILL_DEPTH;
-        t.k = k; t.k.sc = t.sc;
-        t.aux.taskQ[0] = c->dTaskQ.p + (size_t)(2 * b) * TASK_QUEUE_CAPACITY; t.aux.taskQ[1] = t.aux.taskQ[0] + TASK_QUEUE_CAPACITY; t.aux.counts = c->dTravCounts.p + PASS_COUNTERS * b;
-        // pipelined batches: one GPU-full of blocks per traversal launch (pt_scene.h PT_T8_MAX_BLOCKS) — and fewer for the launches of a small frame (one rank
-        // of a sharded frame): every wave then works through more chunks before it runs dry and fewer of its rays are cut into sub-trees; the other batches
-        // keep the GPU full. profiles/r05q_grid_cap_ab.txt: a rank of eight (4.1 M paths) 896 blocks -1 ... -3 %, a rank of four / two 1120 blocks -1 %, the
-        // full frame (33 M paths) +1 % with either: hence by size.
-        t.aux.maxBlocks = (numBatches >= 3u) ? (total < (6u << 20) ? 256u * 7u / 2u : (total < (24u << 20) ? 256u * 35u / 8u : 256u * 7u)) : 0u;
-        { static const uint blocksOverride = []() { const char* e = getenv("MI355PT_MAX_BLOCKS"); return e ? (uint)strtoul(e, nullptr, 10) : 0u; }(); if (blocksOverride) t.aux.maxBlocks = blocksOverride < T8_MAX_BLOCKS ? blocksOverride : T8_MAX_BLOCKS; }      // (clamped: a batch's stack-tail slice is sized for T8_MAX_BLOCKS blocks)      // developer A/B switch
-        t.aux.taskCap = TASK_QUEUE_CAPACITY; t.aux.bestKey = c->dBestKey.p + sbase; t.aux.resolveList = c->dResolveList.p + sbase; t.aux.primToSlot = c->bvh.primToSlot;
-        t.timed = c->serialKernels || c->countersEnabled || getenv("MI355PT_PASS_LOG") != nullptr;
-        memset(t.hwc, 0, sizeof(WaveCounters)); t.hwc->extendCount[0] = t.total;
-        t.active = t.total;
-    }
-    // uploads issued on the main stream (prepare) must be visible to the second stream
-    if (numBatches > 1) PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    hipEvent_t frame0, frame1; PT_CHECK_HIP(c, hipEventCreate(&frame0)); PT_CHECK_HIP(c, hipEventCreate(&frame1));
-    PT_CHECK_HIP(c, hipEventRecord(frame0, c->stream));
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        t.t0 = t.mark();
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.wc, t.hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, t.st));
-        launch_generate(t.k, t.pool, c->dOwned.p + t.pixFirst, t.numPix, first, count, 0u, t.total, t.queue[0], nullptr, t.st);
-    }
-    // upper bound on extend passes: bounceCount+1 vertices plus rejected (nested dielectric) re-traces
-    uint maxIter = c->S.bounceCount + 2 + ((c->S.nestedDielectricsQuality == 2) ? 16u : (c->S.nestedDielectricsQuality == 1 ? 4u : 0u));
-    // the tail kernel takes over a batch once it holds at most this many paths (0: never). Not in serial-kernel / counter frames (their per-kernel attribution
-    // is the point), not with grouped NEE samples (NEEFullSamples > 1 folds a vertex's samples in k_resolve_nee) and not without a tree (the traversal's
-    // empty-scene path is per launch, not per wave)
-    const uint tailBelow = (!c->serialKernels && !c->countersEnabled && !shadowGroup && c->dsc.rootIsValid) ? c->tailBelow : 0u;
-    // Fused traversal launches (round 6; pt_set_fused_traversal, k_trace_pair): the visibility rays a bounce's shading leaves in the shadow queue are not
-    // traced in a launch of their own but wait (Batch::pendingShadow) for the next bounce's closest-hit launch and share it — and its task rounds and resolve
-    // pass — block by block. Nothing of vertex k + 1 needs the visibility of vertex k before vertex k + 1 is shaded (the order of the fp16 additions into a
-    // path's L), and that is exactly where the fused launch sits, so the image cannot change; the visibility rays need their own task queues, merge keys and
-    // resolve list (auxSh). A batch whose paths have ended, or which goes to the tail kernel, traces what is pending in a plain visibility launch first. Not in
-    // serial-kernel / counter frames (their per-kernel attribution is the point) and not with grouped NEE samples (k_resolve_nee).
-    const bool fused = !c->serialKernels && !c->countersEnabled && !shadowGroup && c->dsc.rootIsValid && (c->fusedTraversal == 1u || (c->fusedTraversal == 2u && total < PT_FUSED_BELOW));
-    if (fused) {
-        PT_CHECK_HIP(c, c->dBestKeySh.resize(c->shadowCapacity)); PT_CHECK_HIP(c, c->dResolveListSh.resize(c->shadowCapacity)); PT_CHECK_HIP(c, c->dTaskQSh.resize((size_t)PT_PIPELINE_BATCHES * 2 * TASK_QUEUE_CAPACITY));
-        for (uint b = 0; b < numBatches; b++) { Batch& t = B[b]; t.auxSh = t.aux; t.auxSh.counts = t.aux.counts + PASS_SHADOW_OFFSET; t.auxSh.taskQ[0] = c->dTaskQSh.p + (size_t)(2 * b) * TASK_QUEUE_CAPACITY; t.auxSh.taskQ[1] = t.auxSh.taskQ[0] + TASK_QUEUE_CAPACITY;
-            t.auxSh.bestKey = c->dBestKeySh.p + (size_t)t.base * shadowPerPath; t.auxSh.resolveList = c->dResolveListSh.p + (size_t)t.base * shadowPerPath; }
-    }
-    // Batches run in lockstep: a batch's next half-pass is queued when ALL batches have delivered their counts, which keeps one batch's shading next to the
-    // others' traversal (free-running streams drift into running the same kernel at the same time: 7 % slower on the full frame and no gain on a rank of a
-    // sharded frame, DESIGN.md §4, profiles/r04i_event_loop_ab.txt).
-    const bool passLog = getenv("MI355PT_PASS_LOG") != nullptr;
-    // Compacted pool (round 6; ptk::PathPool::home). A path's state lives at its home slot (owned pixel x sample) for the whole frame in the layout above, and from the second bounce on
-    // the survivors are scattered over the pool: a wave's 64 paths touch up to 64 lines per word group where the first bounce touches 8. Here k_shade writes a survivor's origin, direction,
-    // interior list | counters | ray cone and {firefly K, MIS info, flags, sample index} at the POSITION it appends the path to, into the other of two array sets; the next bounce's
-    // traversal reads rays, and writes hits, by position (the extend queue is the identity), k_classify and k_shade read dense arrays. Only throughput | radiance — what the
-    // visibility resolve and k_accumulate address by path — stays at the home slot, which the extend queue keeps carrying (and the shadow queue names). Same values, another place:
-    // the image cannot change. A batch that goes to the tail kernel is scattered back to its home slots first (k_uncompact) and continues in the home-slot layout. Not for NEE-AT
-    // (its visibility resolve patches the path's flags), grouped NEE samples, serial-kernel and counter frames.
-    const bool neeatShade = c->dsc.lights.LocalSamplingBuffer != nullptr || c->dsc.lights.TemporalFeedbackRequired != 0u;
-    const bool compactPool = c->compactPool && !c->serialKernels && !c->countersEnabled && !shadowGroup && !neeatShade && !feedback && c->dsc.rootIsValid;
-    if (compactPool) {
-        PT_CHECK_HIP(c, c->dS0b.resize(c->poolCapacity)); PT_CHECK_HIP(c, c->dS1b.resize(c->poolCapacity)); PT_CHECK_HIP(c, c->dS3b.resize(c->poolCapacity)); PT_CHECK_HIP(c, c->dS4b.resize(c->poolCapacity)); PT_CHECK_HIP(c, c->dHitb.resize(c->poolCapacity));
-        for (uint b = 0; b < numBatches; b++) { Batch& t = B[b]; t.compact = true; t.set = 0; t.poolSet[0] = t.pool;
-            t.poolSet[1] = PathPool{c->dS0b.p + t.base, c->dS1b.p + t.base, t.pool.s2, c->dS3b.p + t.base, c->dS4b.p + t.base, c->dHitb.p + t.base, nullptr}; }
-    }
-    // One pass of a batch is queued by queue_pass (counter reset, traversal — fused with the pending visibility rays — classify + shade, read-back of the two
-    // queue counts) and finished by finish_pass once those counts have arrived (the visibility rays become pending, or are traced if the batch ends here).
-    uint wavefrontPasses = 0;
-    auto queue_pass = [&](Batch& t) -> int32_t {
-        uint nxt = t.cur ^ 1u;
-        // the pass's traversal / class counters and the two queue counters it refills: one launch (fused: the shadow queue's counter still counts the pending
-        // rays; k_resolve_pair zeroes it)
-        launch_pass_reset(t.aux.counts, &t.wc->extendCount[nxt], fused ? nullptr : &t.wc->shadowCount, t.st);
-        if (tailBelow && t.active <= tailBelow && !t.afterTail && t.compact) {      // the tail kernel works on home slots: scatter the live paths back, into the array set that is not being read
-            PathPool in = t.poolSet[t.set]; in.home = t.queue[t.cur];
-            launch_uncompact(in, t.poolSet[t.set ^ 1u], &t.wc->extendCount[t.cur], t.active, t.st);
-            t.pool = t.poolSet[t.set ^ 1u]; t.compact = false;
-        }
-        if (tailBelow && t.active <= tailBelow && !t.afterTail) {
-            if (t.pendingShadow) { launch_shadow(t.sc, t.pool, t.sq, &t.wc->shadowCount, t.pendingShadow, t.wc, false, t.auxSh, t.st); PT_CHECK_HIP(c, hipMemsetAsync(&t.wc->shadowCount, 0, 4, t.st)); t.pendingShadow = 0; }      // (the tail kernel adds to the paths' radiance itself: what is pending lands first)      // few paths left: one launch runs them to their end, wave by wave (pt_tail.hip); stragglers come back through queue[nxt] / the shadow queue
-            size_t e0 = t.mark(); launch_tail(t.k, t.pool, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.queue[nxt], &t.wc->extendCount[nxt], t.sq, t.wc, maxIter - t.bound, c->tailDefer, t.aux.maxBlocks, t.st); size_t e1 = t.mark();
-            if (t.timed) t.spans.push_back({e0, e1, 3, t.active});
-            // what comes back — stragglers — is traced by a wavefront pass (task rounds included) before the tail kernel gets another turn
-            t.tailLaunches++; t.afterTail = true; t.inTail = true;
-            PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));
-            t.waiting = true;
-            return PT_OK;
-        }
-        t.afterTail = false; t.bound++; wavefrontPasses++;
-        size_t e0 = t.mark();
-        PathPool pin = t.pool, pout = PathPool{};
-        if (t.compact) { pin = t.poolSet[t.set]; pin.home = t.queue[t.cur]; pout = t.poolSet[t.set ^ 1u]; t.set ^= 1u; }
-        if (t.pendingShadow) { launch_trace_pair(t.sc, pin, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.sq, &t.wc->shadowCount, t.pendingShadow, t.wc, t.aux, t.auxSh, t.st); t.pendingShadow = 0; }
-        else launch_extend(t.sc, pin, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.wc, c->countersEnabled, t.aux, t.st);
-        size_t e1 = t.mark(); if (t.timed) t.spans.push_back({e0, e1, 0, t.active});
-        launch_shade(t.k, pin, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.queue[nxt], &t.wc->extendCount[nxt], t.sq, t.wc, t.active >= PT_CLASSIFY_FROM ? reinterpret_cast<uint*>(t.aux.bestKey) : nullptr /* the straggler keys are idle between k_resolve_extend and the shadow launch; a few thousand paths are shaded in queue order: one launch fewer */, t.aux.counts + PASS_CLASS_OFFSET, t.st, pout); size_t e2 = t.mark(); if (t.timed) t.spans.push_back({e1, e2, 1, t.active});
-        t.extendRays += t.active;
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));
-        t.waiting = true;
-        return PT_OK;
-    };
-    auto finish_pass = [&](Batch& t, uint b) -> int32_t {
-        t.waiting = false; t.inTail = false;
-        uint nxt = t.cur ^ 1u, nShadow = t.hwc->shadowCount;
-        // the pass's straggler counters: sub-trees split off by k_extend and by task rounds 0..2, rays sent to the resolve pass (the previous pass's shadow
-        // launch is reported with the next line)
-        if (passLog) {
-            uint pc[PASS_COUNTERS]; PT_CHECK_HIP(c, hipMemcpy(pc, t.aux.counts, sizeof(pc), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[pass log]   b%u pass %u: %u paths -> extend splits %u / %u / %u / %u sub-trees, %u rays resolved; %u visibility rays next\n", b, t.iterations, t.active, pc[0], pc[1], pc[2], pc[3], pc[TRAV_RESOLVE], nShadow);
-        }
-        TravAux auxShadow = t.aux; auxShadow.counts = t.aux.counts + PASS_SHADOW_OFFSET;
-        t.active = t.hwc->extendCount[nxt];
-        // they ride with the next closest-hit launch
-        if (fused && nShadow && t.active && t.bound < maxIter) { t.pendingShadow = nShadow; t.shadowRays += nShadow; }
-        else if (nShadow) { size_t s0 = t.mark(); launch_shadow(t.sc, t.pool, t.sq, &t.wc->shadowCount, nShadow, t.wc, c->countersEnabled, fused ? t.auxSh : auxShadow, t.st); size_t s1 = t.mark(); if (t.timed) t.spans.push_back({s0, s1, 2, nShadow}); if (!shadowGroup) t.shadowRays += nShadow;
-                            if (fused) PT_CHECK_HIP(c, hipMemsetAsync(&t.wc->shadowCount, 0, 4, t.st)); }
-        t.cur = nxt; t.iterations++;
-        return PT_OK;
-    };
-    auto live = [&](const Batch& t) { return t.active && t.bound < maxIter; };
-    // Small passes run free (round 6). The lockstep above pays while every pass fills the GPU; at the end of a frame — and for the whole of a small frame — a
-    // pass is a chain of a dozen short launches, the batches no longer take equally long, and in lockstep three streams sit idle until the slowest has
-    // delivered its counts (0.7 - 1 ms per late pass of the 4K frame, profiles/r06i_*). Once every live batch holds fewer than `freeRunBelow` paths the loop
-    // turns event-driven: whichever batch's counts arrive first is finished and its next pass queued at once.
-    static const uint freeRunBelow = []() { const char* e = getenv("MI355PT_FREE_RUN_BELOW"); return e ? (uint)strtoul(e, nullptr, 10) : (uint)PT_FREE_RUN_BELOW; }();
-    bool any = true;
-    while (any) {
-        bool freeRun = freeRunBelow != 0u && numBatches > 1u;
-        for (uint b = 0; b < numBatches; b++) if (live(B[b]) && B[b].active >= freeRunBelow) freeRun = false;
-        // phase 1: every live batch queues extend + shade and the read-back of its queue counts
-        wavefrontPasses = 0;
-        for (uint b = 0; b < numBatches; b++) {
-            Batch& t = B[b];
-            if (t.waiting) continue;                        // a tail launch still in flight (below): the batch rejoins the lockstep when it is done
-            if (!live(t)) continue;
-            int32_t r1 = queue_pass(t); if (r1 != PT_OK) return r1;
-        }
-        any = false;
-        if (freeRun) {      // event-driven until every batch has ended
-            uint waiting = 0; for (uint b = 0; b < numBatches; b++) waiting += B[b].waiting ? 1u : 0u;
-            while (waiting) {
-                for (uint b = 0; b < numBatches; b++) {
-                    Batch& t = B[b];
-                    if (!t.waiting || hipStreamQuery(t.st) == hipErrorNotReady) continue;
-                    PT_CHECK_HIP(c, hipStreamSynchronize(t.st));
-                    int32_t r2 = finish_pass(t, b); if (r2 != PT_OK) return r2;
-                    waiting--;
-                    if (live(t)) { int32_t r1 = queue_pass(t); if (r1 != PT_OK) return r1; waiting++; }
-                }
-            }
-            break;
-        }
-        // phase 2: as each batch's counts arrive, its visibility rays become pending (or are traced, if the batch ends); the other batches keep the GPU busy
-        // meanwhile
-        for (uint b = 0; b < numBatches; b++) {
-            Batch& t = B[b];
-            if (!t.waiting) continue;
-            // a tail launch runs for about a millisecond — several of the other batches' passes: while those have wavefront passes to queue, it is only polled
-            if (t.inTail && wavefrontPasses && hipStreamQuery(t.st) == hipErrorNotReady) { any = true; continue; }
-            PT_CHECK_HIP(c, hipStreamSynchronize(t.st));
-            int32_t r2 = finish_pass(t, b); if (r2 != PT_OK) return r2;
-            if (live(t)) any = true;
-        }
-    }
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        launch_accumulate(t.pool, c->dOwned.p + t.pixFirst, t.numPix, count, c->dAccum.p, c->accumCount, c->width, t.st);
-        t.t1 = t.mark();
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, sizeof(WaveCounters), hipMemcpyDeviceToHost, t.st));
-    }
-    for (uint b = 0; b < numBatches; b++) PT_CHECK_HIP(c, hipStreamSynchronize(B[b].st));
-    PT_CHECK_HIP(c, hipEventRecord(frame1, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    bool overflow = false;
-    for (uint b = 0; b < numBatches; b++) overflow = overflow || B[b].hwc->overflow;
-    c->accumCount += count;
-    if (feedback) c->fbSamples = count;
-    if (stats) {
-        // whole-call time: from the first batch's start to the later batch's end (both streams were idle before and are drained now)
-        float ms = 0; (void)hipEventElapsedTime(&ms, frame0, frame1); stats->gpuMilliseconds = ms;
-        for (uint b = 0; b < numBatches; b++) {
-            Batch& t = B[b]; const WaveCounters& h = *t.hwc;
-            for (auto& sp : t.spans) { float m = 0; (void)hipEventElapsedTime(&m, t.ev[sp.a], t.ev[sp.b]); if (sp.kind == 0) stats->extendKernelMs += m; else if (sp.kind == 1) stats->shadeKernelMs += m; else if (sp.kind == 2) stats->shadowKernelMs += m; }      // (zero in pipelined frames: no per-launch events there)
-            stats->extendLaunches += t.iterations;
-            stats->extendRays += t.extendRays + h.tailExtendRays; stats->shadowRays += shadowGroup ? h.shadowValid : t.shadowRays + h.tailShadowRays; stats->hits += h.hits; stats->tailLaunches += t.tailLaunches;
-            if (getenv("MI355PT_PASS_LOG") && t.tailLaunches) fprintf(stderr, "[pass log] batch %u: %u tail launches traced %llu + %llu rays, handed back %llu extend stragglers, %llu visibility stragglers, %llu paths at the bounce bound\n", b, t.tailLaunches,
-                (unsigned long long)h.tailExtendRays, (unsigned long long)h.tailShadowRays, (unsigned long long)h.tailHandedBack[0], (unsigned long long)h.tailHandedBack[1], (unsigned long long)h.tailHandedBack[2]);
-            stats->nodeVisitsExtend += h.nodeVisitsExt; stats->triTestsExtend += h.triTestsExt;
-            stats->nodeVisitsShadow += h.nodeVisitsSh; stats->triTestsShadow += h.triTestsSh;
-            stats->leafVisitsExtend += h.leafVisitsExt; stats->waveItersExtend += h.itersExt; stats->leafVisitsShadow += h.leafVisitsSh; stats->waveItersShadow += h.itersSh;
-            for (int q = 0; q < 4; q++) stats->extendPhaseCycles[q] += h.phaseCycExt[q];
-            stats->leafBlocksExtend += h.leafBlocksExt; if (h.itersMaxExt > stats->waveItersMaxExtend) stats->waveItersMaxExtend = h.itersMaxExt;
-            for (int q = 0; q < 8; q++) stats->extendEvents[q] += h.eventsExt[q];
-            for (int q = 0; q < 16; q++) stats->extendRayIterHist[q] += h.rayIterHistExt[q];
-            for (uint q = 0; q < h.longRayCount && q < 32u && stats->longRayCount < 32u; q++) { memcpy(stats->longRays[stats->longRayCount], h.longRays[q], 32); stats->longRayCount++; }
-            if (t.iterations > stats->iterations) stats->iterations = t.iterations;
-        }
-        stats->pathsTraced = total;
-    }
-    if (getenv("MI355PT_PASS_LOG")) {        // developer probe: the launch sequence of every batch with item counts and HIP-event durations (stderr)
-        for (uint b = 0; b < numBatches; b++) { Batch& t = B[b]; float whole = 0; if (!t.timed) continue; (void)hipEventElapsedTime(&whole, t.ev[t.t0], t.ev[t.t1]);
-            fprintf(stderr, "[pass log] batch %u of %u: %u paths, %u passes, %.3f ms from first to last event\n", b, numBatches, t.total, t.iterations, whole);
-            for (auto& sp : t.spans) { float m = 0, at = 0; (void)hipEventElapsedTime(&m, t.ev[sp.a], t.ev[sp.b]); (void)hipEventElapsedTime(&at, t.ev[t.t0], t.ev[sp.a]);
-                fprintf(stderr, "[pass log]   b%u %-6s %9u items  start %8.3f ms  %7.3f ms\n", b, sp.kind == 0 ? "extend" : (sp.kind == 1 ? "shade" : (sp.kind == 2 ? "shadow" : "tail")), sp.items, at, m); } }
-    }
-    for (uint b = 0; b < numBatches; b++) for (auto e : B[b].ev) (void)hipEventDestroy(e);
-    (void)hipEventDestroy(frame0); (void)hipEventDestroy(frame1);
-    if (overflow) return fail(c, PT_ERROR_HIP, "BVH8 traversal: stack tail or straggler task queue overflow (raise T8_SPILL_DEPTH / TASK_QUEUE_CAPACITY)");
-    // The pass bound (maxIter) is a safety net, never what ends a path: a path ends by its own bounce / rejected-hit counters (PathTracer.hlsli:40-45,
-    // PathTracerNestedDielectrics.hlsli). Were a path still alive here, the set of dropped paths — the image — would depend on how the passes were composed
-    // (tail threshold): reported, not swallowed.
-    for (uint b = 0; b < numBatches; b++) if (B[b].active) return fail(c, PT_ERROR_HIP, "pt_render: paths still alive at the pass bound (bounceCount + 2 + the nested-dielectric allowance): the bound must be raised");
-    return PT_OK;
-}
 static_assert(sizeof(::PtStablePlanesParams) == sizeof(ptk::StablePlanesParams) && sizeof(::PtStablePlane) == sizeof(ptk::StablePlane), "stable-plane ABI");
 int32_t pt_stable_planes_plane_stride(uint32_t width, uint32_t height, uint32_t* stride) { if (!stride) return PT_ERROR_INVALID_ARGUMENT; *stride = ptk::GenericTSComputePlaneStride(width, height); return PT_OK; }
-int32_t pt_build_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStablePlanesParams* params, PtFrameStats* stats) {
-    if (!c || !params) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    const uint numOwned = (uint)c->owned.size();
-    r = ensure_pool(c, numOwned ? numOwned : 1u, 1u); if (r != PT_OK) return r;
-    const size_t N = (size_t)c->width * c->height;
-    ptk::StablePlanesParams prm; memcpy(&prm, params, sizeof(prm));
-    StablePlanesContext sp; sp.C = ptk::SP_make_consts(prm, c->width, c->height, c->S.bounceCount);
-    PT_CHECK_HIP(c, c->dSpHeader.resize(4 * N)); PT_CHECK_HIP(c, c->dSpPlanes.resize((size_t)cStablePlaneCount * sp.C.genericTSPlaneStride)); PT_CHECK_HIP(c, c->dSpRadiance.resize(N)); PT_CHECK_HIP(c, c->dSpMotion.resize(N));
-    PT_CHECK_HIP(c, c->dSpDepth.resize(N)); PT_CHECK_HIP(c, c->dSpHitT.resize(N)); PT_CHECK_HIP(c, c->dSpThroughput.resize(N));
-    // a new size: nothing of the old frame is meaningful (pixels of other ranks' tiles and the records of planes that do not exist stay zero)
-    if (c->spW != c->width || c->spH != c->height) {
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpHeader.p, 0xFF, 16 * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpPlanes.p, 0, sizeof(ptk::StablePlane) * cStablePlaneCount * sp.C.genericTSPlaneStride, c->stream));
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpRadiance.p, 0, 8 * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpMotion.p, 0, 8 * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpDepth.p, 0, 4 * N, c->stream));
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpHitT.p, 0, 4 * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpThroughput.p, 0, 4 * N, c->stream));
-        c->spW = c->width; c->spH = c->height;
-    }
-    sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
-    c->spGathered = false; c->spSampleBase = sampleIndex;
-    if (!numOwned) return PT_OK;
-    PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
-    PathPool pool{c->dS0.p, c->dS1.p, c->dS2.p, c->dS3.p, c->dS4.p, c->dHit.p};
-    uint* queue[2] = {c->dQueue[0].p, c->dQueue[1].p};
-    WaveCounters* wc = c->dCounters.p; WaveCounters* hwc = c->hostCounters;
-    TravAux aux; aux.taskQ[0] = c->dTaskQ.p; aux.taskQ[1] = aux.taskQ[0] + TASK_QUEUE_CAPACITY; aux.counts = c->dTravCounts.p; aux.maxBlocks = 0u;
-    aux.taskCap = TASK_QUEUE_CAPACITY; aux.bestKey = c->dBestKey.p; aux.resolveList = c->dResolveList.p; aux.primToSlot = c->bvh.primToSlot;
-    memset(hwc, 0, sizeof(WaveCounters)); hwc->extendCount[0] = numOwned;
-    hipEvent_t e0, e1; PT_CHECK_HIP(c, hipEventCreate(&e0)); PT_CHECK_HIP(c, hipEventCreate(&e1));
-    PT_CHECK_HIP(c, hipEventRecord(e0, c->stream));
-    PT_CHECK_HIP(c, hipMemcpyAsync(wc, hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, c->stream));
-    launch_sp_generate(k, sp, pool, c->dOwned.p, numOwned, sampleIndex, queue[0], c->stream);
-    // every pass is one vertex of every pixel that still explores: at most three planes of at most maxStablePlaneVertexDepth + 1 vertices, plus the false hits
-    // nested dielectrics reject
-    const uint maxIter = cStablePlaneCount * (sp.C.maxStablePlaneVertexDepth + 2u + ((c->S.nestedDielectricsQuality == 2) ? 16u : (c->S.nestedDielectricsQuality == 1 ? 4u * (sp.C.maxStablePlaneVertexDepth + 1u) : 0u)));
-    uint cur = 0, active = numOwned, iterations = 0; unsigned long long rays = 0;
-    while (active && iterations < maxIter) {
-        const uint nxt = cur ^ 1u;
-        launch_pass_reset(aux.counts, &wc->extendCount[nxt], &wc->shadowCount, c->stream);
-        launch_extend(c->dsc, pool, queue[cur], &wc->extendCount[cur], active, wc, c->countersEnabled, aux, c->stream);
-        launch_sp_build_shade(k, sp, pool, queue[cur], &wc->extendCount[cur], active, queue[nxt], &wc->extendCount[nxt], sampleIndex, wc, c->stream);
-        rays += active;
-        PT_CHECK_HIP(c, hipMemcpyAsync(hwc, wc, 16, hipMemcpyDeviceToHost, c->stream));
-        PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-        active = hwc->extendCount[nxt]; cur = nxt; iterations++;
-    }
-    PT_CHECK_HIP(c, hipEventRecord(e1, c->stream));
-    PT_CHECK_HIP(c, hipMemcpyAsync(hwc, wc, sizeof(WaveCounters), hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    if (stats) { float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); stats->gpuMilliseconds = ms; stats->extendRays = rays; stats->hits = hwc->hits; stats->iterations = iterations; stats->extendLaunches = iterations; stats->pathsTraced = numOwned;
-                 stats->nodeVisitsExtend = hwc->nodeVisitsExt; stats->triTestsExtend = hwc->triTestsExt; }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (hwc->overflow) return fail(c, PT_ERROR_HIP, "BVH8 traversal: stack tail or straggler task queue overflow (raise T8_SPILL_DEPTH / TASK_QUEUE_CAPACITY)");
-    if (active) return fail(c, PT_ERROR_HIP, "stable-plane build pass: paths still exploring after the iteration bound");
-    return PT_OK;
-}
-int32_t pt_fill_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStablePlanesParams* params, PtFrameStats* stats) {
-    if (!c || !params) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes first");
-    if (c->S.NEEEnabled && c->S.NEEFullSamples > 1u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "the fill pass traces one full NEE sample per vertex (NEEFullSamples 0 or 1, the reference's default)");
-    // temporal feedback: with the baker in the loop (pt_set_neeat + pt_realtime_frame) the pass's visible light samples fill the run's reservoirs; a host that
-    // runs its own baker (pt_set_local_light_sampling with temporalFeedback) gets its per-sample planes from pt_render only
-    const bool feedback = c->neeat.enabled && c->feedbackRequired && c->S.NEEEnabled && c->S.NEEFullSamples != 0u;
-    if (c->feedbackRequired && !c->neeat.enabled) return fail(c, PT_ERROR_INVALID_ARGUMENT, "the fill pass feeds NEE-AT's reservoirs only with the baker in the loop (pt_set_neeat, pt_realtime_frame): switch the temporal feedback of pt_set_local_light_sampling off");
-    if (feedback && (!c->neeat.fbW.p || c->neeat.W != c->width || c->neeat.H != c->height)) return fail(c, PT_ERROR_NOT_READY, "NEE-AT: no baker frame of this size yet (pt_realtime_frame runs it)");
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    const uint numOwned = (uint)c->owned.size();
-    if (!numOwned) return PT_OK;
-    r = ensure_pool(c, numOwned, 1u); if (r != PT_OK) return r;
-    const bool freshMark = c->dSpMark.n < numOwned;
-    PT_CHECK_HIP(c, c->dSpMark.resize(numOwned)); PT_CHECK_HIP(c, c->dSpNewL.resize(numOwned));
-    if (feedback) PT_CHECK_HIP(c, c->dSq3.resize(c->shadowCapacity));
-    // (k_sp_fill_resolve clears what a pass marked)
-    if (freshMark) PT_CHECK_HIP(c, hipMemsetAsync(c->dSpMark.p, 0, sizeof(ptk::uint4) * c->dSpMark.n, c->stream));
-    ptk::StablePlanesParams prm; memcpy(&prm, params, sizeof(prm));
-    StablePlanesContext sp; sp.C = ptk::SP_make_consts(prm, c->width, c->height, c->S.bounceCount);
-    sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
-    PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
-    // As pt_render: the pixels are traced as up to PT_PIPELINE_BATCHES independent batches, each on its own stream with its own queues, counters, task queues
-    // and slice of the pool, advancing in lockstep (queue all, then service each as its counts arrive) — the shading of one batch overlaps the traversal of the
-    // others and the drain at the end of every launch is hidden.
-    struct Batch { uint pixFirst = 0, numPix = 0; hipStream_t st = nullptr; WaveCounters* wc = nullptr; WaveCounters* hwc = nullptr; PathPool pool, markPool; ShadowQueue sq; ptk::float4* newL = nullptr; uint* queue[2] = {nullptr, nullptr};
-                   DeviceScene sc; PathKernelContext k; TravAux aux; uint cur = 0, active = 0, iterations = 0; unsigned long long rays = 0, shadowRays = 0; bool waiting = false; };
-    const uint numBatches = (c->serialKernels || numOwned < (1u << 20)) ? 1u : ((numOwned < PT_PIPELINE_FULL_AT) ? (uint)PT_PIPELINE_MID_BATCHES : PT_PIPELINE_BATCHES);
-    Batch B[PT_PIPELINE_BATCHES];
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        t.pixFirst = (uint)((unsigned long long)numOwned * b / numBatches); t.numPix = (uint)((unsigned long long)numOwned * (b + 1) / numBatches) - t.pixFirst;
-        const uint base = t.pixFirst;
-        t.st = c->streams[b]; t.wc = c->dCounters.p + b; t.hwc = c->hostCounters + b;
-        t.pool = PathPool{c->dS0.p + base, c->dS1.p + base, c->dS2.p + base, c->dS3.p + base, c->dS4.p + base, c->dHit.p + base};
-        t.markPool = t.pool; t.markPool.s2 = c->dSpMark.p + base; t.newL = c->dSpNewL.p + base;
-        t.sq = ShadowQueue{c->dSq0.p + base, c->dSq1.p + base, c->dSq2.p + base, 0u, nullptr, nullptr, nullptr, 0u, 0u, 0u};
-        // feedback: the fourth word group of an entry and the reservoir planes; the reference mode's shadow kernels then apply the reservoir update and the
-        // roulette fix-up of a visible entry themselves (pt_wavefront.hip shadow_visible; one slot per pixel: plane stride 0)
-        if (feedback) { t.sq.q3 = c->dSq3.p + base; t.sq.fbTotalWeight = c->neeat.fbW.p; t.sq.fbCandidates = c->neeat.fbC.p; t.sq.fbWidth = c->width; t.sq.fbPlane = 0u; t.sq.fbSampleFirst = 0u; }
-        t.queue[0] = c->dQueue[0].p + base; t.queue[1] = c->dQueue[1].p + base;
-        t.sc = c->dsc; t.sc.travSpill = c->dsc.travSpill + (size_t)b * T8_MAX_BLOCKS * T8_GROUPS_PER_BLOCK * T8_SPILL_DEPTH;
-        t.k = k; t.k.sc = t.sc;
-        t.aux.taskQ[0] = c->dTaskQ.p + (size_t)(2 * b) * TASK_QUEUE_CAPACITY; t.aux.taskQ[1] = t.aux.taskQ[0] + TASK_QUEUE_CAPACITY; t.aux.counts = c->dTravCounts.p + PASS_COUNTERS * b;
-        t.aux.maxBlocks = (numBatches >= 3u) ? 256u * 7u : 0u;
-        t.aux.taskCap = TASK_QUEUE_CAPACITY; t.aux.bestKey = c->dBestKey.p + base; t.aux.resolveList = c->dResolveList.p + base; t.aux.primToSlot = c->bvh.primToSlot;
-        memset(t.hwc, 0, sizeof(WaveCounters));
-    }
-    // uploads / memsets issued on the main stream (prepare, the marks) must be visible to the batch streams
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    hipEvent_t e0, e1; PT_CHECK_HIP(c, hipEventCreate(&e0)); PT_CHECK_HIP(c, hipEventCreate(&e1));
-    PT_CHECK_HIP(c, hipEventRecord(e0, c->stream));
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.wc, t.hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, t.st));
-        launch_sp_fill_generate(t.k, sp, t.pool, c->dOwned.p + t.pixFirst, t.numPix, sampleIndex, t.queue[0], &t.wc->extendCount[0], t.st);
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));
-    }
-    for (uint b = 0; b < numBatches; b++) { PT_CHECK_HIP(c, hipStreamSynchronize(B[b].st)); B[b].active = B[b].hwc->extendCount[0]; }
-    const uint maxIter = c->S.bounceCount + 2 + ((c->S.nestedDielectricsQuality == 2) ? 16u : (c->S.nestedDielectricsQuality == 1 ? 4u : 0u)) * (c->S.bounceCount + 1u);
-    bool any = true;
-    while (any) {
-        for (uint b = 0; b < numBatches; b++) {      // phase 1: every live batch queues extend + shade and the read-back of its queue counts
-            Batch& t = B[b]; t.waiting = false;
-            if (!t.active || t.iterations >= maxIter) continue;
-            const uint nxt = t.cur ^ 1u;
-            launch_pass_reset(t.aux.counts, &t.wc->extendCount[nxt], &t.wc->shadowCount, t.st);
-            launch_extend(t.sc, t.pool, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.wc, c->countersEnabled, t.aux, t.st, /*ranged*/ t.iterations == 0u && PT_SP_FILL_RANGED);
-            launch_sp_fill_shade(t.k, sp, t.pool, t.queue[t.cur], &t.wc->extendCount[t.cur], t.active, t.queue[nxt], &t.wc->extendCount[nxt], t.sq, t.newL, sampleIndex, t.wc,
-                                 (PT_SP_FILL_CLASSES && t.active >= PT_CLASSIFY_FROM) ? reinterpret_cast<uint*>(t.aux.bestKey) : nullptr, t.aux.counts + PASS_CLASS_OFFSET, t.st);      // (the straggler keys are idle between k_resolve_extend and the shadow launch, as in pt_render)
-            t.rays += t.active;
-            PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));
-            t.waiting = true;
-        }
-        any = false;
-        // phase 2: as each batch's counts arrive, its visibility rays and their resolve; the other batches keep the GPU busy meanwhile
-        for (uint b = 0; b < numBatches; b++) {
-            Batch& t = B[b];
-            if (!t.waiting) continue;
-            PT_CHECK_HIP(c, hipStreamSynchronize(t.st));
-            const uint nxt = t.cur ^ 1u, nShadow = t.hwc->shadowCount;
-            if (nShadow) {
-                TravAux auxShadow = t.aux; auxShadow.counts = t.aux.counts + PASS_SHADOW_OFFSET;
-                launch_shadow(t.sc, t.markPool, t.sq, &t.wc->shadowCount, nShadow, t.wc, c->countersEnabled, auxShadow, t.st);
-                launch_sp_fill_resolve(t.pool, t.markPool.s2, t.sq, t.newL, &t.wc->shadowCount, nShadow, t.st);
-                t.shadowRays += nShadow;
-            }
-            t.active = t.hwc->extendCount[nxt]; t.cur = nxt; t.iterations++;
-            if (t.active && t.iterations < maxIter) any = true;
-        }
-    }
-    for (uint b = 0; b < numBatches; b++) {
-        Batch& t = B[b];
-        launch_sp_fill_commit(t.k, sp, t.pool, t.numPix, sampleIndex, t.st);
-        PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, sizeof(WaveCounters), hipMemcpyDeviceToHost, t.st));
-    }
-    for (uint b = 0; b < numBatches; b++) PT_CHECK_HIP(c, hipStreamSynchronize(B[b].st));
-    PT_CHECK_HIP(c, hipEventRecord(e1, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    bool overflow = false; uint active = 0;
-    if (stats) { float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); stats->gpuMilliseconds = ms; stats->pathsTraced = numOwned; }
-    for (uint b = 0; b < numBatches; b++) {
-        const Batch& t = B[b]; overflow = overflow || t.hwc->overflow; active += t.active;
-        if (stats) { stats->extendRays += t.rays; stats->shadowRays += t.shadowRays; stats->hits += t.hwc->hits; stats->extendLaunches += t.iterations; if (t.iterations > stats->iterations) stats->iterations = t.iterations;
-                     stats->nodeVisitsExtend += t.hwc->nodeVisitsExt; stats->triTestsExtend += t.hwc->triTestsExt; stats->nodeVisitsShadow += t.hwc->nodeVisitsSh; stats->triTestsShadow += t.hwc->triTestsSh; }
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (overflow) return fail(c, PT_ERROR_HIP, "BVH8 traversal: stack tail or straggler task queue overflow (raise T8_SPILL_DEPTH / TASK_QUEUE_CAPACITY)");
-    if (active) return fail(c, PT_ERROR_HIP, "stable-plane fill pass: paths still alive after the iteration bound");
-    return PT_OK;
-}
 // The realtime mode's frame with everything coupled (Sample.cpp:2438-2516; pt_set_neeat on): LightsBaker::UpdateBegin -> build pass -> LightsBaker::UpdateEnd
 // on THAT frame's depth and screen-space motion vectors -> the fill passes, which sample the tables just made and fill the reservoirs the next frame's
 // UpdateBegin reads.
-static StablePlanesContext sp_buffers(pt_context* c) {
-    ptk::StablePlanesParams prm; memset(&prm, 0, sizeof(prm)); prm.activeStablePlaneCount = cStablePlaneCount;
-    StablePlanesContext sp; sp.C = ptk::SP_make_consts(prm, c->width, c->height, c->S.bounceCount);
-    sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
-    return sp;
-}
 // ---- the realtime frame on tile shards (no reference analogue). The baker's passes read whole neighbourhoods of three things a rank only has for its own
 // tiles: last frame's reservoirs (UpdateBegin resolves them into the history), and this frame's depth and motion vectors (UpdateEnd reprojects through them).
 // So a sharded frame has two exchanges: the reservoirs before UpdateBegin (neeat_exchange_feedback, as between two reference-mode frames) and the build pass's
@@ -1758,7 +1102,7 @@ static int sp_exchange_guides(pt_context* c) {
         PT_CHECK_HIP(c, c->dSpGatherPixels.upload(others, s)); PT_CHECK_HIP(c, c->dSpGatherRecv.resize(others.size() * W)); PT_CHECK_HIP(c, c->dSpGatherSend.resize(n * W)); PT_CHECK_HIP(c, hipStreamSynchronize(s));
         c->spGatherW = c->width; c->spGatherH = c->height;
     }
-    const StablePlanesContext sp = sp_buffers(c);
+    const StablePlanesContext sp = sp_context(c, nullptr);
     launch_sp_pack(sp, c->dOwned.p, (uint)n, c->dSpGatherSend.p, false, s, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
     PT_CHECK_NCCL(c, g_rccl.GroupStart());
     size_t off = 0; ncclResult_t bad = ncclSuccess;
@@ -1779,7 +1123,7 @@ int32_t pt_pack_stable_plane_guides(pt_context* c, void* dst, size_t bytes) {
     if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes");
     if (bytes < c->owned.size() * (size_t)SP_GUIDE_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small (16 bytes per owned pixel)");
     (void)hipSetDevice(c->device);
-    launch_sp_pack(sp_buffers(c), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
+    launch_sp_pack(sp_context(c, nullptr), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
 }
@@ -1790,7 +1134,7 @@ int32_t pt_unpack_stable_plane_guides(pt_context* c, const void* src, size_t byt
     if (bytes < px.size() * (size_t)SP_GUIDE_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small (16 bytes per pixel of that rank)");
     (void)hipSetDevice(c->device);
     DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_sp_pack(sp_buffers(c), tmp.p, (uint)px.size(), (uint*)src, true, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
+    launch_sp_pack(sp_context(c, nullptr), tmp.p, (uint)px.size(), (uint*)src, true, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     tmp.free();
     return PT_OK;
@@ -1857,7 +1201,7 @@ int32_t pt_pack_stable_planes(pt_context* c, void* dst, size_t bytes) {
     if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes");
     if (bytes < c->owned.size() * (size_t)SP_SHARD_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small (pt_stable_planes_shard_bytes)");
     (void)hipSetDevice(c->device);
-    launch_sp_pack(sp_buffers(c), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream);
+    launch_sp_pack(sp_context(c, nullptr), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream);
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
 }
@@ -1868,7 +1212,7 @@ int32_t pt_unpack_stable_planes(pt_context* c, const void* src, size_t bytes, ui
     if (bytes < px.size() * (size_t)SP_SHARD_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small (pt_stable_planes_shard_bytes)");
     (void)hipSetDevice(c->device);
     DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_sp_pack(sp_buffers(c), tmp.p, (uint)px.size(), (uint*)src, true, c->stream);
+    launch_sp_pack(sp_context(c, nullptr), tmp.p, (uint)px.size(), (uint*)src, true, c->stream);
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     tmp.free();
     c->spGathered = true;      // (the host says when all ranks are in: pt_denoise_spec_hit_t trusts it from here on)
@@ -1883,7 +1227,7 @@ int32_t pt_gather_stable_planes(pt_context* c) {
     if (!c->comm) return fail(c, PT_ERROR_NOT_READY, "pt_comm_init first");
     (void)hipSetDevice(c->device);
     hipStream_t st = c->stream;
-    const StablePlanesContext sp = sp_buffers(c);
+    const StablePlanesContext sp = sp_context(c, nullptr);
     const size_t W = SP_SHARD_WORDS, n = c->owned.size();
     if (c->shardCount == 1) {
         if (!n) return PT_OK;
@@ -1981,19 +1325,13 @@ static int32_t dn_alloc(pt_context* c) {
     c->dnW = c->width; c->dnH = c->height;
     return PT_OK;
 }
-static StablePlanesContext dn_planes(pt_context* c, const PtStablePlanesParams* params) {
-    ptk::StablePlanesParams prm; memcpy(&prm, params, sizeof(prm));
-    StablePlanesContext sp; sp.C = ptk::SP_make_consts(prm, c->width, c->height, c->S.bounceCount); memset(&sp.B, 0, sizeof(sp.B));
-    sp.B.Header = c->dSpHeader.p; sp.B.Planes = c->dSpPlanes.p; sp.B.StableRadiance = c->dSpRadiance.p; sp.B.Depth = c->dSpDepth.p; sp.B.SpecularHitT = c->dSpHitT.p; sp.B.MotionVectors = c->dSpMotion.p; sp.B.Throughput = c->dSpThroughput.p;
-    return sp;
-}
 int32_t pt_denoiser_prepare_dlss_rr(pt_context* c, const PtStablePlanesParams* spParams, const PtDenoiserParams* params) {
     if (!c || !spParams || !params) return PT_ERROR_INVALID_ARGUMENT;
     int32_t r = dn_ready(c); if (r != PT_OK) return r;
     (void)hipSetDevice(c->device);
     r = dn_alloc(c); if (r != PT_OK) return r;
     ptk::DenoiserParams P; memcpy(&P, params, sizeof(P));
-    launch_dn_prepare_dlss_rr(dn_planes(c, spParams), P, dn_buffers(c), c->dAccum.p, c->stream);
+    launch_dn_prepare_dlss_rr(sp_context(c, spParams), P, dn_buffers(c), c->dAccum.p, c->stream);
     c->accumCount = 1;      // the radiance buffer holds one finished frame (as after pt_stable_planes_merge)
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
@@ -2006,7 +1344,7 @@ int32_t pt_denoiser_prepare_nrd(pt_context* c, const PtStablePlanesParams* spPar
     r = dn_alloc(c); if (r != PT_OK) return r;
     ptk::DenoiserParams P; memcpy(&P, params, sizeof(P));
     PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
-    launch_dn_prepare_nrd(k, dn_planes(c, spParams), P, dn_buffers(c), planeIndex, initWithStableRadiance != 0u, c->spSampleBase, c->dAccum.p, c->stream);
+    launch_dn_prepare_nrd(k, sp_context(c, spParams), P, dn_buffers(c), planeIndex, initWithStableRadiance != 0u, c->spSampleBase, c->dAccum.p, c->stream);
     if (initWithStableRadiance) c->accumCount = 1;
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
@@ -2017,7 +1355,7 @@ int32_t pt_denoiser_merge_nrd(pt_context* c, uint32_t planeIndex, const float* d
     int32_t r = dn_ready(c); if (r != PT_OK) return r;
     if (c->dnW != c->width || c->dnH != c->height) return fail(c, PT_ERROR_NOT_READY, "the merge reads the NRD prepare pass's viewZ: pt_denoiser_prepare_nrd first");
     (void)hipSetDevice(c->device);
-    launch_dn_merge_nrd(sp_buffers(c), dn_buffers(c), planeIndex, (const ptk::float4*)diffDevice, (const ptk::float4*)specDevice, c->dAccum.p, c->stream);
+    launch_dn_merge_nrd(sp_context(c, nullptr), dn_buffers(c), planeIndex, (const ptk::float4*)diffDevice, (const ptk::float4*)specDevice, c->dAccum.p, c->stream);
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
 }

@@ -1,0 +1,216 @@
+// mi355pt — what the translation units behind include/mi355pt.h share: the context, its device buffers, the error helpers, the tuning
+// defines and the few functions of pt_api.hip that the frame drivers (pt_frame.hip) call. Private: nothing here is exported.
+#pragma once
+#include "../../include/mi355pt.h"
+#include "pt_wavefront.h"
+#include "pt_stableplanes_launch.h"
+#include "pt_build.h"
+#include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+using namespace ptk;
+
+template <typename T> struct DevBuf {
+    T* p = nullptr; size_t n = 0;
+    hipError_t resize(size_t count) {
+        if (count <= n && p) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+        hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
+        if (e == hipSuccess) n = count ? count : 1;
+        return e;
+    }
+    hipError_t upload(const T* src, size_t count, hipStream_t st) {
+        hipError_t e = resize(count); if (e != hipSuccess) return e;
+        if (!count) return hipSuccess;
+        return hipMemcpyAsync(p, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
+    }
+    hipError_t upload(const std::vector<T>& v, hipStream_t st) { return upload(v.data(), v.size(), st); }
+    void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
+
+struct HostTexture { uint w, h, mipLevels; std::vector<std::vector<ptk::float4>> mips; };
+
+static const uint TILE = 32;
+static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per queue (2 queues per pipelined batch, 16 B each)
+#ifndef PT_SHARD_TILE_GROUP
+#define PT_SHARD_TILE_GROUP 1      // consecutive Morton-ordered 32x32 tiles dealt to the same rank (locality vs load balance)
+#endif
+#ifndef PT_PIPELINE_FULL_AT
+// paths per pt_render call from which all PT_PIPELINE_BATCHES are used (one rank of an 8-way sharded 4K frame has 4.1 M)
+#define PT_PIPELINE_FULL_AT (1u << 21)
+#endif
+#ifndef PT_PIPELINE_MID_BATCHES
+#define PT_PIPELINE_MID_BATCHES 2      // batches between 1 M paths and PT_PIPELINE_FULL_AT
+#endif
+#ifndef PT_CLASSIFY_FROM
+// passes with fewer paths skip k_classify (class-ordered shading pays through coherence, which a handful of waves do not have)
+#define PT_CLASSIFY_FROM 65536u
+#endif
+#ifndef PT_SP_FILL_CLASSES
+// the stable-plane fill pass shades in class order (k_classify), like reference mode; 0: queue order (A/B)
+#define PT_SP_FILL_CLASSES 1
+#endif
+#ifndef PT_SP_FILL_RANGED
+// the fill pass's first traversal launch uses FirstHitFromVBuffer's narrowed ray interval (pt_stableplanes.h firstHitInterval);
+// 0: the whole ray (A/B) — same hits
+#define PT_SP_FILL_RANGED 1
+#endif
+#ifndef PT_TAIL_PATHS
+// a batch with at most this many live paths is finished by the tail kernel (pt_tail.hip, pt_set_tail_paths); 0: never. With fused traversal
+// launches and free-running small passes a pass of tens of thousands of paths is cheaper as a wavefront pass than in the tail kernel's
+// under-filled GPU (rank of eight 12.56 -> 12.11 ms without it; the threshold was 32768 before those two), while the chains of passes that
+// hold a few hundred paths each — nested-dielectric re-traces: C5 runs 19 passes, twelve of them below 10 k paths at ~0.25 ms each — are
+// what the kernel is for: 4096 takes C5's rank of eight 13.9 -> 13.2 ms, C3's 12.0 -> 11.8 (profiles/r06o_tail_small_ab.txt)
+#define PT_TAIL_PATHS 4096u
+#endif
+#ifndef PT_FUSED_TRAVERSAL
+// pt_set_fused_traversal (default: on — it pays at every size, profiles/r06b_fused_traversal_ab.txt): 0 = every bounce traces its
+// visibility rays in a launch of their own, 1 = together with the closest-hit rays of the next bounce (k_trace_pair, pt_wavefront.hip),
+// 2 = by the size of the call (PT_FUSED_BELOW)
+#define PT_FUSED_TRAVERSAL 1u
+#endif
+#ifndef PT_FUSED_BELOW
+// mode 2: calls of fewer paths than this fuse (one rank of a 4- or 8-way sharded 4K frame, 1080p frames); a full 4K x 4 spp frame (33 M)
+// keeps its own launches
+#define PT_FUSED_BELOW (12u << 20)
+#endif
+#ifndef PT_COMPACT_POOL
+// pt_render keeps the live paths' state compacted by queue position (ptk::PathPool::home; environment MI355PT_COMPACT_POOL overrides)
+#define PT_COMPACT_POOL 1
+#endif
+#ifndef PT_FREE_RUN_BELOW
+// pt_render: once every live batch holds fewer paths than this, the batches stop advancing in lockstep (0: lockstep to the end)
+#define PT_FREE_RUN_BELOW (1u << 22)
+#endif
+#ifndef PT_PIPELINE_BATCHES
+// independent sub-frame batches pt_render keeps in flight on separate streams (A/B on C3 in DESIGN.md)
+#define PT_PIPELINE_BATCHES 4
+#endif
+// a full task queue is reported as an error (pt_render), it does not silently disable splitting
+
+#pragma GCC visibility pop
+struct pt_context {      // (the type include/mi355pt.h names: default visibility, like its declaration there)
+    int device = 0; hipStream_t stream = nullptr; uint shardRank = 0, shardCount = 1;
+    // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
+    hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
+    uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0;
+    std::string lastError;
+    // host copies of the scene (kept for re-bake / animation)
+    std::vector<uint> indices; std::vector<float> positions; std::vector<ptk::float2> uvs; std::vector<uint> normals, tangents;
+    std::vector<GeometryDesc> geometries; std::vector<MeshDesc> meshes; std::vector<InstanceDesc> instances;
+    std::vector<ptk::PTMaterialData> materials; std::vector<HostTexture> textures; HostTexture envTex; bool envEnabled = false;
+    float3x4 envToWorld, envToLocal; ptk::float3 envColorMul;
+    // sceneDirLights: world-space lights of the loaded scene (pt_set_scene_directional_lights), converted at bake time
+    uint envCubeDim = 2048; std::vector<ptk::EnvDirectionalLight> envDirLights, sceneDirLights; bool envCubeDirty = true;
+    ptk::EnvCube envCube;      // EnvMapBaker state (pt_set_environment_bake)
+    std::vector<PolymorphicLightInfoFull> analyticLights;
+    std::vector<SubInstanceData> subInstances; std::vector<ptk::uint2> subInstToInstGeom; std::vector<ptk::uint2> primInfo;
+    std::vector<uint> subInstFirstPrim;
+    // (light weights / proxy table live on the device only)
+    std::vector<ptk::PolymorphicLightInfo> lights; std::vector<ptk::PolymorphicLightInfoEx> lightsEx; std::vector<uint> envLookup;
+    uint envLookupDim = 0; uint numProxies = 0, envLightsBaked = 0;
+    DevBuf<float> dLightW; DevBuf<uint> dProxyOffsets; void* dScanTemp = nullptr; size_t scanTempBytes = 0;
+    // device
+    DevBuf<uint> dIndices, dNormals, dTangents, dProxyCounters, dProxyIndices, dEnvLookup, dOwned, dQueue[2], dEmissiveList, dEmissiveOffsets;
+    // pt_set_motion_history: the previous frame's pose; the (first, count) vertex ranges in which it differs from the current one
+    DevBuf<float> dPrevPositions; DevBuf<InstanceDesc> dPrevInstances; bool motionHistory = false, prevAllStale = false;
+    std::vector<uint32_t> prevStaleRanges;
+    DevBuf<float> dPositions; DevBuf<ptk::float2> dUvs; DevBuf<GeometryDesc> dGeometries; DevBuf<InstanceDesc> dInstances;
+    DevBuf<SubInstanceData> dSubInstances;
+    DevBuf<ptk::AlphaPlane> dAlphaPlanes; DevBuf<unsigned char> dAlphaPool; DevBuf<ptk::ShadeTri> dShadeTris;
+    DevBuf<ptk::uint2> dSubInstToInstGeom, dPrimInfo; DevBuf<ptk::PTMaterialData> dMaterials; DevBuf<TexInfo> dTexInfos; DevBuf<ptk::float4> dTexels;
+    // pt_set_procedural_sky
+    bool skyEnabled = false; ptk::ProceduralSkyContext sky; DevBuf<ptk::float4> dSkyTex[4]; DevBuf<ptk::ProceduralSkyContext> dSky;
+    DevBuf<ptk::uint2> dSkyLowRes;
+    // pt_set_environment_cube: the environment image as a cube map (RGBA16F), uploaded by the setter
+    DevBuf<ptk::uint2> dEnvImageCube; uint envImageCubeDim = 0;
+    // envCompression: EnvMapBaker's BC6U compression (0 off, 1 fast)
+    DevBuf<ptk::uint2> dEnvCube, dEnvCubeSource; DevBuf<ptk::EnvDirectionalLight> dEnvDirLights; uint envCompression = 0;
+    DevBuf<ptk::PolymorphicLightInfo> dLights; DevBuf<ptk::PolymorphicLightInfoEx> dLightsEx;
+    // NEE-AT (pt_set_local_light_sampling): the screen-tile local samplers as the host hands them in, and the feedback reservoirs of the
+    // last pt_render call (one plane per sample)
+    DevBuf<uint> dLocalTable; uint localResX = 0, localResY = 0, localJitterX = 0, localJitterY = 0, localMaxLight = 0;
+    float localRatio = 0.f, sscThreshold = 0.f; bool feedbackRequired = false;
+    DevBuf<float> dFbWeight; DevBuf<uint> dFbCand; DevBuf<ptk::float4> dSq3; uint fbSamples = 0;
+    // pt_set_light_importance_boost: ImportanceBooster's frustum term (mul 0: off)
+    ptk::LightFrustumBoost lightBoost = {}; bool weightsDirty = false;
+    // NEE-AT with the baker in the loop (pt_set_neeat): what LightsBaker keeps between frames (LightsBaker.h:225-260) and the textures /
+    // buffers its feedback passes bind
+    struct NeeAt {
+        bool enabled = false; float globalFeedbackWeight = 0.75f, localRatio = 0.65f, sscThreshold = 0.3f, dropoff = 0.005f, intensityDeltaMul = 64.0f;
+        bool preFilter = true;
+        uint updateCounter = 0; float jitterF[2] = {0, 0}; uint jitter[2] = {0, 0}, prevJitter[2] = {0, 0};
+        bool feedbackFilled = false, lastFeedbackAvailable = false; uint historicTotalLightCount = 0, W = 0, H = 0, nHist = 0;
+        // between UpdateBegin and UpdateEnd of a frame (realtime mode: the build pass runs in between)
+        bool frameOpen = false, frameFeedbackAvailable = false, frameLocalAvailable = false, exportDepth = true; uint framePrevLightCount = 0;
+        DevBuf<float> fbW, scW, blW, snapW, curW, histW; DevBuf<uint> fbC, scC, blC, snapC, local, counters;
+        // the exported depth of the last traced frame / of the one before; columns 2 and 3 of pt_set_view_projection's matrix
+        DevBuf<float> depth, histDepth; bool haveClip = false; float clipZ[4] = {0, 0, 0, 0}, clipW[4] = {0, 0, 0, 0};
+        // tile-sharded frames: the exchange of the owned pixels' reservoirs between frames
+        DevBuf<uint> xSend, xRecv; DevBuf<uint> xPixels; uint xW = 0, xH = 0;
+        void reset() {
+            W = H = 0; updateCounter = 0; jitterF[0] = jitterF[1] = 0; jitter[0] = jitter[1] = prevJitter[0] = prevJitter[1] = 0;
+            feedbackFilled = lastFeedbackAvailable = false; frameOpen = false; exportDepth = true; historicTotalLightCount = 0; nHist = 0;
+        }
+        void free() {
+            fbW.free(); scW.free(); blW.free(); snapW.free(); curW.free(); histW.free(); fbC.free(); scC.free(); blC.free(); snapC.free();
+            local.free(); counters.free(); xSend.free(); xRecv.free(); xPixels.free(); depth.free(); histDepth.free();
+        }
+    } neeat;
+    // the path pool (ensure_pool). ...b: the second array set of a compacted pool (pt_render)
+    DevBuf<ptk::uint4> dS0, dS1, dS2, dS3, dS4, dHit, dS0b, dS1b, dS3b, dS4b, dHitb; DevBuf<ptk::float4> dSq0, dSq1, dSq2, dAccum, dScratch4;
+    DevBuf<WaveCounters> dCounters; DevBuf<ptk::uint2> dTravSpill; DevBuf<ptk::TravTask> dTaskQ; DevBuf<uint> dTravCounts, dResolveList;
+    DevBuf<unsigned long long> dBestKey;
+    // ...Sh: the visibility rays' own straggler state in a frame of fused traversal launches
+    DevBuf<ptk::TravTask> dTaskQSh; DevBuf<uint> dResolveListSh; DevBuf<unsigned long long> dBestKeySh;
+    std::vector<TexInfo> texInfos; TexInfo envTexInfo;
+    BvhBuildBuffers bvh; bool bvhAllocated = false; uint numTris = 0; uint bvhBuilder = BVH_BUILDER_SAH;
+    DeviceScene dsc;
+    // frame state
+    ptk::PtSettings S; ptk::PathTracerCameraData cam; uint width = 0, height = 0, accumCount = 0; std::vector<uint> owned;
+    std::vector<std::vector<uint>> shardPixels;
+    std::vector<float> hostRadiance; bool countersEnabled = false;
+    bool geomDirty = true, lightsDirty = true, texDirty = true;
+    double buildMs = 0, refitMs = 0, lightBakeMs = 0;
+    uint poolCapacity = 0; size_t shadowCapacity = 0;
+    // stable planes (pt_build_stable_planes): the realtime mode's per-frame buffers (RenderTargets.cpp:60-141, 340-352) of the last pre-pass
+    DevBuf<uint> dSpHeader, dSpThroughput; DevBuf<ptk::StablePlane> dSpPlanes; DevBuf<ptk::uint2> dSpRadiance, dSpMotion;
+    DevBuf<float> dSpDepth, dSpHitT; uint spW = 0, spH = 0; bool spGathered = false;
+    DevBuf<ptk::uint4> dSpMark; DevBuf<ptk::float4> dSpNewL;      // scratch of the fill passes
+    DevBuf<float> dSpScratch; DevBuf<uint> dSpGatherSend, dSpGatherRecv, dSpGatherPixels; uint spGatherW = 0, spGatherH = 0;
+    // the denoiser buffers (pt_denoiser_prepare_dlss_rr / _nrd, pt_denoiser.h), allocated zeroed for a frame size by the first prepare call
+    DevBuf<uint> dDnRRDiff, dDnRRSpec, dDnRRSpecMV; DevBuf<ptk::uint2> dDnRRNormal, dDnMotion; DevBuf<float> dDnViewZ, dDnRoughness;
+    DevBuf<ptk::float4> dDnNormal, dDnDiff, dDnSpec;
+    DevBuf<unsigned char> dDnDisocclusion, dDnHistoryClamp; uint dnW = 0, dnH = 0;
+    // the sample index of the last build pass: Bridge::getSampleIndex's sampleBaseIndex for the NRD pass's camera rays
+    uint spSampleBase = 0;
+    // frame gather (pt_comm_init / pt_gather)
+    ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
+    std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
+};
+
+#pragma GCC visibility push(hidden)
+
+inline int fail(pt_context* c, int code, const std::string& msg) { if (c) c->lastError = msg; return code; }
+#define PT_CHECK_HIP(c, expr) \
+    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+// ---- pt_api.hip, for the frame drivers
+int prepare(pt_context* c);                          // whatever is dirty — textures, environment cube, geometry, lights — brought up to date
+int neeat_exchange_feedback(pt_context* c);          // tile shards with a communicator: the other ranks' reservoirs and depth
+// One frame of LightsBaker::UpdateBegin (NEEAT_BEGIN) / UpdateEnd (NEEAT_END) for the NEE-AT layer; see the definition
+enum { NEEAT_BEGIN = 1, NEEAT_END = 2, NEEAT_BOTH = 3 };
+int neeat_frame(pt_context* c, int phases = NEEAT_BOTH, const float* depth = nullptr, const ptk::uint2* motion = nullptr);
+// ---- pt_frame.hip
+// the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
+// passes that only address the buffers need: pack / unpack, merge, read-back)
+StablePlanesContext sp_context(pt_context* c, const PtStablePlanesParams* params);
+// t += o for every additive field of PtFrameStats (the batches of a call, the samples of a call that traces them one frame at a time;
+// maxima stay maxima)
+void add_frame_stats(PtFrameStats& t, const PtFrameStats& o);
+
+#pragma GCC visibility pop

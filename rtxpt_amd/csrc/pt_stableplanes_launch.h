@@ -1,4 +1,4 @@
-// mi355pt — launches of the stable-plane build pass (pt_stableplanes.hip), called by pt_build_stable_planes (pt_api.hip)
+// mi355pt — launches of the stable-plane build pass (pt_stableplanes.hip), called by pt_build_stable_planes (pt_frame.hip)
 #pragma once
 #include "pt_wavefront.h"
 #include "pt_stableplanes_device.h"

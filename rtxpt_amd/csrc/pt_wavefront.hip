@@ -146,9 +146,6 @@ __global__ void __launch_bounds__(256) k_resolve_extend(DeviceScene sc, PathPool
 #ifndef PT_SHADE_MIN_BLOCKS
 #define PT_SHADE_MIN_BLOCKS 1
 #endif
-#ifndef PT_SHADE_BLOCK_APPEND
-#define PT_SHADE_BLOCK_APPEND 1      // 1: k_shade appends to the extend / shadow queues with one atomic per block and counter, 0: one per wave
-#endif
 #ifndef PT_SHADE_PROBE
 #define PT_SHADE_PROBE 0
 #endif
@@ -205,6 +202,7 @@ __global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __
 template <bool MULTI, class PKC, bool NEEAT, bool COMPACT = false>
 __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(PKC k, PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr,
                                                uint* __restrict__ queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc, const uint* __restrict__ classCount, PathPool outPool) {
+    static_assert(!COMPACT || !PT_SHADE_PROBE, "the PT_SHADE_PROBE timing builds do not know the compacted pool: take the COMPACT launch out of launch_shade and run with MI355PT_COMPACT_POOL=0");
     const uint count = *countInPtr;
     uint i = blockIdx.x * (uint)PT_SHADE_BLOCK + threadIdx.x;
     bool inRange = i < count;
@@ -252,7 +250,6 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
         }
 #endif
     }
-#if PT_SHADE_BLOCK_APPEND
     // Queue appends, one atomic per BLOCK and counter: the four waves' counts meet in LDS, thread 0 reserves both ranges. A launch of 33 M paths has 518 k
     // waves; one returning atomic per wave on each of three words — all waves of the GPU on the same three addresses — is what the kernel waited for
     // (same-address atomics serialise in the L2: ~10^8 per second and address). The hit count needs no atomic at all when the paths were classified: it is the
@@ -287,18 +284,6 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
     }
     if (classCount) { if (blockIdx.x == 0u && threadIdx.x == 0u) atomicAdd(&wc->hits, (unsigned long long)classCount[0] + classCount[1]); }
     else wave_add64(isHit ? 1ull : 0ull, &wc->hits);
-#else
-    uint slot = wave_append(alive, countOutPtr);
-    if (alive) queueOut[slot] = p;
-    uint sslot = MULTI ? 0u : wave_append(req.valid, &wc->shadowCount);
-    if (!MULTI && req.valid) {
-        sq.q0[sslot] = make_float4(req.origin.x, req.origin.y, req.origin.z, req.tmax);
-        sq.q1[sslot] = make_float4(req.dir.x, req.dir.y, req.dir.z, asfloat(p));
-        sq.q2[sslot] = make_float4(req.radiance.x, req.radiance.y, req.radiance.z, 0.f);
-        if (NEEAT && sq.q3) sq.q3[sslot] = make_float4(req.fbWeight, req.fbRandom, asfloat(req.fbLight), asfloat(req.rrFix));
-    }
-    wave_add64(isHit ? 1ull : 0ull, &wc->hits);
-#endif
 }
 
 template <bool GROUPED>
@@ -799,7 +784,8 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
 // One launch for the closest-hit rays of the extend queue AND the visibility rays the previous vertex left in the shadow queue (k_trace_pair), then the task
 // rounds and resolve passes of both. auxE / auxS: separate task queues, counters, merge keys and resolve lists. The grid is what the two launches would use if
 // it fits the bound, else the bound split by ray count (a visibility ray costs about what a closest-hit ray costs: 0.50 against 0.44 ns on C3). Zeroes
-// *shCountPtr at its end.
+// *shCountPtr at its end. Precondition: the bound (auxE.maxBlocks, where set) is >= 2 — each half needs a block, and with a bound of 1 the visibility half
+// would get none while its count is zeroed all the same; pt_render clamps the only way in (MI355PT_MAX_BLOCKS).
 void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* extCountPtr, uint extCount, ShadowQueue sq, uint* shCountPtr, uint shCount, WaveCounters* wc, TravAux auxE, TravAux auxS, hipStream_t st) {
     const uint rpc = rays_per_chunk(extCount + shCount);
     const uint bound = (auxE.maxBlocks && auxE.maxBlocks < T8_MAX_BLOCKS) ? auxE.maxBlocks : T8_MAX_BLOCKS;

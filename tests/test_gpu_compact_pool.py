@@ -1,4 +1,4 @@
-"""The compacted path pool (ptk::PathPool::home; rtxpt_amd/csrc/pt_api.hip pt_render, pt_wavefront.hip k_shade<..., COMPACT>) on the device (run with -m gpu): from the second bounce on a
+"""The compacted path pool (ptk::PathPool::home; rtxpt_amd/csrc/pt_frame.hip pt_render, pt_wavefront.hip k_shade<..., COMPACT>) on the device (run with -m gpu): from the second bounce on a
 surviving path's state is written at its position in the extend queue, into the other of two array sets, instead of at its home slot; only throughput | radiance stays at home. Same values in
 another place: the frame, the ray counts and the hit count equal the home-slot layout's, bit for bit — on one, two and four pipelined batches, with the tail kernel (which scatters the live
 paths back to their home slots first) at several thresholds, with fused and separate traversal launches, continued accumulations, nested dielectrics, tile shards. MI355PT_COMPACT_POOL is

@@ -50,7 +50,7 @@ for f in glob.glob(d + "/**/stats_kernel_stats.csv", recursive=True):
         stats[n] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) * 1e-6, "total_ms": float(r["TotalDurationNs"]) * 1e-6, "percent": float(r["Percentage"])}
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rtxpt_amd
-out = {"source": "tools/profile_round.sh: rocprofv3 --kernel-trace --pmc (separate passes), 1 %s step of bench.py's default workload" % ("pipelined (product composition: fused traversal launches, compacted pool; rocprofv3 serialises the dispatches it counts)" if os.environ.get("PIPELINED") else "serial-kernel"),
+out = {"source": "tools/profile_round.sh: rocprofv3 --pmc (separate passes), 1 %s step of bench.py's default workload" % ("pipelined (product composition: fused traversal launches, compacted pool; rocprofv3 serialises the dispatches it counts)" if os.environ.get("PIPELINED") else "serial-kernel"),
        "kernel_source_sha256": rtxpt_amd.kernel_source_digest(),      # bench.py quotes these counters only for the kernels they were collected on
        "library_sha256": rtxpt_amd.library_digest(),                  # ... and the binary they ran in
        "issue_ceilings": {"total_instr_per_simd_cycle": 0.486, "four_cycle_class_instr_per_simd_cycle": 0.248, "source": "profiles/r06a_valu_ceiling.txt (tools/valu_ceiling on this GPU)"},
