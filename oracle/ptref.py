@@ -166,7 +166,7 @@ def refpin_pt(variant=(2, 1, 1, 1, 1, 1), lp16=False, mode=0):
         return _pin_pt[key]
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(os.path.dirname(_PIN), "librefpin_pt_%d%d%d%d%d%d%s%s.so" % (tuple(variant) + ("_lp16" if lp16 else "", "_m%d" % mode if mode else "")))
-    srcs = [os.path.join(here, "refpin", f) for f in ("hlsl_tu.py", "hlsl_shim.h", "hlsl_pt_stubs.h", "hlsl_pt_bridge_stubs.h", "hlsl_pt_wrappers.inc", "hlsl_lbfb_stubs.h", "hlsl_envbake_stubs.h", "hlsl_emisb_stubs.h")] + [os.path.join(here, "ptref", f) for f in os.listdir(os.path.join(here, "ptref"))]
+    srcs = [os.path.join(here, "refpin", f) for f in ("hlsl_tu.py", "hlsl_shim.h", "hlsl_pt_stubs.h", "hlsl_pt_bridge_stubs.h", "hlsl_pt_wrappers.inc", "hlsl_postprocess_stubs.h", "hlsl_lbfb_stubs.h", "hlsl_envbake_stubs.h", "hlsl_emisb_stubs.h")] + [os.path.join(here, "ptref", f) for f in os.listdir(os.path.join(here, "ptref"))]
     stale = not os.path.exists(path) or any(os.path.getmtime(f) > os.path.getmtime(path) for f in srcs)
     if stale:
         if not os.path.isdir("/root/reference/Rtxpt/Shaders"):
@@ -715,6 +715,102 @@ def denoise_spec_hit_t(depth, spec_hit_t, reference=False):
     if reference: refpin_pt().refpt_denoise_spec_hit_t(w, h, _p(d), _p(t))
     else: lib().ptref_denoise_spec_hit_t(w, h, _p(d), _p(t))
     return t
+
+
+# ---- the denoiser passes of PostProcess.hlsl (reference text only: the oracle has no restatement of them; the numpy one is tests/denoiser_inputs_ref.py)
+DENOISER_RR_BUFFERS = {"rr_diffuse_albedo": ((), np.uint32), "rr_specular_albedo": ((), np.uint32), "rr_normal_roughness": ((4,), np.uint16), "rr_specular_motion_vectors": ((2,), np.uint16)}
+DENOISER_NRD_BUFFERS = {"nrd_view_z": ((), np.float32), "nrd_motion_vectors": ((4,), np.uint16), "nrd_normal_roughness": ((4,), np.float32), "nrd_diff_radiance_hit_dist": ((4,), np.float32),
+                        "nrd_spec_radiance_hit_dist": ((4,), np.float32), "nrd_roughness": ((), np.float32), "nrd_disocclusion_threshold_mix": ((), np.uint8),
+                        "nrd_combined_history_clamp_relax": ((), np.uint8)}      # keyed and laid out as rtxpt_amd.DENOISER_BUFFERS
+REBLUR_HIT_DIST_PARAMS = (3.0, 0.1, 20.0, -25.0)      # NRD's ReblurHitDistanceParameters defaults; the recorder stand-in takes and ignores them
+
+
+class _PpFrame(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("sampleBaseIndex", ctypes.c_uint32), ("perPixelJitterAAScale", ctypes.c_float)] + \
+               [(k, ctypes.c_void_p) for k in ("prm", "dn", "hitParams", "cam", "header", "planes", "stableRadiance", "specHitT", "motionVectors")]
+
+
+class _PpNrdState(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("viewZ", "motionVectors", "normalRoughness", "diffRadianceHitDist", "specRadianceHitDist", "roughness", "disocclusionThresholdMix",
+                                               "combinedHistoryClampRelax", "normHitDistCalls")]
+
+
+def _pp_frame(frame, sp_params, dn_params, cam, settings, sample_base):
+    """the PpFrame of hlsl_pt_wrappers.inc plus the arrays it points into (kept alive by the caller)"""
+    hd = np.ascontiguousarray(frame["header"], np.uint32); _, h, w = hd.shape
+    dn = np.asarray(dn_params)
+    keep = [hd, np.ascontiguousarray(frame["planes"], np.uint32), np.ascontiguousarray(frame["stable_radiance"], np.uint16), np.ascontiguousarray(frame["spec_hit_t"], np.float32),
+            np.ascontiguousarray(frame["motion_vectors"], np.uint16), np.ascontiguousarray(sp_params),
+            np.concatenate([np.asarray(dn["matWorldToView"], np.float32).reshape(16), np.array([dn["preExposedGrayLuminance"], dn["denoiserRadianceClampK"], dn["DLSSRRBrightnessClampK"],
+                                                                                                 dn["stablePlanesSuppressPrimaryIndirectSpecularK"]], np.float32)]),
+            np.array(REBLUR_HIT_DIST_PARAMS, np.float32), np.ascontiguousarray(cam)]
+    assert keep[5].nbytes == 224 and keep[8].nbytes == 112 and keep[1].shape[0] * 80 == keep[1].nbytes
+    f = _PpFrame(w, h, int(sample_base), float(np.asarray(settings["perPixelJitterAAScale"]).reshape(-1)[0]))
+    adr = lambda a: a.ctypes.data
+    f.header, f.planes, f.stableRadiance, f.specHitT, f.motionVectors, f.prm, f.dn, f.hitParams, f.cam = (adr(a) for a in keep)
+    return f, keep, w, h
+
+
+def _pp_lib(settings, reference):
+    if not reference: raise NotImplementedError("the denoiser passes exist as the reference's text only (reference=True); the numpy restatement is tests/denoiser_inputs_ref.py")
+    L = refpin_pt(pt_variant(settings))
+    if L is None: raise RuntimeError("librefpin_pt.so not available (needs /root/reference)")
+    return L
+
+
+def denoiser_empty_state(w, h):
+    """the NRD buffers and the output colour as the library allocates them: zero"""
+    st = {k: np.zeros((h, w) + s, t) for k, (s, t) in DENOISER_NRD_BUFFERS.items()}; st["output_color"] = np.zeros((h, w, 4), np.float32)
+    return st
+
+
+def denoiser_prepare_dlss_rr(frame, sp_params, dn_params, cam, settings, sample_base=0, reference=True):
+    """PostProcess.hlsl's DENOISER_PREPARE_INPUTS + DENOISER_DLSS_RR `main` over a frame in get_stable_planes layout (the reference's text: librefpin_pt): the RR buffers keyed
+    as rtxpt_amd.DENOISER_BUFFERS (typed-target words) plus output_color float32 [h, w, 4]."""
+    L = _pp_lib(settings, reference); f, keep, w, h = _pp_frame(frame, sp_params, dn_params, cam, settings, sample_base)
+    out = {k: np.zeros((h, w) + s, t) for k, (s, t) in DENOISER_RR_BUFFERS.items()}; out["output_color"] = np.zeros((h, w, 4), np.float32)
+    L.refpt_denoiser_prepare_dlss_rr(ctypes.byref(f), _p(out["output_color"]), _p(out["rr_diffuse_albedo"]), _p(out["rr_specular_albedo"]), _p(out["rr_normal_roughness"]), _p(out["rr_specular_motion_vectors"]))
+    return out
+
+
+def denoiser_prepare_nrd(state, frame, sp_params, dn_params, cam, settings, plane, init, sample_base=0, use_relax=False, reference=True):
+    """PostProcess.hlsl's NRD DENOISER_PREPARE_INPUTS `main` for one plane, g_MiniConst.params = (plane, init) as Sample::Denoise sets them. state: the buffers before the call
+    (denoiser_empty_state, or what the previous call returned); an updated copy is returned. use_relax: the USE_RELAX 1 build of the pass (nrd_roughness is REBLUR's argument
+    only and keeps the state's value there). REBLUR builds also return "norm_hit_dist_calls" [h, w, 4]: (hitDist, roughness) of REBLUR_FrontEnd_GetNormHitDist's two calls."""
+    L = _pp_lib(settings, reference); f, keep, w, h = _pp_frame(frame, sp_params, dn_params, cam, settings, sample_base)
+    st = {k: np.array(state[k], DENOISER_NRD_BUFFERS[k][1], copy=True, order="C") for k in DENOISER_NRD_BUFFERS}; st["output_color"] = np.array(state["output_color"], np.float32, copy=True, order="C")
+    calls = np.zeros((h, w, 4), np.float32)
+    s = _PpNrdState(*[st[k].ctypes.data for k in ("nrd_view_z", "nrd_motion_vectors", "nrd_normal_roughness", "nrd_diff_radiance_hit_dist", "nrd_spec_radiance_hit_dist", "nrd_roughness",
+                                                  "nrd_disocclusion_threshold_mix", "nrd_combined_history_clamp_relax")], calls.ctypes.data)
+    L.refpt_denoiser_prepare_nrd(ctypes.byref(f), int(plane), 1 if init else 0, 1 if use_relax else 0, _p(st["output_color"]), ctypes.byref(s))
+    if not use_relax: st["norm_hit_dist_calls"] = calls
+    return st
+
+
+def denoiser_merge_nrd(state, frame, sp_params, dn_params, cam, settings, plane, diff, spec, sample_base=0, use_relax=False, reference=True):
+    """PostProcess.hlsl's DENOISER_FINAL_MERGE `main` (+ DenoiserNRD::PostDenoiseProcess) for one plane over the state a prepare call left, with the host's unpacked denoised
+    radiance diff / spec float32 [h, w, 4]: the updated output colour."""
+    L = _pp_lib(settings, reference); f, keep, w, h = _pp_frame(frame, sp_params, dn_params, cam, settings, sample_base)
+    out = np.array(state["output_color"], np.float32, copy=True, order="C")
+    d, s = np.ascontiguousarray(diff, np.float32), np.ascontiguousarray(spec, np.float32); vz = np.ascontiguousarray(state["nrd_view_z"], np.float32); mix = np.ascontiguousarray(state["nrd_disocclusion_threshold_mix"], np.uint8)
+    assert d.shape == (h, w, 4) and s.shape == (h, w, 4)
+    L.refpt_denoiser_merge_nrd(ctypes.byref(f), int(plane), 1 if use_relax else 0, _p(d), _p(s), _p(vz), _p(mix), _p(out))
+    return out
+
+
+def denoiser_nrd_sequence(frame, sp_params, dn_params, cam, settings, sample_base=0, state=None, use_relax=False):
+    """Sample::Denoise's order (Sample.cpp:2589): planes active - 1 .. 0, init on the first, each prepare followed by its merge with the identity as the denoiser.
+    Returns (state after the last merge, {plane: state after its prepare}, {plane: output colour after its merge})."""
+    hd = np.asarray(frame["header"]); _, h, w = hd.shape
+    active = int(min(max(int(np.asarray(sp_params["activeStablePlaneCount"])), 1), 3))
+    st = denoiser_empty_state(w, h) if state is None else state
+    per, merged = {}, {}
+    for n, p in enumerate(range(active - 1, -1, -1)):
+        st = denoiser_prepare_nrd(st, frame, sp_params, dn_params, cam, settings, p, n == 0, sample_base, use_relax)
+        per[p] = {k: v.copy() for k, v in st.items()}
+        st["output_color"] = denoiser_merge_nrd(st, frame, sp_params, dn_params, cam, settings, p, st["nrd_diff_radiance_hit_dist"], st["nrd_spec_radiance_hit_dist"], sample_base, use_relax)
+        merged[p] = st["output_color"].copy()
+    return st, per, merged
 
 
 def num_threads():

@@ -74,7 +74,7 @@ struct PackedHitInfo { uint4 d; };
 // PathTracerDebug.hlsli's context: the integrator only ever calls into it behind ENABLE_DEBUG_* switches that are off here
 struct DebugConstantsPin { uint exploreDeltaTree = 0; };
 struct DebugContext { DebugConstantsPin constants; uint2 pixelPos; bool IsDebugPixel() const { return false; } bool IsDebugPixel(uint2) const { return false; } void Reset(uint) {} void Reset(uint2, int) {} void SetPickedMaterial(uint) {}
-    template <class... A> void DrawDebugViz(A...) {} };
+    template <class... A> void DrawDebugViz(A...) {} template <class... A> void Init(A...) {} };      // Init: the compute passes of PostProcess.hlsl set the context up and never use it
 static inline void DebugCross(float3, float, float4) {}
 static inline bool isfinite(float v) { uint u; memcpy(&u, &v, 4); return (u & 0x7F800000u) != 0x7F800000u; }      // HLSL isfinite (PathTracerSample.hlsl FirstHitFromVBuffer)
 static inline float max3(float a, float b, float c) { return max(a, max(b, c)); }              // Utils/ColorHelpers.hlsli:19-27

@@ -518,6 +518,83 @@ namespace hl { static void stable_planes_merge(uint32_t w, uint32_t hgt, const u
     for (uint32_t y = 0; y < hgt; y++) for (uint32_t x = 0; x < w; x++) { const float3 c = stablePlanes.GetAllRadiance(uint2(x, y)); float* o = rgba + 4 * ((size_t)y * w + x); o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = 1.0f; }
 } }
 void refpt_stable_planes_merge(uint32_t w, uint32_t hgt, const uint32_t* header, const void* planes, const uint32_t* stableRadiance, float* rgba) { hl::stable_planes_merge(w, hgt, header, planes, stableRadiance, rgba); }
+} // extern "C" (the helpers below are templates)
+// ---- PostProcess.hlsl: the denoiser passes as the reference's own text (hl::pp, over hlsl_postprocess_stubs.h). One frame's inputs and constants travel in a PpFrame; the
+// outputs and the state that one pass leaves for the next are the caller's arrays, so a sequence of calls runs over what the previous call left, as Sample::Denoise's
+// dispatches do (Sample.cpp:2561-2619, 2712-2719). Every `main` runs over every thread of whole 8 x 8 groups; the shader rejects the threads beyond the frame.
+struct PpFrame {
+    uint32_t width, height, sampleBaseIndex; float perPixelJitterAAScale;
+    const ptref::StablePlanesParams* prm; const float* dn;          // dn: matWorldToView[16], preExposedGrayLuminance, denoiserRadianceClampK, DLSSRRBrightnessClampK, stablePlanesSuppressPrimaryIndirectSpecularK
+    const float* hitParams; const ptref::PathTracerCameraData* cam;  // hitParams: g_Const.denoisingHitParamConsts (REBLUR's hit-distance parameters; the recorder ignores them)
+    const uint32_t* header; const void* planes; const uint32_t* stableRadiance; const float* specHitT; const uint32_t* motionVectors;
+};
+struct PpNrdState { float* viewZ; uint16_t* motionVectors; float* normalRoughness; float* diffRadianceHitDist; float* specRadianceHitDist; float* roughness; unsigned char* disocclusionThresholdMix; unsigned char* combinedHistoryClampRelax;
+                    float* normHitDistCalls; };      // normHitDistCalls: [h][w][2][2] the (hitDist, roughness) arguments of REBLUR_FrontEnd_GetNormHitDist's two calls, or null
+namespace hl {
+struct PpBound { std::vector<float4> stableRadiance, motionVectors; };
+static void pp_bind(const PpFrame* f, uint32_t p0, uint32_t p1, PpBound& B) {
+    using namespace pp;
+    const uint32_t w = f->width, h = f->height; const size_t N = (size_t)w * h;
+    memset(&g_Const, 0, sizeof(g_Const)); memset(&g_MiniConst, 0, sizeof(g_MiniConst));
+    const ptref::StablePlanesConsts K = ptref::SP_make_consts(*f->prm, w, h, 0);
+    PathTracerConstants& k = g_Const.ptConsts;
+    static_assert(sizeof(PathTracerCameraData) == sizeof(ptref::PathTracerCameraData), "camera layout");
+    memcpy(&k.camera, f->cam, sizeof(k.camera));
+    k.imageWidth = w; k.imageHeight = h; k.sampleBaseIndex = f->sampleBaseIndex; k.perPixelJitterAAScale = f->perPixelJitterAAScale;
+    k._activeStablePlaneCount = K.activeStablePlaneCount; k.genericTSLineStride = K.genericTSLineStride; k.genericTSPlaneStride = K.genericTSPlaneStride;
+    k.preExposedGrayLuminance = f->dn[16]; k.denoiserRadianceClampK = f->dn[17]; k.DLSSRRBrightnessClampK = f->dn[18]; k.stablePlanesSuppressPrimaryIndirectSpecularK = f->dn[19];
+    auto mat = [](float4x4& M, const float* m) { for (int r = 0; r < 4; r++) M.r[r] = float4(m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]); };
+    mat(g_Const.view.matWorldToClip, K.matWorldToClip); mat(g_Const.view.matWorldToClipNoOffset, K.matWorldToClipNoOffset); mat(g_Const.previousView.matWorldToClipNoOffset, K.prevMatWorldToClipNoOffset);
+    mat(g_Const.view.matWorldToView, f->dn);
+    g_Const.view.clipToWindowScale = float2(K.clipToWindowScale[0], K.clipToWindowScale[1]); g_Const.previousView.clipToWindowScale = g_Const.view.clipToWindowScale;
+    if (f->hitParams) g_Const.denoisingHitParamConsts = float4(f->hitParams[0], f->hitParams[1], f->hitParams[2], f->hitParams[3]);
+    g_MiniConst.params = uint4(p0, p1, 0, 0);          // Sample::Denoise: (plane, initWithStableRadiance, 0, 0); the DLSS-RR pass: zeros
+    auto half4 = [](const uint32_t* q) { return float4(ptref::f16tof32(q[0] & 0xffffu), ptref::f16tof32(q[0] >> 16), ptref::f16tof32(q[1] & 0xffffu), ptref::f16tof32(q[1] >> 16)); };
+    B.stableRadiance.resize(N); B.motionVectors.resize(N);
+    for (size_t i = 0; i < N; i++) { B.stableRadiance[i] = half4(f->stableRadiance + 2 * i); B.motionVectors[i] = f->motionVectors ? half4(f->motionVectors + 2 * i) : float4(); }
+    u_StablePlanesHeader.p = (uint*)f->header; u_StablePlanesHeader.w = w; u_StablePlanesHeader.h = h; u_StablePlanesBuffer.p = (StablePlane*)f->planes; t_StablePlanesBuffer.p = (const StablePlane*)f->planes;
+    u_StableRadiance.p = B.stableRadiance.data(); u_StableRadiance.w = w; u_StableRadiance.h = h;
+    hl::u_MotionVectors.p = B.motionVectors.data(); hl::u_MotionVectors.w = w; hl::u_MotionVectors.h = h; hl::u_SpecularHitT.p = (float*)f->specHitT; hl::u_SpecularHitT.w = w; hl::u_SpecularHitT.h = h;
+}
+static void pp_unbind() { hl::u_MotionVectors.p = nullptr; hl::u_SpecularHitT.p = nullptr; pp::g_nrdCalls = nullptr; }
+template <class M> static void pp_dispatch(uint32_t w, uint32_t h, M entry) {
+    for (uint32_t y = 0; y < (h + 7) / 8 * 8; y++) for (uint32_t x = 0; x < (w + 7) / 8 * 8; x++) { pp::g_nrdPixel = (size_t)(y < h ? y : 0) * w + (x < w ? x : 0); pp::g_nrdCallCount = 0; entry(uint3(x, y, 0)); }
+}
+template <class T, class P> static void pp_target(T& t, P* p, uint32_t w, uint32_t h) { t.p = p; t.w = w; t.h = h; }
+}
+extern "C" {
+void refpt_denoiser_prepare_dlss_rr(const PpFrame* f, float* outputColor, uint32_t* rrDiffuseAlbedo, uint32_t* rrSpecAlbedo, uint16_t* rrNormalsAndRoughness, uint16_t* rrSpecMotionVectors) {
+    using namespace hl::pp; hl::PpBound B; hl::pp_bind(f, 0, 0, B); const uint32_t w = f->width, h = f->height;
+    hl::pp_target(u_OutputColor, (hl::float4*)outputColor, w, h); hl::pp_target(u_RRDiffuseAlbedo, rrDiffuseAlbedo, w, h); hl::pp_target(u_RRSpecAlbedo, rrSpecAlbedo, w, h);
+    hl::pp_target(u_RRNormalsAndRoughness, (Half4*)rrNormalsAndRoughness, w, h); hl::pp_target(u_RRSpecMotionVectors, (Half2*)rrSpecMotionVectors, w, h);
+    hl::pp_dispatch(w, h, [](hl::uint3 id) { rr::main(id); });
+    hl::pp_unbind();
+}
+// init: g_MiniConst.params[1], and the host's per-frame clear of CombinedHistoryClampRelax (RenderTargets::Clear, RenderTargets.cpp:380) before the frame's first plane
+void refpt_denoiser_prepare_nrd(const PpFrame* f, uint32_t plane, uint32_t init, uint32_t useRelax, float* outputColor, const PpNrdState* s) {
+    using namespace hl::pp; hl::PpBound B; hl::pp_bind(f, plane, init ? 1u : 0u, B); const uint32_t w = f->width, h = f->height;
+    if (init) memset(s->combinedHistoryClampRelax, 0, (size_t)w * h);
+    hl::pp_target(u_OutputColor, (hl::float4*)outputColor, w, h); hl::pp_target(u_DenoiserViewspaceZ, s->viewZ, w, h); hl::pp_target(u_DenoiserMotionVectors, (Half4*)s->motionVectors, w, h);
+    hl::pp_target(u_DenoiserNormalRoughness, (hl::float4*)s->normalRoughness, w, h); hl::pp_target(u_DenoiserDiffRadianceHitDist, (hl::float4*)s->diffRadianceHitDist, w, h);
+    hl::pp_target(u_DenoiserSpecRadianceHitDist, (hl::float4*)s->specRadianceHitDist, w, h);
+    hl::pp_target(u_DenoiserDisocclusionThresholdMix, s->disocclusionThresholdMix, w, h); hl::pp_target(u_CombinedHistoryClampRelax, s->combinedHistoryClampRelax, w, h);
+    std::vector<float> calls((size_t)w * h * 4, 0.0f); std::vector<unsigned char> called((size_t)w * h, 0);
+    g_nrdCalls = useRelax ? nullptr : calls.data();
+    if (useRelax) hl::pp_dispatch(w, h, [](hl::uint3 id) { relax::prepare::main(id); });
+    else hl::pp_dispatch(w, h, [&](hl::uint3 id) { reblur::prepare::main(id); if (id.x < w && id.y < h && g_nrdCallCount) called[g_nrdPixel] = 1; });
+    // REBLUR hands the plane's raw roughness to NRD through its second GetNormHitDist call (RELAX has no such argument): the pixels that made the call record it
+    if (!useRelax) for (size_t i = 0; i < (size_t)w * h; i++) if (called[i]) { s->roughness[i] = calls[4 * i + 3]; if (s->normHitDistCalls) memcpy(s->normHitDistCalls + 4 * i, &calls[4 * i], 16); }
+    hl::pp_unbind();
+}
+void refpt_denoiser_merge_nrd(const PpFrame* f, uint32_t plane, uint32_t useRelax, const float* diff, const float* spec, const float* viewZ, const unsigned char* disocclusionThresholdMix, float* outputColor) {
+    using namespace hl::pp; hl::PpBound B; hl::pp_bind(f, plane, 0, B); const uint32_t w = f->width, h = f->height;
+    hl::pp_target(u_InputOutput, (hl::float4*)outputColor, w, h); hl::pp_target(t_DiffRadiance, (const hl::float4*)diff, w, h); hl::pp_target(t_SpecRadiance, (const hl::float4*)spec, w, h);
+    hl::pp_target(t_DenoiserViewspaceZ, viewZ, w, h); hl::pp_target(t_DenoiserDisocclusionThresholdMix, (unsigned char*)disocclusionThresholdMix, w, h);
+    if (useRelax) hl::pp_dispatch(w, h, [](hl::uint3 id) { relax::merge::main(id); }); else hl::pp_dispatch(w, h, [](hl::uint3 id) { reblur::merge::main(id); });
+    hl::pp_unbind();
+}
+}
+extern "C" {
 // DenoisingGuidesBaker::DenoiseSpecHitT: the reference's compute shader, thread by thread, ping then pong (DenoisingGuidesBaker.cpp:62-84)
 void refpt_denoise_spec_hit_t(uint32_t w, uint32_t hgt, const float* depth, float* specHitT) {
     using namespace hl::dgb;

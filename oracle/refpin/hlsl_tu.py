@@ -316,6 +316,29 @@ def main_pt(ref):
         for body in extract_function(dtext, name, "DenoisingGuidesBaker.hlsl"):      # (int2 >= uint2: HLSL converts the signed operand)
             w(to_cpp("\n".join(l for l in body.split("\n") if not re.match(r"\s*#\s*define", l))).replace("any(pixelPos >= uint2(", "any(uint2(pixelPos) >= uint2(") + "\n")
     w("} // namespace dgb\n")
+    # PostProcess.hlsl: the denoiser's side of a realtime frame — the DLSS-RR prepare pass, the NRD prepare pass (one plane a dispatch) and the NRD final merge, with the helpers
+    # they call and DenoiserNRD::PostDenoiseProcess (NRD/DenoiserNRD.hlsli), over the stand-in bindings, typed targets and NRD recorders of hlsl_postprocess_stubs.h. The three
+    # entry points are all called `main`: each gets a namespace of its own, the two that depend on USE_RELAX once per setting.
+    ppath = os.path.join(ref, "Rtxpt/ProcessingPasses/PostProcess.hlsl")
+    ptext = strip_comments(open(ppath, encoding="latin-1").read())
+    ptext = re.sub(r"(?<![\w.])([01])\.xx\b", r"int2(\1,\1)", ptext)      # `0.xx` / `1.xx` next to int2 operands (the neighbour clamp): integer splats
+    ntext = strip_comments(open(os.path.join(ref, "Rtxpt/NRD/DenoiserNRD.hlsli"), encoding="latin-1").read())
+    mains = [ptext[m.start():match_brace(ptext, m.end() - 1) + 1] for m in re.finditer(r"^void main\s*\([^)]*\)\s*\{", ptext, re.M)]      # (extract_function keeps one definition per signature)
+    def entry(mark):          # the `main` whose body names `mark`
+        found = [b for b in mains if mark in b]
+        if len(found) != 1: raise SystemExit("hlsl_tu.py: %d entry points of PostProcess.hlsl name %s" % (len(found), mark))
+        return to_cpp(found[0]).replace("any(pixelPos >= uint2(", "any(uint2(pixelPos) >= uint2(")      # (as in DenoiseSpecHitT above: both sides unsigned)
+    w("// ======== PostProcess.hlsl (denoiser passes) + DenoiserNRD.hlsli (selected items)\nnamespace pp {\n#pragma push_macro(\"ENABLE_DEBUG_VIZUALISATIONS\")\n#undef ENABLE_DEBUG_VIZUALISATIONS\n#define ENABLE_DEBUG_VIZUALISATIONS 0\n")
+    w(re.search(r"^#define\s+VIEWZ_SKY_MARKER\b.*$", ptext, re.M).group(0) + "\n")
+    w('#include "%s/hlsl_postprocess_stubs.h"\n' % HERE)
+    for name in ("ComputeNeighbourDisocclusionRelaxation", "ComputeDisocclusionRelaxation", "ComputeSpecularMotionVector", "NRDRadianceClamp"):
+        for body in extract_function(ptext, name, "PostProcess.hlsl"): w(to_cpp(body) + "\n")
+    w("namespace rr {\n" + entry("u_RRDiffuseAlbedo") + "\n} // namespace rr\n")
+    for relax, space in ((0, "reblur"), (1, "relax")):
+        w("namespace %s {\n#define USE_RELAX %d\nnamespace DenoiserNRD {\n" % (space, relax))
+        for body in extract_function(ntext, "PostDenoiseProcess", "DenoiserNRD.hlsli"): w(to_cpp(body) + "\n")
+        w("} // namespace DenoiserNRD\nnamespace prepare {\n" + entry("initWithStableRadiance") + "\n}\nnamespace merge {\n" + entry("u_InputOutput") + "\n}\n#undef USE_RELAX\n} // namespace %s\n" % space)
+    w("#pragma pop_macro(\"ENABLE_DEBUG_VIZUALISATIONS\")\n} // namespace pp\n")
     w("} // namespace hl\n")
     w(open(os.path.join(HERE, "hlsl_pt_wrappers.inc")).read())
 

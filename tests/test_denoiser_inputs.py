@@ -16,8 +16,8 @@ f32 = np.float32
 W, H = 11, 9                  # no multiple of the 8 x 8 addressing tiles
 
 
-def _params(active=3, suppress=0.6, K=4096.0):
-    sp = scenes.stable_planes_params(W, H, np.eye(4, dtype=f32), active_planes=active)
+def _params(active=3, suppress=0.6, K=4096.0, w=W, h=H):
+    sp = scenes.stable_planes_params(w, h, np.eye(4, dtype=f32), active_planes=active)
     dn = np.zeros((), [("matWorldToView", "<f4", 16), ("preExposedGrayLuminance", "<f4"), ("denoiserRadianceClampK", "<f4"), ("DLSSRRBrightnessClampK", "<f4"),
                        ("stablePlanesSuppressPrimaryIndirectSpecularK", "<f4")])
     dn["matWorldToView"] = np.eye(4, dtype=f32).reshape(16); dn["preExposedGrayLuminance"] = 1.0; dn["denoiserRadianceClampK"] = 8.0
@@ -25,7 +25,7 @@ def _params(active=3, suppress=0.6, K=4096.0):
     return sp, dn
 
 
-def hand_frame():
+def hand_frame(W=W, H=H):
     """plane 0 everywhere (a surface at distance 2 straight ahead) except a sky column at x = 10; plane 1 (vertex 2) at (0, 0) alone and at (3..5, 4); plane 2 (vertex 3) at (4, 4);
     dominant plane 2 at (4, 4); stable radiance 0.25 at (7, 2); specular hit distance 3 at (3, 4) and (10, 0)"""
     fr = ref.make_frame(W, H)
@@ -42,10 +42,12 @@ def hand_frame():
 
 
 def hand_cases():
-    """the hand-built frames both suites run: (name, frame, params); three-plane, two-plane, one-plane, suppression off, K = 0"""
+    """the hand-built frames both suites run: (name, frame, params); three-plane, two-plane, one-plane, suppression off, K = 0, and the same frame at 13 x 7 (wider than high,
+    neither size a multiple of the 8 x 8 addressing tiles)"""
     fr = hand_frame(); out = []
     for name, kw in (("three_planes", {}), ("two_planes", dict(active=2)), ("one_plane", dict(active=1)), ("suppression_off", dict(suppress=0.0)), ("brightness_clamp_0", dict(K=0.0))):
         sp, dn = _params(**kw); out.append(dict(name=name, frame=fr, sp=sp, dn=dn, w=W, h=H))
+    sp, dn = _params(w=13, h=7); out.append(dict(name="frame_13x7", frame=hand_frame(13, 7), sp=sp, dn=dn, w=13, h=7))
     return out
 
 
@@ -154,12 +156,33 @@ def test_camera_rays_equal_the_oracle():
 
 
 def test_restatement_equals_the_committed_fixture():
+    """The fixture is made by the compiled reference text (tests/golden/make_denoiser_inputs_golden.py, which needs the reference checkout). This test needs only the oracle: it
+    rebuilds every fixture case's inputs and holds the restatement to every array of the fixture the restatement covers: the DLSS-RR buffers, the state after each plane's
+    prepare, the colour after each merge. The thin-lens case runs with the oracle's camera rays (the restatement's own stop at the pinhole camera)."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_dn_golden", os.path.join(ROOT, "tests", "golden", "make_denoiser_inputs_golden.py"))
     m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
-    got, g = m.generate(), np.load(GOLDEN)
-    assert sorted(got) == sorted(g.keys())
-    for k in got: assert np.array_equal(ref.canonical(got[k]), ref.canonical(g[k])), k
+    g = np.load(GOLDEN); seen = set()
+    def same(key, want):
+        assert want.dtype == g[key].dtype and want.shape == g[key].shape, key
+        assert np.array_equal(ref.canonical(want), ref.canonical(g[key])), key
+        seen.add(key)
+    for case, frame_keys in m.fixture_cases():
+        name, fr, sp, dn, w, h = case["name"], case["frame"], case["sp"], case["dn"], case["w"], case["h"]
+        for k in frame_keys: same(("frame_" if name == "zoo_fp32" else name + "_frame_") + k, np.asarray(fr[k]))
+        rr = ref.dlss_rr(fr, sp, dn, w, h); pre = "" if name == "zoo_fp32" else name + "_"
+        for k in m.RR: same(pre + k, rr[k])
+        same(pre + "rr_output_color", rr["output_color"])
+        rays = case["rays"] if case["rays"] is not None else {p: ref.camera_rays(case["cam"], case["S"], w, h, case["base"] + p) for p in range(3)}
+        st, per = ref.nrd_sequence(fr, sp, dn, w, h, rays)
+        for p in per:
+            for k in ref.NRD_KEYS + ("output_color",): same("%s_p%d_%s" % (name, p, k), per[p][k])
+            same("%s_p%d_merged" % (name, p), ref.nrd_merge(per[p], fr, w, h, p, per[p]["nrd_diff_radiance_hit_dist"], per[p]["nrd_spec_radiance_hit_dist"]))
+        if name == "zoo_fp32":
+            for k in ref.NRD_KEYS: same(k, st[k])
+            same("nrd_output_color", st["output_color"])
+        assert g[name + "_dims"].tolist() == [w, h, case["base"]]; seen.update(name + "_" + k for k in ("sp", "dn", "cam", "dims"))
+    assert seen == set(g.keys()), sorted(set(g.keys()) ^ seen)[:8]
 
 
 def test_header_declares_and_library_exports_the_entry_points():

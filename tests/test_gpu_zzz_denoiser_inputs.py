@@ -1,5 +1,6 @@
 """The denoiser passes of a realtime stable-plane frame on the device (run with -m gpu): pt_denoiser_prepare_dlss_rr, pt_denoiser_prepare_nrd and pt_denoiser_merge_nrd against the
-independent numpy restatement of PostProcess.hlsl (tests/denoiser_inputs_ref.py) over the device's own plane buffers, bit for bit, and against the committed fixture."""
+independent numpy restatement of PostProcess.hlsl (tests/denoiser_inputs_ref.py) over the device's own plane buffers, bit for bit, and against the committed fixture, which
+the reference's own PostProcess.hlsl text made (compiled by the oracle/refpin recipe): every buffer after every call, a thin-lens camera and a fuzz frame included."""
 import os, sys
 import numpy as np
 import pytest
@@ -8,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import denoiser_inputs_ref as ref
 import stable_planes_cases as spc
 import realtime_cases as rc
+import denoiser_text_cases as dtc
 from rtxpt_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +119,57 @@ def _push(t, frame, w, h):
     t.unpack_stable_planes(b.data_ptr(), b.numel() * 4, 0)
     back = t.get_stable_planes()
     assert np.array_equal(back["header"], frame["header"]) and np.array_equal(back["spec_hit_t"], frame["spec_hit_t"])
+
+
+FIXTURE_ZOO = {"zoo_fp32": ("zoo_fp32", {}), "zoo_lp16": ("zoo_lp16", {}), "zoo_two_planes_no_psr": ("zoo_two_planes_no_psr", {}), "zoo_thin_lens": ("zoo_fp32", dtc.THIN_LENS)}
+FIXTURE_PUSHED = ("hand_frame_13x7", "fuzz0")
+
+
+def _record(words, dtype): return np.frombuffer(np.ascontiguousarray(words).tobytes(), dtype)[0].copy()
+
+
+@pytest.mark.parametrize("name", list(FIXTURE_ZOO) + list(FIXTURE_PUSHED))
+def test_device_equals_the_reference_text_fixture(name):
+    """Every buffer after every call against tests/golden/denoiser_inputs_golden.npz, which the compiled PostProcess.hlsl text made (tests/golden/make_denoiser_inputs_golden.py):
+    the DLSS-RR pass, then Sample::Denoise's NRD sequence with the state after each plane's prepare and the colour after each merge. No restatement and no oracle in the loop;
+    the thin-lens case has no other reference than the text. Zoo cases render their frame on the device and check its plane inputs against the fixture's first; hand-built and
+    fuzz frames go in through pt_unpack_stable_planes."""
+    import rtxpt_amd as pt
+    g = np.load(GOLDEN)
+    w, h, base = (int(v) for v in g[name + "_dims"])
+    prm, dn, camd = _record(g[name + "_sp"], scenes.STABLE_PLANES_PARAMS_DTYPE), _record(g[name + "_dn"], pt.DENOISER_PARAMS_DTYPE), _record(g[name + "_cam"], scenes.CAMERA_DTYPE)
+    if name in FIXTURE_ZOO:
+        zoo, lens = FIXTURE_ZOO[name]
+        sc, camd2, S, prm2, _ = dtc.zoo_setup(zoo, w, h, **lens)
+        assert camd2.tobytes() == camd.tobytes() and np.asarray(prm2).tobytes() == prm.tobytes() and base == spc.SAMPLE
+        if lens: assert float(camd["ApertureRadius"]) > 0
+        t = _tracer(sc, camd, S, w, h)
+        t.build_stable_planes(base, prm); t.fill_stable_planes(base, prm, sub_samples=spc.SUBSAMPLES); t.denoise_spec_hit_t()
+        frame = t.get_stable_planes(); pre = "frame_" if name == "zoo_fp32" else name + "_frame_"
+        for k in ("header", "stable_radiance", "spec_hit_t", "motion_vectors"): assert np.array_equal(frame[k].view(np.uint8), g[pre + k].view(np.uint8)), (name, k)
+    else:
+        sc, cam = scenes.stable_planes_zoo(); S = scenes.config_settings("C2")
+        frame = {k: g["%s_frame_%s" % (name, k)] for k in ("header", "planes", "stable_radiance", "depth", "spec_hit_t", "motion_vectors", "throughput")}
+        t = _tracer(sc, camd, S, w, h)
+        t.build_stable_planes(base, scenes.stable_planes_params(w, h, scenes.view_projection(w, h, **cam)))
+        _push(t, frame, w, h)
+    rr = "" if name == "zoo_fp32" else name + "_"      # zoo_fp32's DLSS-RR arrays keep the names they have had
+    t.denoiser_prepare_dlss_rr(prm, dn)
+    got = t.get_denoiser_inputs(RR_KEYS)
+    for k in RR_KEYS: assert _eq(got[k], g[rr + k]), "%s: %s differs in %d values" % (name, k, _diff(got[k], g[rr + k]))
+    assert _eq(t.radiance(), g[rr + "rr_output_color"]), "%s: DLSS-RR colour differs in %d values" % (name, _diff(t.radiance(), g[rr + "rr_output_color"]))
+    active = int(min(max(int(prm["activeStablePlaneCount"]), 1), 3))
+    for n, p in enumerate(range(active - 1, -1, -1)):
+        t.denoiser_prepare_nrd(prm, dn, p, n == 0)
+        got = t.get_denoiser_inputs(ref.NRD_KEYS); got["output_color"] = t.radiance()
+        for k in ref.NRD_KEYS + ("output_color",):
+            want = g["%s_p%d_%s" % (name, p, k)]
+            assert _eq(got[k], want), "%s plane %d: %s differs in %d values" % (name, p, k, _diff(got[k], want))
+        dd, ss = _upload(got["nrd_diff_radiance_hit_dist"]), _upload(got["nrd_spec_radiance_hit_dist"])
+        t.denoiser_merge_nrd(p, dd.data_ptr(), ss.data_ptr())
+        want = g["%s_p%d_merged" % (name, p)]
+        assert _eq(t.radiance(), want), "%s plane %d: merged colour differs in %d values" % (name, p, _diff(t.radiance(), want))
+    t.close()
 
 
 def test_hand_built_corner_cases_on_the_device():
