@@ -407,6 +407,43 @@ int32_t pt_denoiser_merge_nrd(pt_context* ctx, uint32_t planeIndex, const float*
 int32_t pt_get_denoiser_inputs(pt_context* ctx, const PtDenoiserBuffers* host);
 /* the device pointers and row pitches of the denoiser buffers, for a denoiser on the same device that reads them in place */
 int32_t pt_denoiser_device_buffers(pt_context* ctx, PtDenoiserBuffers* out);
+
+/* ---- The device denoiser between pt_denoiser_prepare_nrd and pt_denoiser_merge_nrd: a RELAX-shaped spatio-temporal filter of the library's own (not NRD's text; the formulas are
+ * stated in docs/WIDENING.md N5), one plane per call, with history per plane as Sample::Denoise keeps one NRD instance per plane (Sample.cpp:2585-2612). The history of a plane is
+ * dropped — the next call behaves as with resetHistory — by pt_resize to another size, by pt_set_geometry (a new scene), by a call with resetHistory itself, and for a plane that
+ * was not denoised on the previous frame (a pt_build_stable_planes / pt_realtime_frame in between without a pt_denoise_plane of it: its history would be two frames old).
+ * The fields are the RELAX and common settings the reference sets, with its defaults (NrdConfig.cpp:15-47, SampleUI.h:294-296), and luminanceSigmaScale of our own. */
+typedef struct PtDenoiseSettings {
+    uint32_t atrousIterationNum;                   /* 5; 2..8 */
+    float    depthThreshold;                       /* 0.004: the spatial depth stop, relative to |viewZ| */
+    float    lobeAngleFraction;                    /* 0.7: the normal cone, in (0, 1] */
+    uint32_t diffuseMaxAccumulatedFrameNum;        /* 25 */
+    uint32_t specularMaxAccumulatedFrameNum;       /* 40 */
+    uint32_t diffuseMaxFastAccumulatedFrameNum;    /* 5 */
+    uint32_t specularMaxFastAccumulatedFrameNum;   /* 6 */
+    uint32_t enableAntiFirefly;                    /* 1 */
+    float    disocclusionThreshold;                /* 0.03: relative |viewZ| threshold of a history tap */
+    float    disocclusionThresholdAlternate;       /* 0.2: the threshold where nrdDisocclusionThresholdMix is 1 */
+    uint32_t useDisocclusionThresholdMix;          /* 1 */
+    float    luminanceSigmaScale;                  /* 4: the variance-guided colour stop reaches 0 at this many sigma; <= 0: no colour stop (weight 1) */
+} PtDenoiseSettings;
+int32_t pt_denoise_default_settings(PtDenoiseSettings* out);
+/* Denoises plane planeIndex over the NRD buffers the pt_denoiser_prepare_nrd(planeIndex) of this frame just left (temporal pass, history clamp, atrousIterationNum a-trous passes)
+ * and keeps that plane's history for the next frame. The result, still demodulated, is in two context-owned RGBA32F buffers (pt_denoised_device_buffers): diffuse with .w = 0,
+ * specular with the prepare pass's hit distance in .w; sky pixels (nrdViewZ == FLT_MAX) are 0. PT_ERROR_NOT_READY without a prepare of that plane on the current frame (one
+ * denoise per prepare), PT_ERROR_INVALID_ARGUMENT for planeIndex >= 3 or settings out of range. Sharded contexts: as the prepare passes. `sp` is the frame's parameter block. */
+int32_t pt_denoise_plane(pt_context* ctx, const PtStablePlanesParams* sp, const PtDenoiseSettings* settings, uint32_t planeIndex, uint32_t resetHistory);
+/* the device pointers of plane planeIndex's denoised buffers (what pt_denoiser_merge_nrd takes) and their row pitch in bytes */
+int32_t pt_denoised_device_buffers(pt_context* ctx, uint32_t planeIndex, void** diffDevice, void** specDevice, size_t* pitch);
+/* host copies (NULL: skip): the two denoised buffers, width x height x 4 floats each, and the plane's history lengths after the call, width x height x 2 floats (diffuse, specular) */
+int32_t pt_get_denoised(pt_context* ctx, uint32_t planeIndex, float* diff, float* spec, float* historyLength);
+/* The whole of Sample::Denoise's loop (Sample.cpp:2589): for planes activeStablePlaneCount - 1 .. 0: pt_denoiser_prepare_nrd (init on the first), pt_denoise_plane,
+ * pt_denoiser_merge_nrd with the plane's denoised buffers. Leaves the picture in the radiance buffer. */
+int32_t pt_denoise_frame(pt_context* ctx, const PtStablePlanesParams* sp, const PtDenoiserParams* params, const PtDenoiseSettings* settings, uint32_t resetHistory);
+/* DIAGNOSTIC, not part of the denoiser's interface proper: event timing of pt_denoise_plane's passes for tools/denoise_probe.py. Off by default; while off pt_denoise_plane records
+ * no event and takes no extra synchronisation. enable != 0 makes the following calls record it. ms (NULL: skip) receives the milliseconds of the last timed call's
+ * passes in order — temporal, history clamp, then the a-trous iterations — and *count their number. */
+int32_t pt_denoise_pass_times(pt_context* ctx, uint32_t enable, float* ms, uint32_t capacity, uint32_t* count);
 int32_t pt_neeat_reset(pt_context* ctx);                                                      /* LightsBaker::BakeSettings::ResetFeedback */
 int32_t pt_get_neeat_tables(pt_context* ctx, uint32_t tilesXY[2], uint32_t jitterXY[2], uint32_t* table, uint32_t tableCapacityWords);
 /* Tile-sharded frames (PtDeviceDesc.shardCount > 1; no reference analogue): a rank traces and feeds back for its own pixels, the baker's passes read whole neighbourhoods, so

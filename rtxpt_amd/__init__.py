@@ -38,6 +38,7 @@ EXPORTS = [
     "pt_default_tone_mapping_parameters", "pt_tonemap_from_parameters", "pt_scene_import_tone_mapping",
     "pt_stable_planes_plane_stride", "pt_build_stable_planes", "pt_fill_stable_planes", "pt_denoise_spec_hit_t", "pt_stable_planes_merge", "pt_get_stable_planes",
     "pt_denoiser_default_params", "pt_denoiser_prepare_dlss_rr", "pt_denoiser_prepare_nrd", "pt_denoiser_merge_nrd", "pt_get_denoiser_inputs", "pt_denoiser_device_buffers",
+    "pt_denoise_default_settings", "pt_denoise_plane", "pt_denoised_device_buffers", "pt_get_denoised", "pt_denoise_frame", "pt_denoise_pass_times",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -672,6 +673,24 @@ def denoiser_default_params(lib=None):
     return out
 
 
+# PtDenoiseSettings (include/mi355pt.h): the device denoiser's settings (pt_denoise_plane / pt_denoise_frame)
+DENOISE_SETTINGS_DTYPE = np.dtype([("atrousIterationNum", "<u4"), ("depthThreshold", "<f4"), ("lobeAngleFraction", "<f4"), ("diffuseMaxAccumulatedFrameNum", "<u4"),
+                                   ("specularMaxAccumulatedFrameNum", "<u4"), ("diffuseMaxFastAccumulatedFrameNum", "<u4"), ("specularMaxFastAccumulatedFrameNum", "<u4"),
+                                   ("enableAntiFirefly", "<u4"), ("disocclusionThreshold", "<f4"), ("disocclusionThresholdAlternate", "<f4"), ("useDisocclusionThresholdMix", "<u4"),
+                                   ("luminanceSigmaScale", "<f4")])
+
+
+def denoise_default_settings(lib=None, **overrides):
+    """pt_denoise_default_settings: the reference's RELAX defaults (NrdConfig.cpp:15-47, SampleUI.h:294-296), luminanceSigmaScale 4; keywords override fields"""
+    L = lib or load_library()
+    out = np.zeros((), DENOISE_SETTINGS_DTYPE)
+    f = L.pt_denoise_default_settings; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_denoise_default_settings")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -922,6 +941,42 @@ class PathTracer:
         f = self.L.pt_denoiser_device_buffers; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
         self._chk(f(self.h, ctypes.byref(b)), "pt_denoiser_device_buffers")
         return {k: (getattr(b, k), int(b.pitch[i])) for i, (k, _, _) in enumerate(DENOISER_BUFFERS)}
+
+    def denoise_plane(self, sp_params, settings, plane_index, reset_history=False):
+        """pt_denoise_plane: the device denoiser over the NRD buffers denoiser_prepare_nrd(plane_index) just left; settings: DENOISE_SETTINGS_DTYPE. Result: get_denoised()"""
+        prm = np.ascontiguousarray(sp_params); ds = np.ascontiguousarray(settings); assert prm.dtype.itemsize == 224 and ds.dtype == DENOISE_SETTINGS_DTYPE
+        f = self.L.pt_denoise_plane; f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(prm), _p(ds), int(plane_index), 1 if reset_history else 0), "pt_denoise_plane")
+
+    def denoised_device_buffers(self, plane_index):
+        """pt_denoised_device_buffers: (diffuse device pointer, specular device pointer, row pitch in bytes) of a plane's denoised radiance: what denoiser_merge_nrd takes"""
+        d, s, pitch = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        f = self.L.pt_denoised_device_buffers; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, int(plane_index), ctypes.byref(d), ctypes.byref(s), ctypes.byref(pitch)), "pt_denoised_device_buffers")
+        return d.value, s.value, int(pitch.value)
+
+    def get_denoised(self, plane_index):
+        """pt_get_denoised: (diffuse [h, w, 4] f32, specular [h, w, 4] f32, history lengths [h, w, 2] f32: diffuse, specular) of a plane after denoise_plane"""
+        h, w = self.height, self.width
+        d, s, n = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32), np.zeros((h, w, 2), np.float32)
+        f = self.L.pt_get_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, int(plane_index), _p(d), _p(s), _p(n)), "pt_get_denoised")
+        return d, s, n
+
+    def denoise_frame(self, sp_params, params, settings, reset_history=False):
+        """pt_denoise_frame: Sample::Denoise's loop — planes active - 1 .. 0: prepare (init on the first), denoise, merge; returns radiance()"""
+        prm = np.ascontiguousarray(sp_params); dn = np.ascontiguousarray(params); ds = np.ascontiguousarray(settings)
+        assert prm.dtype.itemsize == 224 and dn.dtype == DENOISER_PARAMS_DTYPE and ds.dtype == DENOISE_SETTINGS_DTYPE
+        f = self.L.pt_denoise_frame; f.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(prm), _p(dn), _p(ds), 1 if reset_history else 0), "pt_denoise_frame")
+        return self.radiance()
+
+    def denoise_pass_times(self, enable=True):
+        """pt_denoise_pass_times: switches the event timing of denoise_plane's passes on / off and returns the last timed call's milliseconds [temporal, clamp, a-trous 0, 1, ...]"""
+        ms = np.zeros(16, np.float32); n = ctypes.c_uint32()
+        f = self.L.pt_denoise_pass_times; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, 1 if enable else 0, _p(ms), 16, ctypes.byref(n)), "pt_denoise_pass_times")
+        return ms[:n.value].copy()
 
     def set_neeat(self, enable=True, global_feedback_weight=0.75, ratio=0.65, ssc_threshold=0.3, prefilter=True):
         """NEE-AT with the light baker in the loop (pt_set_neeat): every sample of render() becomes a frame — feedback passes, then the path tracer"""

@@ -604,6 +604,7 @@ int32_t pt_destroy(pt_context* c) {
     if (c->comm && g_rccl.lib) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
     c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
+    relax_free(c);
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
     c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
     if (c->bvhAllocated) bvh_free(c->bvh);
@@ -641,6 +642,7 @@ int32_t pt_set_geometry(pt_context* c, const PtGeometryBuffers* b, const PtGeome
     c->geometries.resize(nGeoms); memcpy(c->geometries.data(), geoms, sizeof(GeometryDesc) * nGeoms);
     c->meshes.resize(nMeshes); memcpy(c->meshes.data(), meshes, sizeof(MeshDesc) * nMeshes);
     c->geomDirty = true;
+    relax_drop_history(c);      // a new scene: the denoiser's history is of another one
     return PT_OK;
 }
 int32_t pt_set_instances(pt_context* c, const PtInstanceDesc* inst, uint32_t n) {
@@ -948,6 +950,7 @@ int32_t pt_set_settings(pt_context* c, const ::PtSettings* s) {
 int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
     if (!c || !w || !h || w > 65535 || h > 65535) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad size");
     (void)hipSetDevice(c->device);
+    if (w != c->width || h != c->height) relax_drop_history(c);
     c->width = w; c->height = h; c->accumCount = 0; c->fbSamples = 0;
     build_shards(c);
     PT_CHECK_HIP(c, c->dAccum.resize((size_t)w * h));
@@ -1298,19 +1301,7 @@ int32_t pt_denoiser_default_params(PtDenoiserParams* out) {
     out->stablePlanesSuppressPrimaryIndirectSpecularK = 0.6f;
     return PT_OK;
 }
-// the planes of the whole frame must be here: an unsharded context, or a sharded one after pt_gather_stable_planes / pt_unpack_stable_planes (the NRD pass reads neighbours)
-static int32_t dn_ready(pt_context* c) {
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes, pt_fill_stable_planes");
-    if (c->shardCount > 1 && !c->spGathered) return fail(c, PT_ERROR_NOT_READY, "the denoiser passes read the whole frame's planes: pt_gather_stable_planes / pt_unpack_stable_planes first");
-    return PT_OK;
-}
-static ptk::DenoiserBuffers dn_buffers(pt_context* c) {
-    ptk::DenoiserBuffers D;
-    D.RRDiffuseAlbedo = c->dDnRRDiff.p; D.RRSpecAlbedo = c->dDnRRSpec.p; D.RRNormalsAndRoughness = c->dDnRRNormal.p; D.RRSpecMotionVectors = c->dDnRRSpecMV.p;
-    D.ViewZ = c->dDnViewZ.p; D.MotionVectors = c->dDnMotion.p; D.NormalRoughness = c->dDnNormal.p; D.DiffRadianceHitDist = c->dDnDiff.p; D.SpecRadianceHitDist = c->dDnSpec.p;
-    D.Roughness = c->dDnRoughness.p; D.DisocclusionThresholdMix = c->dDnDisocclusion.p; D.CombinedHistoryClampRelax = c->dDnHistoryClamp.p;
-    return D;
-}
+// (dn_ready, dn_buffers: pt_context.h — the device denoiser's entry points in pt_relax_api.hip use them too)
 static int32_t dn_alloc(pt_context* c) {
     if (c->dnW == c->width && c->dnH == c->height) return PT_OK;
     const size_t N = (size_t)c->width * c->height;
@@ -1346,6 +1337,7 @@ int32_t pt_denoiser_prepare_nrd(pt_context* c, const PtStablePlanesParams* spPar
     PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
     launch_dn_prepare_nrd(k, sp_context(c, spParams), P, dn_buffers(c), planeIndex, initWithStableRadiance != 0u, c->spSampleBase, c->dAccum.p, c->stream);
     if (initWithStableRadiance) c->accumCount = 1;
+    c->dnPreparedPlane = (int)planeIndex;      // what pt_denoise_plane may run on
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
     return PT_OK;
 }

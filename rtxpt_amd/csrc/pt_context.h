@@ -4,6 +4,7 @@
 #include "../../include/mi355pt.h"
 #include "pt_wavefront.h"
 #include "pt_stableplanes_launch.h"
+#include "pt_denoiser.h"
 #include "pt_build.h"
 #include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
 #include <string>
@@ -188,6 +189,15 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     DevBuf<unsigned char> dDnDisocclusion, dDnHistoryClamp; uint dnW = 0, dnH = 0;
     // the sample index of the last build pass: Bridge::getSampleIndex's sampleBaseIndex for the NRD pass's camera rays
     uint spSampleBase = 0;
+    // the device denoiser (pt_denoise_plane; pt_relax.h). Per plane: the history of the previous and of the current frame, five records a pixel each (ptk::RelaxHistory), and the
+    // two denoised buffers; shared by the planes: the guide records and the a-trous ping-pong pairs. dnPreparedPlane: the plane the last pt_denoiser_prepare_nrd of this frame
+    // left in the NRD buffers (-1: none, or already denoised). rxSide: which of the two histories is the previous frame's. spFrameSerial counts the build passes; rxFrameSerial:
+    // the build pass a plane's history is of — a history older than the previous build pass (a plane that was not denoised in between) is not used.
+    DevBuf<ptk::float4> dRxHist[3][2][5], dRxOut[3][2], dRxGuide, dRxPing[2], dRxPong[2];
+    uint rxW = 0, rxH = 0, rxSide[3] = {0, 0, 0}; bool rxHistory[3] = {false, false, false}, rxDenoised[3] = {false, false, false}; int dnPreparedPlane = -1;
+    uint spFrameSerial = 0, rxFrameSerial[3] = {0, 0, 0};
+    // diagnostic only (pt_denoise_pass_times, for tools/denoise_probe.py): off unless asked for; when off pt_denoise_plane records no event
+    bool rxTiming = false; std::vector<float> rxPassMs; std::vector<hipEvent_t> rxEvents;
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -205,6 +215,22 @@ int neeat_exchange_feedback(pt_context* c);          // tile shards with a commu
 // One frame of LightsBaker::UpdateBegin (NEEAT_BEGIN) / UpdateEnd (NEEAT_END) for the NEE-AT layer; see the definition
 enum { NEEAT_BEGIN = 1, NEEAT_END = 2, NEEAT_BOTH = 3 };
 int neeat_frame(pt_context* c, int phases = NEEAT_BOTH, const float* depth = nullptr, const ptk::uint2* motion = nullptr);
+// the planes of the whole frame must be here: an unsharded context, or a sharded one after pt_gather_stable_planes / pt_unpack_stable_planes (the NRD pass reads neighbours)
+inline int32_t dn_ready(pt_context* c) {
+    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes, pt_fill_stable_planes");
+    if (c->shardCount > 1 && !c->spGathered) return fail(c, PT_ERROR_NOT_READY, "the denoiser passes read the whole frame's planes: pt_gather_stable_planes / pt_unpack_stable_planes first");
+    return PT_OK;
+}
+inline ptk::DenoiserBuffers dn_buffers(pt_context* c) {
+    ptk::DenoiserBuffers D;
+    D.RRDiffuseAlbedo = c->dDnRRDiff.p; D.RRSpecAlbedo = c->dDnRRSpec.p; D.RRNormalsAndRoughness = c->dDnRRNormal.p; D.RRSpecMotionVectors = c->dDnRRSpecMV.p;
+    D.ViewZ = c->dDnViewZ.p; D.MotionVectors = c->dDnMotion.p; D.NormalRoughness = c->dDnNormal.p; D.DiffRadianceHitDist = c->dDnDiff.p; D.SpecRadianceHitDist = c->dDnSpec.p;
+    D.Roughness = c->dDnRoughness.p; D.DisocclusionThresholdMix = c->dDnDisocclusion.p; D.CombinedHistoryClampRelax = c->dDnHistoryClamp.p;
+    return D;
+}
+// ---- pt_relax_api.hip: the device denoiser's history is dropped (resize to another size, new scene) / its buffers freed
+void relax_drop_history(pt_context* c);
+void relax_free(pt_context* c);
 // ---- pt_frame.hip
 // the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
 // passes that only address the buffers need: pack / unpack, merge, read-back)

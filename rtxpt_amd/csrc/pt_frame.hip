@@ -640,7 +640,7 @@ int32_t pt_build_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStab
     r = ensure_pool(c, numOwned ? numOwned : 1u, 1u); if (r != PT_OK) return r;
     r = ensure_stable_planes(c, ptk::GenericTSComputePlaneStride(c->width, c->height)); if (r != PT_OK) return r;
     const StablePlanesContext sp = sp_context(c, params);
-    c->spGathered = false; c->spSampleBase = sampleIndex;
+    c->spGathered = false; c->spSampleBase = sampleIndex; c->dnPreparedPlane = -1; c->spFrameSerial++;      // a new frame: no plane of it is prepared for the denoiser yet
     if (!numOwned) return PT_OK;
     PathKernelContext k = kernel_context(c);
     // a batch of one, but on the context's main stream: what later calls synchronise with
