@@ -444,6 +444,42 @@ int32_t pt_denoise_frame(pt_context* ctx, const PtStablePlanesParams* sp, const 
  * no event and takes no extra synchronisation. enable != 0 makes the following calls record it. ms (NULL: skip) receives the milliseconds of the last timed call's
  * passes in order — temporal, history clamp, then the a-trous iterations — and *count their number. */
 int32_t pt_denoise_pass_times(pt_context* ctx, uint32_t enable, float* ms, uint32_t capacity, uint32_t* count);
+
+/* ---- The temporal anti-aliasing resolve after the realtime merge: the seam of Sample::PostProcessAA (Sample.cpp:2621-2639), which with RealtimeAA == 1 sends OutputColor through
+ * TemporalAntiAliasingPass::TemporalResolve into ProcessedOutputColor, the picture the tone mapper then reads (Sample.cpp:2194-2197). The pass is Donut's and is not in the
+ * reference tree: this is a filter of the library's own (not Donut's text and not compared with Donut's output; the formulas are stated in docs/WIDENING.md N6). The four
+ * fields with a citation take the reference's names and defaults; clampingFactor, maxRadiance and luminanceWeighted are our own. */
+typedef struct PtTaaParams {
+    float    newFrameWeight;          /* 0.1; (0, 1]   — "TAA New Frame Weight", SampleUI.cpp:1199 */
+    float    clampingFactor;          /* 1.0; >= 0     — box half-width in standard deviations */
+    float    maxRadiance;             /* 10000; > 0    — input components are clamped to [0, maxRadiance] */
+    uint32_t enableHistoryClamping;   /* 1             — SampleUI.cpp:1198 */
+    uint32_t useHistoryClampRelax;    /* 1             — SampleUI.cpp:161, 1200 */
+    uint32_t useCatmullRomFilter;     /* 1             — Sample.cpp:1311; 0: bilinear */
+    uint32_t luminanceWeighted;       /* 1             — ours; 0 makes the blend plain newFrameWeight */
+} PtTaaParams;
+int32_t pt_taa_default_params(PtTaaParams* out);
+/* Resolves the radiance buffer (what pt_denoiser_merge_nrd / pt_denoise_frame / pt_stable_planes_merge left) against the previous call's result, reprojected through the motion
+ * vectors of the last build pass (the longest of the pixel's 3 x 3), clamped to the current 3 x 3's mean +- clampingFactor x (1 + 3 relax) sigma and blended. relax is
+ * nrdCombinedHistoryClampRelax; it reads as 0 with useHistoryClampRelax 0, without denoiser buffers of this size, or when no pt_denoiser_prepare_nrd ran since the last build
+ * pass. The result goes to one of two context-owned RGBA32F buffers (the reference's TemporalFeedback1 / 2) that swap on every call; the radiance buffer is never written.
+ * The input is not un-jittered, there is no depth-based history rejection (the clamp is the only ghosting control) and no change of resolution.
+ * History is dropped — the next call behaves as with resetHistory: the sanitised input goes through — by pt_resize to another size, by pt_set_geometry, and by a build pass
+ * that was not resolved (pt_build_stable_planes / pt_realtime_frame twice without a pt_taa_resolve in between).
+ * Allowed where pt_denoiser_prepare_nrd is: PT_ERROR_NOT_READY before a build pass of this size, or on a sharded context before the frame's planes arrived;
+ * PT_ERROR_INVALID_ARGUMENT for parameters outside the ranges above (NaN and infinity included).
+ * gpuMs (NULL: not timed — no event is recorded and no extra synchronisation taken) receives the kernel's event-timed milliseconds. */
+int32_t pt_taa_resolve(pt_context* ctx, const PtTaaParams* params, uint32_t resetHistory, float* gpuMs);
+/* the resolved picture of the last pt_taa_resolve (ProcessedOutputColor): RGBA32F, alpha 1; PT_ERROR_NOT_READY without one of this frame size */
+int32_t pt_resolved_device_buffer(pt_context* ctx, void** devicePtr, size_t* pitch);
+int32_t pt_get_resolved(pt_context* ctx, float* rgba);                                        /* host copy, width x height x 4 floats */
+/* pt_tonemap's pass over the resolved picture instead of the radiance buffer (ToneMappingPass reads ProcessedOutputColor, Sample.cpp:2194-2197) */
+int32_t pt_tonemap_resolved(pt_context* ctx, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes);
+/* Host only: the sub-pixel camera offset of frame frameIndex, in pixels, in [-0.5, 0.5) — what pt_bridge_camera's `jitter` and the offset in PtStablePlanesParams'
+ * matWorldToClip take. `sequence` follows the UI combo "MSAA\0Halton\0R2\0White Noise" (SampleUI.cpp:1126): 1 = Halton, bases (2, 3), of frameIndex + 1, minus 0.5;
+ * 2 = R2, frac(0.5 + (frameIndex + 1) x (0.7548776662466927, 0.5698402909980532)) - 0.5; both evaluated in double and returned as float. These are the published
+ * definitions of the two sequences, not Donut's code. 0 and 3 (Donut's sample table and generator are not in the reference tree): PT_ERROR_INVALID_ARGUMENT. */
+int32_t pt_taa_jitter(uint32_t sequence, uint32_t frameIndex, float offset[2]);
 int32_t pt_neeat_reset(pt_context* ctx);                                                      /* LightsBaker::BakeSettings::ResetFeedback */
 int32_t pt_get_neeat_tables(pt_context* ctx, uint32_t tilesXY[2], uint32_t jitterXY[2], uint32_t* table, uint32_t tableCapacityWords);
 /* Tile-sharded frames (PtDeviceDesc.shardCount > 1; no reference analogue): a rank traces and feeds back for its own pixels, the baker's passes read whole neighbourhoods, so

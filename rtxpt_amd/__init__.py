@@ -39,6 +39,7 @@ EXPORTS = [
     "pt_stable_planes_plane_stride", "pt_build_stable_planes", "pt_fill_stable_planes", "pt_denoise_spec_hit_t", "pt_stable_planes_merge", "pt_get_stable_planes",
     "pt_denoiser_default_params", "pt_denoiser_prepare_dlss_rr", "pt_denoiser_prepare_nrd", "pt_denoiser_merge_nrd", "pt_get_denoiser_inputs", "pt_denoiser_device_buffers",
     "pt_denoise_default_settings", "pt_denoise_plane", "pt_denoised_device_buffers", "pt_get_denoised", "pt_denoise_frame", "pt_denoise_pass_times",
+    "pt_taa_default_params", "pt_taa_resolve", "pt_resolved_device_buffer", "pt_get_resolved", "pt_tonemap_resolved", "pt_taa_jitter",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -691,6 +692,33 @@ def denoise_default_settings(lib=None, **overrides):
     return out
 
 
+# PtTaaParams (include/mi355pt.h): the temporal anti-aliasing resolve's parameters (pt_taa_resolve)
+TAA_PARAMS_DTYPE = np.dtype([("newFrameWeight", "<f4"), ("clampingFactor", "<f4"), ("maxRadiance", "<f4"), ("enableHistoryClamping", "<u4"), ("useHistoryClampRelax", "<u4"),
+                             ("useCatmullRomFilter", "<u4"), ("luminanceWeighted", "<u4")])
+TAA_JITTER_HALTON, TAA_JITTER_R2 = 1, 2      # the UI combo "MSAA\0Halton\0R2\0White Noise" (SampleUI.cpp:1126); 0 and 3 are refused
+
+
+def taa_default_params(lib=None, **overrides):
+    """pt_taa_default_params: new frame weight 0.1, clamping on (factor 1, relaxed by nrdCombinedHistoryClampRelax), Catmull-Rom history, luminance-weighted blend; keywords override"""
+    L = lib or load_library()
+    out = np.zeros((), TAA_PARAMS_DTYPE)
+    f = L.pt_taa_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_taa_default_params")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
+def taa_jitter(sequence, frame_index, lib=None):
+    """pt_taa_jitter: the sub-pixel camera offset (x, y) of a frame, in pixels in [-0.5, 0.5): sequence 1 Halton (2, 3), 2 R2. Does not need a device."""
+    L = lib or load_library()
+    out = (ctypes.c_float * 2)()
+    f = L.pt_taa_jitter; f.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(int(sequence), int(frame_index), out)
+    if r != PT_OK: raise PtError(r, "pt_taa_jitter")
+    return np.float32(out[0]), np.float32(out[1])
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -970,6 +998,37 @@ class PathTracer:
         f = self.L.pt_denoise_frame; f.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32]; f.restype = ctypes.c_int32
         self._chk(f(self.h, _p(prm), _p(dn), _p(ds), 1 if reset_history else 0), "pt_denoise_frame")
         return self.radiance()
+
+    def taa_resolve(self, params=None, reset_history=False, timed=False):
+        """pt_taa_resolve: the radiance buffer resolved against the previous call's result (TAA_PARAMS_DTYPE; defaults if None). Returns get_resolved(), or with timed
+        (resolved, the kernel's event-timed milliseconds)"""
+        tp = np.ascontiguousarray(taa_default_params(self.L) if params is None else params); assert tp.dtype == TAA_PARAMS_DTYPE
+        ms = ctypes.c_float(0.0)
+        f = self.L.pt_taa_resolve; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(tp), 1 if reset_history else 0, ctypes.byref(ms) if timed else None), "pt_taa_resolve")
+        return (self.get_resolved(), float(ms.value)) if timed else self.get_resolved()
+
+    def get_resolved(self):
+        """pt_get_resolved: the resolved picture of the last taa_resolve, [h, w, 4] f32, alpha 1"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        f = self.L.pt_get_resolved; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out)), "pt_get_resolved")
+        return out
+
+    def resolved_device_buffer(self):
+        """pt_resolved_device_buffer: (device pointer, row pitch in bytes) of the resolved picture"""
+        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
+        f = self.L.pt_resolved_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_resolved_device_buffer")
+        return d.value, int(pitch.value)
+
+    def tonemap_resolved(self, params=None):
+        """pt_tonemap_resolved: tonemap() over the resolved picture instead of the radiance buffer -> (H, W, 4) uint8"""
+        t = default_tonemap() if params is None else params
+        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        f = self.L.pt_tonemap_resolved; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_resolved")
+        return out
 
     def denoise_pass_times(self, enable=True):
         """pt_denoise_pass_times: switches the event timing of denoise_plane's passes on / off and returns the last timed call's milliseconds [temporal, clamp, a-trous 0, 1, ...]"""

@@ -198,6 +198,11 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     uint spFrameSerial = 0, rxFrameSerial[3] = {0, 0, 0};
     // diagnostic only (pt_denoise_pass_times, for tools/denoise_probe.py): off unless asked for; when off pt_denoise_plane records no event
     bool rxTiming = false; std::vector<float> rxPassMs; std::vector<hipEvent_t> rxEvents;
+    // the temporal anti-aliasing resolve (pt_taa_resolve; pt_taa.h): the reference's two feedback buffers; taaSide: the one written last (the resolved picture), the other one
+    // is its history. taaFrameSerial: the build pass the resolved picture is of (rxFrameSerial's rule). dnNrdSerial: the build pass of the last pt_denoiser_prepare_nrd — the
+    // relax buffer is read only when it is the current one. taaEvents: created by the first call that asks for its time.
+    DevBuf<ptk::float4> dTaa[2]; uint taaW = 0, taaH = 0, taaSide = 0, taaFrameSerial = 0, dnNrdSerial = 0; bool taaHistory = false, taaResolved = false;
+    hipEvent_t taaEvents[2] = {nullptr, nullptr};
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -231,6 +236,9 @@ inline ptk::DenoiserBuffers dn_buffers(pt_context* c) {
 // ---- pt_relax_api.hip: the device denoiser's history is dropped (resize to another size, new scene) / its buffers freed
 void relax_drop_history(pt_context* c);
 void relax_free(pt_context* c);
+// ---- pt_taa_api.hip: the same two hooks for the temporal anti-aliasing resolve
+void taa_drop_history(pt_context* c);
+void taa_free(pt_context* c);
 // ---- pt_frame.hip
 // the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
 // passes that only address the buffers need: pack / unpack, merge, read-back)
