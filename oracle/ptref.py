@@ -167,6 +167,7 @@ def refpin_pt(variant=(2, 1, 1, 1, 1, 1), lp16=False, mode=0):
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(os.path.dirname(_PIN), "librefpin_pt_%d%d%d%d%d%d%s%s.so" % (tuple(variant) + ("_lp16" if lp16 else "", "_m%d" % mode if mode else "")))
     srcs = [os.path.join(here, "refpin", f) for f in ("hlsl_tu.py", "hlsl_shim.h", "hlsl_pt_stubs.h", "hlsl_pt_bridge_stubs.h", "hlsl_pt_wrappers.inc", "hlsl_postprocess_stubs.h", "hlsl_lbfb_stubs.h", "hlsl_envbake_stubs.h", "hlsl_emisb_stubs.h")] + [os.path.join(here, "ptref", f) for f in os.listdir(os.path.join(here, "ptref"))]
+    srcs += [os.path.join(here, "..", "rtxpt_amd", "csrc", "pt_%s.h" % n) for n in "vec dmath rng sampling bsdf lights neeat envcube sky tonemap stableplanes".split()]      # the leaf headers: the product's, one text
     stale = not os.path.exists(path) or any(os.path.getmtime(f) > os.path.getmtime(path) for f in srcs)
     if stale:
         if not os.path.isdir("/root/reference/Rtxpt/Shaders"):
@@ -243,7 +244,7 @@ _PIN_MAT = os.path.join(os.path.dirname(_PIN), "librefpin_mat.so")
 
 def frustum_planes(view_proj, reference=False):
     """LightsBaker::UpdateFrustumConsts' five normalised clip planes of a row-vector view-projection matrix (float32 [5, 4]); reference=True: the reference's C++ text
-    (librefpin_mat.so), otherwise the oracle's restatement (neeat.h light_frustum_planes_from_viewproj). None when the reference library is unavailable."""
+    (librefpin_mat.so), otherwise the oracle's restatement (pt_neeat.h light_frustum_planes_from_viewproj). None when the reference library is unavailable."""
     m = np.ascontiguousarray(view_proj, np.float32).reshape(16); out = np.zeros((5, 4), np.float32)
     if reference:
         if not os.path.exists(_PIN_MAT):

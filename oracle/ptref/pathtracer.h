@@ -15,12 +15,13 @@
 // no temporal feedback), full MIS (RTXPT_USE_APPROXIMATE_MIS=0), no ReSTIR, no stable planes, no STF.
 // lp types: both builds of the reference are restated. PT_LP16 = 0 is RTXPT_LP_TYPES_USE_16BIT_PRECISION 0; PT_LP16 = 1 (libptref_lp16.so) is the
 // reference's default (SampleUI.h:182, Sample.cpp:1035): every value the reference declares lpfloat / lpfloat3 is rounded to binary16 where it is
-// converted, and the operations the reference performs between lp values are half operations (LPOps, vec.h) — MaterialProperties
+// converted, and the operations the reference performs between lp values are half operations (LPOps, pt_vec.h) — MaterialProperties
 // (BridgeDonut:311-380), the BSDF inputs of Bridge::loadSurface (:732-790), ShadingData::IoR / emission / shadowNoLFadeout, SurfaceData::interiorIoR,
 // updateOutsideIoR / loadIoR (:855-869), the emission terms and FireflyFilter (PathTracer.hlsli:438-480, 593-660, PathTracerHelpers.hlsli:206-213).
 #pragma once
-#include "bsdf.h"
-#include "rng.h"
+#include "leaf.h"
+#include "../../rtxpt_amd/csrc/pt_bsdf.h"
+#include "../../rtxpt_amd/csrc/pt_rng.h"
 #include "scene.h"
 
 namespace ptref {

@@ -8,9 +8,10 @@
 //   Rtxpt/Lighting/LightsBaker.hlsl:738-751,880-948      ComputeWeight (flux^0.8) and ComputeProxyCounts
 //   Rtxpt/Lighting/Distant/EnvMapImportanceSamplingBaker.hlsl:57-90   importance/radiance map (1024^2, 16 taps per texel)
 //   Rtxpt/ProcessingPasses/AccumulationPass.hlsl:36-66 + Rtxpt/Sample.cpp:2770-2778   accumulation lerp, weight 1/(n+1)
+#include "leaf.h"
 #include "pathtracer.h"
-#include "tonemap.h"
-#include "neeat.h"
+#include "../../rtxpt_amd/csrc/pt_tonemap.h"
+#include "../../rtxpt_amd/csrc/pt_neeat.h"
 #include "stableplanes_oracle.h"
 #include "../refpin/pin_fns.h"
 #include <cstdio>
@@ -407,7 +408,7 @@ struct NeeAtState {
     uint W = 0, H = 0; std::vector<float> fbW, scW, blW, histWeights, curWeights, depth, histDepth; std::vector<uint> fbC, scC, blC, local, counters;      // depth: the last traced frame's export; histDepth: the one before
     void reset() { updateCounter = 0; jitterF[0] = jitterF[1] = 0; jitter[0] = jitter[1] = prevJitter[0] = prevJitter[1] = 0; feedbackFilled = lastFeedbackAvailable = false; frameOpen = false; historicTotalLightCount = 0; W = H = 0; histWeights.clear(); }
 };
-// the passes as the oracle restates them (neeat.h), one call per pixel / low-resolution pixel / tile in the order a dispatch would enumerate them (the order does not matter:
+// the passes as the oracle restates them (pt_neeat.h), one call per pixel / low-resolution pixel / tile in the order a dispatch would enumerate them (the order does not matter:
 // every pass reads what the previous one wrote and writes only its own slot). The reference-text harness (refpin/hlsl_pt_wrappers.inc) supplies the same interface.
 struct OracleNeeAtPasses {
     void prefilter(const NeeAtFrame& F) {
@@ -568,7 +569,7 @@ uint32_t ptref_get_env_cube(void* h, uint32_t* out, uint32_t capacity, uint32_t*
     if (out && capacity >= e.cubeTexels.size()) memcpy(out, e.cubeTexels.data(), e.cubeTexels.size() * sizeof(uint2));
     return (uint32_t)e.cubeTexels.size();
 }
-// the cube compressor: BC6UCompress.hlsl's EncodeP1 restated (envcube.h) on n blocks of 16 RGB texels -> 4 words each; and the mode-11 decode -> 16 x 3 half bit patterns
+// the cube compressor: BC6UCompress.hlsl's EncodeP1 restated (pt_envcube.h) on n blocks of 16 RGB texels -> 4 words each; and the mode-11 decode -> 16 x 3 half bit patterns
 void ptref_bc6_encode(const float* texels, uint32_t n, uint32_t* out) {
     for (uint32_t k = 0; k < n; k++) { float3 t[16]; for (int i = 0; i < 16; i++) t[i] = make_float3(texels[48 * k + 3 * i], texels[48 * k + 3 * i + 1], texels[48 * k + 3 * i + 2]); bc6_encode_p1(t, out + 4 * k); }
 }
@@ -933,7 +934,7 @@ void ptref_camera_ray(void* h, uint32_t px, uint32_t py, uint32_t sampleIndex, f
     out6[0] = o.x; out6[1] = o.y; out6[2] = o.z; out6[3] = d.x; out6[4] = d.y; out6[5] = d.z;
 }
 
-// display path: n RGBA32F pixels -> n packed sRGB RGBA8 (tonemap.h)
+// display path: n RGBA32F pixels -> n packed sRGB RGBA8 (pt_tonemap.h)
 void ptref_tonemap(const float* rgba, uint32_t n, const ToneMapParams* p, uint32_t* out) {
     for (uint32_t i = 0; i < n; i++) out[i] = tm_pixel(*p, make_float4(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]));
 }
@@ -1028,7 +1029,7 @@ void ptref_light_probe(int kind, const uint32_t* in, unsigned n, uint32_t* out) 
     }
 }
 
-// display path before the SRGBA8 store: tm_apply (tonemap.h) as floats, the oracle's side of refhlsl_tonemap
+// display path before the SRGBA8 store: tm_apply (pt_tonemap.h) as floats, the oracle's side of refhlsl_tonemap
 void ptref_tonemap_linear(const float* rgba, uint32_t n, const ToneMapParams* p, float* out) {
     for (uint32_t i = 0; i < n; i++) { float3 c = tm_apply(*p, make_float3(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2])); out[4 * i] = c.x; out[4 * i + 1] = c.y; out[4 * i + 2] = c.z; out[4 * i + 3] = rgba[4 * i + 3]; }
 }

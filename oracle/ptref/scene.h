@@ -1,4 +1,5 @@
-// ORACLE (test infrastructure only) — scene data contract, textures, environment map, BVH + intersection.
+// ORACLE (test infrastructure only) — scene data contract, textures, environment map, BVH + intersection: the oracle's own (the lights, the baker's passes, the
+// cube and the sky it calls are the product's leaf headers, one text included by both: leaf.h).
 //
 // Data contract (mirrors the buffers the reference binds at Rtxpt/Sample.cpp:2319-2384):
 //   * PTMaterialData 128 B        Rtxpt/Shaders/PathTracer/Materials/MaterialPT.h:45-77 (flags :24-42)
@@ -13,10 +14,11 @@
 #pragma once
 #include <functional>
 #include <cstdio>
-#include "lights.h"
-#include "neeat.h"
-#include "envcube.h"
-#include "sky.h"
+#include "leaf.h"
+#include "../../rtxpt_amd/csrc/pt_lights.h"
+#include "../../rtxpt_amd/csrc/pt_neeat.h"
+#include "../../rtxpt_amd/csrc/pt_envcube.h"
+#include "../../rtxpt_amd/csrc/pt_sky.h"
 #include <vector>
 #include <algorithm>
 
@@ -140,7 +142,7 @@ static inline float4 sample_grad_anisotropic(const Texture& t, float2 uv, float2
     return make_float4(sum.x / n, sum.y / n, sum.z / n, sum.w / n);
 }
 
-// ---- environment: the host hands over a lat-long RGB image (row 0 = +Y pole); the path tracer samples the CUBE EnvMapBaker makes of it (envcube.h);
+// ---- environment: the host hands over a lat-long RGB image (row 0 = +Y pole); the path tracer samples the CUBE EnvMapBaker makes of it (pt_envcube.h);
 // EnvMap.hlsli:54-93 semantics for transform / multiplier
 struct EnvMap {
     bool enabled; Texture tex; float3x4 toWorld, toLocal; float3 colorMultiplier;
@@ -148,7 +150,7 @@ struct EnvMap {
     // BC6H round trip (EnvMapBaker.cpp:593-633): `cube` is what the path tracer samples — the decoded compressed cube when cubeCompression != 0 — while the importance map keeps
     // reading the uncompressed texels (`cubeSource`, :635)
     uint cubeCompression = 0; std::vector<uint2> cubeTexelsSource; EnvCube cubeSource;
-    // the procedural sky as (additional) source of the bake (EnvMapBaker.hlsl:228-236, 247-265; sky.h): constants, the four look-up textures, the half-resolution cloud pre-pass cube
+    // the procedural sky as (additional) source of the bake (EnvMapBaker.hlsl:228-236, 247-265; pt_sky.h): constants, the four look-up textures, the half-resolution cloud pre-pass cube
     bool skyEnabled = false; ProceduralSkyContext sky; std::vector<float4> skyTex[4]; std::vector<uint2> skyLowResTexels; EnvCube skyLowRes;
     // the image as a CUBE map instead of a lat-long image (ptref_set_environment_cube; EnvMapBaker.cpp:399-411, EnvMapBaker.hlsl BackgroundSourceType 2): 6 x dim x dim RGBA16F texels
     std::vector<uint2> imageCube; uint imageCubeDim = 0;

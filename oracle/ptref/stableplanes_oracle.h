@@ -1,4 +1,4 @@
-// ORACLE (test infrastructure only) — the oracle's view of stableplanes.h: what the stable-plane passes take from ptref::PathTracer, and the per-pixel loops of the
+// ORACLE (test infrastructure only) — the oracle's view of pt_stableplanes.h (one text, included by the product and here): what the stable-plane passes take from ptref::PathTracer, and the per-pixel loops of the
 // two passes as the reference's raygen shader runs them (PathTracerSample.hlsl:200-250 with PATH_TRACER_MODE_BUILD_STABLE_PLANES / _FILL_STABLE_PLANES).
 #pragma once
 #include "pathtracer.h"
@@ -26,7 +26,7 @@ static inline float SP_ray_cone_expansion(const PathTracer&, float pdf) { return
 static inline bool SP_isfinite(float v) { return (asuint(v) & 0x7F800000u) != 0x7F800000u; }
 
 #define SP_BRANCH_FIELD stableBranchID
-#include "stableplanes.h"
+#include "../../rtxpt_amd/csrc/pt_stableplanes.h"
 
 // the BUILD pass of one pixel: delta paths only, one plane after the other (PathTracerSample.hlsl:216-230, nextHit :114-169, postProcessHit :96-112)
 static inline void sp_build_pixel(const StablePlanesBuilder<PathTracer>& b, uint px, uint py) {

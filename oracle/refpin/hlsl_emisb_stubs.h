@@ -1,7 +1,7 @@
 // ORACLE pin (test infrastructure only): stand-ins for what Rtxpt/Lighting/Distant/EnvMapImportanceSamplingBaker.hlsl binds, so that its
 // BuildMIPDescentImportanceMapCS text compiles as C++ and runs over the oracle's baked environment cube. Included inside namespace hl::emisb by hlsl_tu.py
 // --integrator, after struct EnvMapImportanceSamplingBakerConstants.
-//   * t_EnvMapCube + s_LinearWrap: the cube fetch restated in oracle/ptref/envcube.h (hardware behaviour, no reference text)
+//   * t_EnvMapCube + s_LinearWrap: the cube fetch restated in rtxpt_amd/csrc/pt_envcube.h (one text, included by the product and the oracle; hardware behaviour, no reference text)
 //   * u_ImportanceMap: R32_FLOAT, u_RadianceMap: RGBA16_FLOAT (EnvMapImportanceSamplingBaker.cpp:159, 170) — the store to the latter rounds to binary16
 static EnvMapImportanceSamplingBakerConstants g_BuilderConsts;
 struct PinCube { const ptref::EnvCube* cube = nullptr;

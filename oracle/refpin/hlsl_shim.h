@@ -1,7 +1,7 @@
 // ORACLE pin (test infrastructure only): the HLSL vocabulary that lets g++ compile functions taken verbatim from the reference's .hlsli files
 // (oracle/refpin/hlsl_tu.py streams them from /root/reference into the compiler; nothing is copied into this repo).
 //
-// Everything whose result HLSL leaves to the implementation is mapped to the oracle's arithmetic contract (oracle/ptref/vec.h, dmath.h):
+// Everything whose result HLSL leaves to the implementation is mapped to the arithmetic contract the product and the oracle share (rtxpt_amd/csrc/pt_vec.h, pt_dmath.h: one text, included by both):
 // dot/normalize/length summation order, 1/sqrt for rsqrt, the dm_* transcendental functions, pow(x, 5) as repeated products, mad() unfused,
 // software fp16. What the pin therefore checks is the *restatement*: operation order, constants, branches and clamps of every pinned function.
 #pragma once
@@ -9,8 +9,8 @@
 #include <cmath>
 #include <cfloat>
 #include <type_traits>
-#include "../ptref/vec.h"
-#include "../ptref/dmath.h"
+#include "../ptref/leaf.h"
+#include "../../rtxpt_amd/csrc/pt_dmath.h"
 
 namespace hl {
 typedef uint32_t uint;

@@ -1,12 +1,12 @@
 // mi355pt device/host leaf library — deterministic elementary functions
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h so that the HIP kernels
-// reproduce the reference estimator bit-for-bit against the independent CPU oracle used by the tests.
+// One text, shared by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use: both include this file. Written to the arithmetic
+// contract stated in pt_vec.h, so that the HIP kernels and the host compiler evaluate every function here to the same bits.
 // Reference anchors are cited per function (paths relative to /root/reference/Rtxpt/Shaders/PathTracer/ unless noted).
 //
 // The reference (HLSL on a GPU) evaluates sin/cos/exp2/log2/pow/atan2 with implementation-defined, few-ulp
 // hardware approximations, so any <=2-3 ulp implementation is an equally valid restatement.
 // These versions use only +,-,*,/ and explicit fmaf() so that they produce bit-identical results on the host CPU
-// and on gfx950; the HIP product path carries its own copy (rtxpt_amd/csrc/pt_dmath.h) written to the same contract.
+// and on gfx950: the HIP kernels and the CPU oracle compile this one file.
 // Polynomial coefficients are the classic Cephes single-precision minimax sets.
 #pragma once
 #include "pt_vec.h"

@@ -1,4 +1,4 @@
-// mi355pt — the baked environment cube. Part of the PRODUCT path (libmi355pt.so); written to the arithmetic contract stated in pt_vec.h.
+// mi355pt — the baked environment cube. Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use; written to the arithmetic contract stated in pt_vec.h.
 #pragma once
 #include "pt_dmath.h"
 #include "pt_vec.h"

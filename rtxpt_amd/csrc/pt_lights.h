@@ -1,6 +1,6 @@
 // mi355pt device/host leaf library — polymorphic lights and the global light sampler
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h so that the HIP kernels
-// reproduce the reference estimator bit-for-bit against the independent CPU oracle used by the tests.
+// One text, shared by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use: both include this file. Written to the arithmetic
+// contract stated in pt_vec.h, so that the HIP kernels and the host compiler evaluate every function here to the same bits.
 // Reference anchors are cited per function (paths relative to /root/reference/Rtxpt/Shaders/PathTracer/ unless noted).
 // Follows:
 //   Lighting/PolymorphicLight.h:18-79                         packed 32 B + 16 B light records, type codes

@@ -1,6 +1,8 @@
 // mi355pt device/host leaf library — NEE-AT, the light baker's feedback passes: last frame's per-pixel feedback reservoirs -> this frame's screen-tile local samplers
 // and the usage counts that re-weight the global sampler.
-// Part of the PRODUCT path (libmi355pt.so): pt_wavefront.hip runs these functions as kernels (k_neeat_*), one thread per pixel / low-res pixel / tile.
+// Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use; written to the arithmetic contract stated in pt_vec.h.
+// pt_wavefront.hip runs these functions as kernels (k_neeat_*), one thread per pixel / low-res pixel / tile; the CPU oracle runs them in loops, and
+// tests/test_neeat_baker.py pins them to the reference's own passes, run thread by thread.
 // Reference anchors (paths relative to /root/reference/Rtxpt/): Lighting/LightsBaker.hlsl:1062-1855 (the ProcessFeedbackHistory passes, FillTile, ClearFeedbackHistory),
 // :753-762 (ResetLightProxyCounters), :880-948 (ComputeProxyCounts' feedback term), :118-162 (ImportanceBooster's intensity-delta term), Lighting/LightsBaker.cpp:943-962,
 // 985-1075, 1186-1213, 1335-1420 (per-frame constants and the order of the passes), Shaders/Libraries/MicroRng.hlsli, Shaders/PathTracer/Lighting/LightingTypes.hlsli:184-320.

@@ -1,6 +1,6 @@
 // mi355pt device/host leaf library — stateless sample generators
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h so that the HIP kernels
-// reproduce the reference estimator bit-for-bit against the independent CPU oracle used by the tests.
+// One text, shared by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use: both include this file. Written to the arithmetic
+// contract stated in pt_vec.h, so that the HIP kernels and the host compiler evaluate every function here to the same bits.
 // Reference anchors are cited per function (paths relative to /root/reference/Rtxpt/Shaders/PathTracer/ unless noted).
 // Restates, function by function:
 //   Rtxpt/Shaders/PathTracer/Utils/NoiseAndSequences.hlsli:58-86 (Hash32, Hash32Combine, Hash32ToFloat),
@@ -9,6 +9,7 @@
 //   :62-171 (SampleSequenceGenerator), :179-232 (UniformSampleSequenceGenerator),
 //   Rtxpt/Shaders/PathTracer/Utils/SampleGenerators.hlsli:16-52 (effect seeds, sampleNext1D).
 // All of it is exact 32-bit integer arithmetic and must match the reference bit-for-bit; it is pinned against the
+// reference's own C++ twin (SobolC / Hash32, compiled from the reference's header by the tests' reference pin).
 #pragma once
 #include "pt_vec.h"
 

@@ -1,6 +1,6 @@
 // mi355pt device/host leaf library — sampling and mapping helpers
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h so that the HIP kernels
-// reproduce the reference estimator bit-for-bit against the independent CPU oracle used by the tests.
+// One text, shared by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use: both include this file. Written to the arithmetic
+// contract stated in pt_vec.h, so that the HIP kernels and the host compiler evaluate every function here to the same bits.
 // Reference anchors are cited per function (paths relative to /root/reference/Rtxpt/Shaders/PathTracer/ unless noted).
 // Restates Rtxpt/Shaders/PathTracer/Utils/Math/MathHelpers.hlsli:185-229 (equal-area octahedral maps),
 // :238-246 (sample_disk), :288-316 (concentric disk / cosine hemisphere), :436-448 (perp_stark),

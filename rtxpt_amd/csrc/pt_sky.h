@@ -1,5 +1,6 @@
-// mi355pt — the procedural sky the environment cube can be baked from instead of an image (SURVEY.md 8f N2 leftovers). Part of the PRODUCT path
-// (libmi355pt.so); written to the arithmetic contract stated in pt_vec.h. Restates, function by function and in the reference's operation order:
+// mi355pt — the procedural sky the environment cube can be baked from instead of an image (SURVEY.md 8f N2 leftovers).
+// Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use; written to the arithmetic contract stated in pt_vec.h, pinned to the
+// reference's own text by tests/test_procedural_sky.py. Restates, function by function and in the reference's operation order:
 //   Rtxpt/Lighting/Distant/precomputed_sky.hlsli   (Bruneton & Neyret's precomputed atmospheric scattering as Q2RTX ships it): ClampRadius, RayIntersectsGround,
 //       DistanceToTopAtmosphereBoundary, GetTransmittanceUV, GetTransmittanceToTopAtmosphereBoundary, GetTransmittance, GetScatteringUVWZ, GetMieFromfloat4,
 //       Sample4D, RayleighPhaseFunction, MiePhaseFunction, GetParameters, GetSkyRadiance, CorrectViewRay, GetSkyRadianceToPoint, GetIrradiance(UV), GetSkyIrradiance

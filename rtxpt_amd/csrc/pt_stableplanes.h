@@ -1,5 +1,6 @@
 // mi355pt — stable planes (second half): the realtime mode's delta-path decomposition and the guide buffers a denoiser reads.
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h.
+// Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use; written to the arithmetic contract stated in pt_vec.h,
+// pinned to the reference's text by tests/test_stable_planes.py.
 // Reference anchors (paths relative to /root/reference/Rtxpt/Shaders/):
 //   PathTracer/StablePlanes.hlsli:28-371                 StablePlane (80 B), StablePlanesContext (header / plane buffer / stable radiance), branch ids
 //   PathTracer/PathTracerStablePlanes.hlsli:24-414       SplitDeltaPath, StablePlanesHandleHit (build), StablePlanesOnScatter (fill), StablePlanesHandleMiss
@@ -10,7 +11,7 @@
 //   PathTracer/Utils/Utils.hlsli:85-90,154-187,272-356   ReinhardMax, NDirToOctUnorm30, PackOrthoMatrix, Morton16BitEncode, GenericTSPixelToAddress
 //   PathTracer/PathTracerHelpers.hlsli:227-268           MatrixRotateFromTo
 //   PathTracerBridgeDonut.hlsli:890-909,1098-1177        computeMotionVector, ExportSurfaceInit / ExportSurface / ExportNonSurface / ExportSpecHitT*
-// This header is written once for both sides of the parity fence: SP_BRANCH_FIELD names the PathState word that carries stableBranchID
+// It has no namespace of its own: each side includes it inside its own, after its adapter functions (SP_camera_ray, SP_env_eval, ...). SP_BRANCH_FIELD names the PathState word that carries stableBranchID
 // (the wavefront pool keeps the sample index there in reference mode, pt_path.h:86).
 #pragma once
 #ifndef SP_BRANCH_FIELD

@@ -2,7 +2,8 @@
 //   tone mapping  Rtxpt/ToneMapper/ToneMapping.ps.hlsli:31-176, constants Rtxpt/ToneMapper/ToneMapping_cb.h:17-45,
 //   colour transform / manual exposure  Rtxpt/ToneMapper/ToneMappingPasses.cpp:428-441 (defaults ToneMappingPasses.h:36-53),
 //   LDR target = SRGBA8_UNORM (Rtxpt/SampleCommon/RenderTargets.cpp:241): linear -> sRGB on write, round to nearest 8-bit.
-// Arithmetic contract: single fp32 operations in the written order, dm_pow for pow().
+// Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use (the auto-exposure helpers at the end are the product's alone).
+// Arithmetic contract (pt_vec.h): single fp32 operations in the written order, dm_pow for pow().
 #pragma once
 #include "pt_vec.h"
 #include "pt_dmath.h"

@@ -1,9 +1,9 @@
 // mi355pt device/host leaf library — HLSL-like vector types, fp16 packing
-// Part of the PRODUCT path (libmi355pt.so). Written to the arithmetic contract stated in pt_vec.h so that the HIP kernels
-// reproduce the reference estimator bit-for-bit against the independent CPU oracle used by the tests.
+// One text, shared by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use: both include this file. Written to the arithmetic
+// contract stated below, so that the HIP kernels and the host compiler evaluate every function here to the same bits.
 // Reference anchors are cited per function (paths relative to /root/reference/Rtxpt/Shaders/PathTracer/ unless noted).
 //
-// Arithmetic contract (shared with the HIP product path so that parity can be bit-exact):
+// Arithmetic contract (what makes the device and the host agree bit for bit):
 //   * every operation is a single IEEE-754 binary32 operation evaluated in the order written;
 //     compile with -ffp-contract=off; fused multiply-adds appear only as explicit fmaf().
 //   * dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z ; normalize(v) = v * (1/sqrt(dot(v,v))).
@@ -13,6 +13,11 @@
 #include <cstdint>
 #include <cstring>
 #include <cmath>
+
+// a plain C++17 compiler (the CPU oracle's) reads these headers too: to it every function here is an ordinary host function
+#if !defined(__HIP__) && !defined(__device__)
+#define __device__
+#endif
 
 namespace ptk {
 #pragma clang force_cuda_host_device begin
@@ -137,7 +142,7 @@ static inline float det3(const float3x4& M) {
 // ---- fp16 (binary16) <-> fp32, round-to-nearest-even, denormals preserved
 // On the device these are the conversion instructions (v_cvt_f16_f32 / v_cvt_f32_f16: IEEE round-to-nearest-even, overflow to infinity, binary16
 // denormals kept — the kernels run with the default float mode, which never flushes 16-bit denormals): the same function as the software routine
-// below, which is what the host side and the oracle execute (tests/test_gpu_parity.py::test_leaf_functions_bit_exact compares the two on 40 000 values
+// below, which is what the host side and the CPU oracle execute (tests/test_gpu_parity.py::test_leaf_functions_bit_exact compares the two on 40 000 values
 // including the denormal range, the overflow boundary 65519.9 / 65520 and the tie 2^-25). One instruction instead of ~20, and far fewer registers.
 #if defined(__HIP_DEVICE_COMPILE__)
 static inline uint f32tof16(float f) { _Float16 h = (_Float16)f; unsigned short b; __builtin_memcpy(&b, &h, 2); return (uint)b; }

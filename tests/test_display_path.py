@@ -1,6 +1,6 @@
 """Display path: tone mapping + sRGB8 store + screenshot writers.
 
-CPU: the oracle (oracle/ptref/tonemap.h, restating Rtxpt/ToneMapper/ToneMapping.ps.hlsli:31-174) against an independent float64 numpy model
+CPU: the oracle (rtxpt_amd/csrc/pt_tonemap.h — one text, included by the product and the oracle — restating Rtxpt/ToneMapper/ToneMapping.ps.hlsli:31-174) against an independent float64 numpy model
 of the same formulas (tolerance 1 LSB of the 8-bit output); the product's host-only PNG/BMP writers round-trip.
 GPU: k_tonemap through the C-ABI (pt_tonemap) == oracle, byte for byte, for every operator.
 """
@@ -18,7 +18,7 @@ OPS = ["linear", "reinhard", "reinhard_modified", "heji_hable_alu", "hable_uc2",
 
 
 def _model(rgba, t):
-    """float64 restatement of applyToneMapping + SRGBA8 store, written independently of tonemap.h."""
+    """float64 restatement of applyToneMapping + SRGBA8 store, written independently of pt_tonemap.h."""
     c = rgba[..., :3].astype(np.float64)
     if t["autoExposure"]:
         c = c * np.clip(0.042 / float(t["avgLuminance"]), float(t["autoExposureLumValueMin"]), float(t["autoExposureLumValueMax"]))

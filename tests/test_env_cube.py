@@ -1,12 +1,12 @@
-"""The environment cube: EnvMapBaker's lat-long -> RGBA16F cube bake, restated by the oracle (oracle/ptref/envcube.h,
-ptref_api.cpp bake_env_cube), against the reference's own EnvMapBaker.hlsl text.
+"""The environment cube: EnvMapBaker's lat-long -> RGBA16F cube bake, restated by the oracle (rtxpt_amd/csrc/pt_envcube.h — one text, included
+by the product and the oracle — and ptref_api.cpp bake_env_cube), against the reference's own EnvMapBaker.hlsl text.
 
   * test_oracle_cube_matches_reference_text_golden: committed cubes (tests/golden/env_cube_golden.npz) baked by BaseLayerCS / MIPReduceCS of the reference
     text — runs everywhere, bit for bit.
   * test_oracle_cube_matches_live_reference_text: the same comparison on further inputs where /root/reference exists.
   * properties: alpha, fp16 range clamp, a constant source stays constant through the mips, the energy of a baked disc, cube addressing at texel centres.
 The cube FETCH (TextureCube.SampleLevel: face selection, bilinear taps clamped to the face, trilinear between mips) is hardware behaviour the reference
-has no text for; it is restated once in envcube.h and shared by the oracle and the reference-text integrator (hlsl_pt_wrappers.inc env_fetch)."""
+has no text for; it is restated once in pt_envcube.h and shared by the oracle and the reference-text integrator (hlsl_pt_wrappers.inc env_fetch)."""
 import os, sys
 import numpy as np
 import pytest
@@ -181,7 +181,7 @@ def test_baked_disc_carries_the_lights_energy():
 
 
 def test_cube_fetch_at_texel_centres_and_integer_lods_returns_the_texel():
-    """TextureCube.SampleLevel restated (envcube.h): a direction through a texel centre at an integer lod reads exactly that texel; lod clamps to the chain."""
+    """TextureCube.SampleLevel restated (pt_envcube.h): a direction through a texel centre at an integer lod reads exactly that texel; lod clamps to the chain."""
     sc = CASES["sky_32_discs"]
     (cube, dim, levels), o = _cube(sc)
     h = _half(cube); cm4 = np.asarray(sc["env"][2], np.float32) * np.float32(4.0)

@@ -1,7 +1,7 @@
 """The HIP path's leaf functions against the REFERENCE TEXT directly (run with -m gpu): tests/golden/refpin_hlsl_golden.npz holds inputs and outputs of
 functions compiled verbatim from the reference's .hlsli files (oracle/refpin/hlsl_tu.py, made by tests/golden/make_refpin_hlsl_golden.py in the build
 container). The device evaluates the product's own implementation of each through pt_probe and must reproduce the reference's output bit for bit.
-No oracle code runs here: the product's headers and the oracle's are textual twins, so "GPU == oracle" alone cannot catch a typo they share — this can."""
+No oracle code runs here: the product and the oracle include one text for the leaf functions, so "GPU == oracle" alone cannot catch a typo they share — this can."""
 import os
 
 import numpy as np

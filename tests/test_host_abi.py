@@ -64,6 +64,31 @@ def test_product_does_not_reference_the_oracle():
                 assert "import oracle" not in txt and "from oracle" not in txt and "ptref" not in txt, f
 
 
+def test_oracle_takes_only_the_leaf_headers_from_the_product():
+    """The converse: the oracle and the product share one text for the leaf functions, and nothing else. Every #include under oracle/ that reaches into
+    rtxpt_amd/ names one of eleven headers, those include only each other, and no copy of them is left under oracle/ptref/: the integrator (pt_path.h), the scene and
+    BVH (pt_scene.h, pt_traverse*.h), the wavefront kernels and the context stay out of the checker, which keeps its own."""
+    leaf = {"pt_%s.h" % n for n in "vec dmath rng sampling bsdf lights neeat envcube sky tonemap stableplanes".split()}
+    inc = re.compile(r'#\s*include\s*"([^"]+)"')
+    reached = set()
+    for dirpath, dirs, files in os.walk(os.path.join(ROOT, "oracle")):
+        dirs[:] = [d for d in dirs if d not in ("_ref", "__pycache__")]
+        for f in files:
+            if f.endswith((".so", ".pyc")): continue
+            for path in inc.findall(open(os.path.join(dirpath, f), errors="replace").read()):
+                if "rtxpt_amd" in path or re.fullmatch(r"pt_\w+\.h", os.path.basename(path)):
+                    assert "rtxpt_amd/csrc/" in path and os.path.basename(path) in leaf, (f, path)
+                    reached.add(os.path.basename(path))
+    assert reached
+    todo = sorted(reached)
+    while todo:
+        for path in inc.findall(open(os.path.join(ROOT, "rtxpt_amd", "csrc", todo.pop())).read()):
+            assert path in leaf, path          # pt_path.h, pt_scene.h, pt_wavefront*.h, pt_traverse*.h, pt_context.h: never
+            if path not in reached: reached.add(path); todo.append(path)
+    assert reached == leaf
+    for n in leaf: assert not os.path.exists(os.path.join(ROOT, "oracle", "ptref", n[3:])), n
+
+
 def test_bridge_camera_matches_reference_golden(lib, golden):
     for c in golden["bridge_camera"]:
         cam = pt.bridge_camera(c["w"], c["h"], c["pos"], c["dir"], c["up"], c["fov"], c["near"], c["far"], c["focal"], c["aperture"], c["jitter"])

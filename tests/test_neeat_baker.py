@@ -2,7 +2,7 @@
 
 Between two frames the reference's LightsBaker turns the path tracer's per-pixel feedback into the next frame's samplers: PreFilter, P0 (usage counts), the proxy
 counts' feedback term, P1a / P1b (one candidate per pixel), P2 / P3 (tile tables), ClearFeedbackHistory (LightsBaker.hlsl:753-830, 880-948, 1062-1855; host side
-LightsBaker.cpp:943-1420). oracle/ptref/neeat.h restates the passes; here whole runs — baker, path tracer, baker, ... — are held against what the reference's own
+LightsBaker.cpp:943-1420). rtxpt_amd/csrc/pt_neeat.h restates the passes (one text, included by the product and the oracle); here whole runs — baker, path tracer, baker, ... — are held against what the reference's own
 text produces frame by frame (tests/golden/neeat_loop_golden.npz; live where /root/reference exists, the passes executed thread by thread with their group-shared
 memory and barriers: oracle/refpin/hlsl_lbfb_stubs.h)."""
 import os, sys

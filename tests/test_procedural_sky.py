@@ -1,7 +1,7 @@
 """The procedural sky (SURVEY.md 8f N2 leftovers; Rtxpt/Lighting/Distant/SampleProceduralSky.{h,cpp,hlsli}, precomputed_sky.hlsli, EnvMapBaker.hlsl:228-236, 247-265):
   * pt_procedural_sky_update against an independent numpy restatement of SampleProceduralSky::Update: presets, the free-running clock, the low-pass filtered presets,
     the "changed" flag, the solid angle in double precision;
-  * the oracle's restatement of the shader side (oracle/ptref/sky.h) against the reference's own text, live where /root/reference exists: whole cubes, bit for bit —
+  * the restatement of the shader side (rtxpt_amd/csrc/pt_sky.h: one text, included by the product and the oracle) against the reference's own text, live where /root/reference exists: whole cubes, bit for bit —
     sky alone, sky over an image with baked discs and the BC6H round trip, the sun inside the frame, the sun below the horizon (tests/test_env_cube.py holds the
     committed reference-text cubes of two cases for every machine);
   * properties: a pitch-black sky bakes to zero, switching the sky off restores the image-only cube, the texel functions are finite and non-negative."""
