@@ -480,6 +480,40 @@ int32_t pt_tonemap_resolved(pt_context* ctx, const PtToneMapParams* params, uint
  * 2 = R2, frac(0.5 + (frameIndex + 1) x (0.7548776662466927, 0.5698402909980532)) - 0.5; both evaluated in double and returned as float. These are the published
  * definitions of the two sequences, not Donut's code. 0 and 3 (Donut's sample table and generator are not in the reference tree): PT_ERROR_INVALID_ARGUMENT. */
 int32_t pt_taa_jitter(uint32_t sequence, uint32_t frameIndex, float offset[2]);
+
+/* ---- The bloom pass between the resolve and the tone mapper: the seam of Sample::PostProcessPreToneMapping (Sample.cpp:1827-1837), which runs BloomPass::Render in place on
+ * ProcessedOutputColor — in realtime and in reference mode alike (AccumulationPass writes ProcessedOutputColor too) — unless !(EnableBloom && BloomIntensity > 0 &&
+ * BloomRadius > 0); it is on by default. The pass is Donut's and is not in the reference tree: this is a filter of the library's own (not Donut's text and not compared with
+ * Donut's output; the formulas are stated in docs/WIDENING.md N7): the sanitised source is reduced 4 x 4 to quarter resolution, blurred there by one separable Gaussian of
+ * sigma = radius / 4 texels, and blended back bilinearly: out = s + (blur - s) x intensity, alpha 1. One Gaussian, no multi-level chain and no threshold; picture borders
+ * repeat. The three fields with a citation take the reference's names, defaults and slider ranges; maxRadiance is our own. */
+typedef struct PtBloomParams {
+    float    radius;        /* 8.0; [0, 64]  — "Bloom Width (Pixels)", SampleUI.h:306, SampleUI.cpp:1541 */
+    float    intensity;     /* 0.004; [0, 1] — "Bloom Intensity", SampleUI.h:307 */
+    float    maxRadiance;   /* 10000; > 0    — ours, as PtTaaParams.maxRadiance: source components are clamped to [0, maxRadiance], not finite ones count as 0 */
+    uint32_t enable;        /* 1             — EnableBloom, SampleUI.h:305 */
+} PtBloomParams;
+int32_t pt_bloom_default_params(PtBloomParams* out);
+/* Host only: the blur's taps for `radius` in (0, 64] (ours): sigma = 0.25 x radius and g[i] = exp(-i^2 / (2 sigma^2)) in double, rounded to float, for i = 0 .. R with
+ * R = max(1, ceil(3 sigma)); *taps receives R, in [1, 48], weights[0 .. R] the taps (g[0] = 1), *weightSum (NULL: skip) their float sum G = 1 + 2 g[1] + ... + 2 g[R] in that
+ * order — the blur divides by it. PT_ERROR_INVALID_ARGUMENT for a radius outside (0, 64] (NaN included) or capacity < R + 1. */
+int32_t pt_bloom_kernel(float radius, float* weights, uint32_t capacity, uint32_t* taps, float* weightSum);
+/* Blooms source 0 — the radiance buffer, what pt_tonemap reads (reference mode: pt_render -> pt_bloom) — or source 1 — the resolved picture of pt_taa_resolve (realtime
+ * mode) — into a third context-owned RGBA32F buffer, the bloomed picture. The source is never written: the resolved picture is the next pt_taa_resolve's history and stays
+ * byte-identical, as do the radiance buffer, the history flags and serials. With enable == 0, intensity == 0 or radius == 0 the pass is skipped as the reference skips it:
+ * the bloomed picture receives the source's bytes unchanged (alpha and NaNs included), and the calls below work on it.
+ * Source 0 is allowed where pt_tonemap is (PT_ERROR_NOT_READY before pt_resize; whether a sharded frame has been gathered is the caller's business, as for pt_tonemap); source 1
+ * needs a resolved picture of this frame size (PT_ERROR_NOT_READY). PT_ERROR_INVALID_ARGUMENT for a source above 1 or a parameter outside the ranges above (NaN and infinity
+ * included). pt_resize to another size drops the bloomed picture.
+ * gpuMs (NULL: not timed — no event is recorded and no extra synchronisation taken) receives the event-timed milliseconds from the pass's first kernel to its last. */
+int32_t pt_bloom(pt_context* ctx, const PtBloomParams* params, uint32_t source, float* gpuMs);
+/* the bloomed picture of the last pt_bloom: RGBA32F; the four calls return PT_ERROR_NOT_READY without one of this frame size */
+int32_t pt_bloomed_device_buffer(pt_context* ctx, void** devicePtr, size_t* pitch);
+int32_t pt_get_bloomed(pt_context* ctx, float* rgba);                                         /* host copy, width x height x 4 floats */
+/* pt_tonemap's pass over the bloomed picture (ToneMappingPass runs after PostProcessPreToneMapping) */
+int32_t pt_tonemap_bloomed(pt_context* ctx, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes);
+/* pt_average_luminance's pass over the bloomed picture: the picture the reference's auto exposure measures */
+int32_t pt_average_luminance_bloomed(pt_context* ctx, float* avgLuminance);
 int32_t pt_neeat_reset(pt_context* ctx);                                                      /* LightsBaker::BakeSettings::ResetFeedback */
 int32_t pt_get_neeat_tables(pt_context* ctx, uint32_t tilesXY[2], uint32_t jitterXY[2], uint32_t* table, uint32_t tableCapacityWords);
 /* Tile-sharded frames (PtDeviceDesc.shardCount > 1; no reference analogue): a rank traces and feeds back for its own pixels, the baker's passes read whole neighbourhoods, so

@@ -40,6 +40,7 @@ EXPORTS = [
     "pt_denoiser_default_params", "pt_denoiser_prepare_dlss_rr", "pt_denoiser_prepare_nrd", "pt_denoiser_merge_nrd", "pt_get_denoiser_inputs", "pt_denoiser_device_buffers",
     "pt_denoise_default_settings", "pt_denoise_plane", "pt_denoised_device_buffers", "pt_get_denoised", "pt_denoise_frame", "pt_denoise_pass_times",
     "pt_taa_default_params", "pt_taa_resolve", "pt_resolved_device_buffer", "pt_get_resolved", "pt_tonemap_resolved", "pt_taa_jitter",
+    "pt_bloom_default_params", "pt_bloom_kernel", "pt_bloom", "pt_bloomed_device_buffer", "pt_get_bloomed", "pt_tonemap_bloomed", "pt_average_luminance_bloomed",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -719,6 +720,33 @@ def taa_jitter(sequence, frame_index, lib=None):
     return np.float32(out[0]), np.float32(out[1])
 
 
+# PtBloomParams (include/mi355pt.h): the bloom pass's parameters (pt_bloom)
+BLOOM_PARAMS_DTYPE = np.dtype([("radius", "<f4"), ("intensity", "<f4"), ("maxRadiance", "<f4"), ("enable", "<u4")])
+BLOOM_SOURCE_RADIANCE, BLOOM_SOURCE_RESOLVED = 0, 1
+BLOOM_MAX_TAPS = 48
+
+
+def bloom_default_params(lib=None, **overrides):
+    """pt_bloom_default_params: on, width 8 pixels, intensity 0.004 (SampleUI.h:305-307), maxRadiance 10000; keywords override"""
+    L = lib or load_library()
+    out = np.zeros((), BLOOM_PARAMS_DTYPE)
+    f = L.pt_bloom_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_bloom_default_params")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
+def bloom_kernel(radius, lib=None, capacity=BLOOM_MAX_TAPS + 1):
+    """pt_bloom_kernel: (the blur's taps g[0 .. R] as float32, their float sum G) for a radius in (0, 64]. Does not need a device."""
+    L = lib or load_library()
+    g = np.zeros(max(int(capacity), 1), np.float32); n, G = ctypes.c_uint32(), ctypes.c_float()
+    f = L.pt_bloom_kernel; f.argtypes = [ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(float(radius), _p(g), int(capacity), ctypes.byref(n), ctypes.byref(G))
+    if r != PT_OK: raise PtError(r, "pt_bloom_kernel")
+    return g[:n.value + 1].copy(), np.float32(G.value)
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -1029,6 +1057,44 @@ class PathTracer:
         f = self.L.pt_tonemap_resolved; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
         self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_resolved")
         return out
+
+    def bloom(self, params=None, source=0, timed=False):
+        """pt_bloom: source 0 (the radiance buffer) or 1 (the resolved picture of taa_resolve) bloomed into a third buffer (BLOOM_PARAMS_DTYPE; defaults if None). Returns
+        bloomed(), or with timed (bloomed, the pass's event-timed milliseconds)"""
+        bp = np.ascontiguousarray(bloom_default_params(self.L) if params is None else params); assert bp.dtype == BLOOM_PARAMS_DTYPE
+        ms = ctypes.c_float(0.0)
+        f = self.L.pt_bloom; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(bp), int(source), ctypes.byref(ms) if timed else None), "pt_bloom")
+        return (self.bloomed(), float(ms.value)) if timed else self.bloomed()
+
+    def bloomed(self):
+        """pt_get_bloomed: the bloomed picture of the last bloom, [h, w, 4] f32"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        f = self.L.pt_get_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out)), "pt_get_bloomed")
+        return out
+
+    def bloomed_device_buffer(self):
+        """pt_bloomed_device_buffer: (device pointer, row pitch in bytes) of the bloomed picture"""
+        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
+        f = self.L.pt_bloomed_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_bloomed_device_buffer")
+        return d.value, int(pitch.value)
+
+    def tonemap_bloomed(self, params=None):
+        """pt_tonemap_bloomed: tonemap() over the bloomed picture instead of the radiance buffer -> (H, W, 4) uint8"""
+        t = default_tonemap() if params is None else params
+        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        f = self.L.pt_tonemap_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_bloomed")
+        return out
+
+    def average_luminance_bloomed(self):
+        """pt_average_luminance_bloomed: average_luminance() of the bloomed picture — the picture the reference's auto exposure measures"""
+        v = ctypes.c_float(0.0)
+        f = self.L.pt_average_luminance_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(v)), "pt_average_luminance_bloomed")
+        return float(v.value)
 
     def denoise_pass_times(self, enable=True):
         """pt_denoise_pass_times: switches the event timing of denoise_plane's passes on / off and returns the last timed call's milliseconds [temporal, clamp, a-trous 0, 1, ...]"""

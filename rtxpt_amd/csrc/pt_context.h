@@ -203,6 +203,10 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // relax buffer is read only when it is the current one. taaEvents: created by the first call that asks for its time.
     DevBuf<ptk::float4> dTaa[2]; uint taaW = 0, taaH = 0, taaSide = 0, taaFrameSerial = 0, dnNrdSerial = 0; bool taaHistory = false, taaResolved = false;
     hipEvent_t taaEvents[2] = {nullptr, nullptr};
+    // the bloom pass (pt_bloom; pt_bloom.h): the bloomed picture — a third buffer, the source (the radiance buffer or dTaa[taaSide]) is never written — and the two
+    // quarter-resolution images of the blur. bloomReady: a bloomed picture of bloomW x bloomH is there. bloomEvents: created by the first call that asks for its time.
+    DevBuf<ptk::float4> dBloom, dBloomQ[2]; uint bloomW = 0, bloomH = 0; bool bloomReady = false;
+    hipEvent_t bloomEvents[2] = {nullptr, nullptr};
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -239,6 +243,10 @@ void relax_free(pt_context* c);
 // ---- pt_taa_api.hip: the same two hooks for the temporal anti-aliasing resolve
 void taa_drop_history(pt_context* c);
 void taa_free(pt_context* c);
+int32_t taa_resolved_ready(pt_context* c);           // PT_OK with a resolved picture of the current frame size, else PT_ERROR_NOT_READY
+// ---- pt_bloom_api.hip: the bloomed picture is dropped (resize to another size) / the pass's buffers freed
+void bloom_drop(pt_context* c);
+void bloom_free(pt_context* c);
 // ---- pt_frame.hip
 // the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
 // passes that only address the buffers need: pack / unpack, merge, read-back)

@@ -10,6 +10,10 @@ using namespace ptk;
 static_assert(sizeof(::PtTaaParams) == sizeof(ptk::TaaParams), "TAA parameter ABI");
 
 void taa_drop_history(pt_context* c) { c->taaHistory = false; c->taaResolved = false; }
+int32_t taa_resolved_ready(pt_context* c) {
+    if (!c->taaResolved || c->taaW != c->width || c->taaH != c->height) return fail(c, PT_ERROR_NOT_READY, "no resolved picture of this frame size yet: pt_taa_resolve");
+    return PT_OK;
+}
 void taa_free(pt_context* c) {
     for (int s = 0; s < 2; s++) { c->dTaa[s].free(); if (c->taaEvents[s]) { (void)hipEventDestroy(c->taaEvents[s]); c->taaEvents[s] = nullptr; } }
     c->taaW = c->taaH = 0; taa_drop_history(c);
@@ -18,10 +22,6 @@ void taa_free(pt_context* c) {
 namespace {
 bool params_ok(const PtTaaParams& p) {      // (every comparison is false for a NaN)
     return p.newFrameWeight > 0.0f && p.newFrameWeight <= 1.0f && p.clampingFactor >= 0.0f && p.clampingFactor <= kDenoiserViewZSkyMarker && p.maxRadiance > 0.0f && p.maxRadiance <= kDenoiserViewZSkyMarker;
-}
-int32_t resolved_ready(pt_context* c) {
-    if (!c->taaResolved || c->taaW != c->width || c->taaH != c->height) return fail(c, PT_ERROR_NOT_READY, "no resolved picture of this frame size yet: pt_taa_resolve");
-    return PT_OK;
 }
 // Halton's radical inverse of i in base b: the digits of i mirrored at the point, as one quotient of integers
 double radical_inverse(unsigned long long i, uint32_t b) {
@@ -68,14 +68,14 @@ int32_t pt_taa_resolve(pt_context* c, const PtTaaParams* params, uint32_t resetH
 
 int32_t pt_resolved_device_buffer(pt_context* c, void** devicePtr, size_t* pitch) {
     if (!c || !devicePtr) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = resolved_ready(c); if (r != PT_OK) return r;
+    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
     *devicePtr = c->dTaa[c->taaSide].p; if (pitch) *pitch = (size_t)c->width * 16u;
     return PT_OK;
 }
 
 int32_t pt_get_resolved(pt_context* c, float* rgba) {
     if (!c || !rgba) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = resolved_ready(c); if (r != PT_OK) return r;
+    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
     (void)hipSetDevice(c->device);
     PT_CHECK_HIP(c, hipMemcpy(rgba, c->dTaa[c->taaSide].p, 16u * (size_t)c->width * c->height, hipMemcpyDeviceToHost));
     return PT_OK;
@@ -83,7 +83,7 @@ int32_t pt_get_resolved(pt_context* c, float* rgba) {
 
 int32_t pt_tonemap_resolved(pt_context* c, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes) {
     if (!c || !params || !rgba8) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = resolved_ready(c); if (r != PT_OK) return r;
+    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
     const size_t n = (size_t)c->width * c->height;
     if (bytes < n * 4) return fail(c, PT_ERROR_INVALID_ARGUMENT, "rgba8 buffer too small");
     if (params->toneMapOperator > 5u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "unknown tone map operator");
