@@ -514,6 +514,50 @@ int32_t pt_get_bloomed(pt_context* ctx, float* rgba);                           
 int32_t pt_tonemap_bloomed(pt_context* ctx, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes);
 /* pt_average_luminance's pass over the bloomed picture: the picture the reference's auto exposure measures */
 int32_t pt_average_luminance_bloomed(pt_context* ctx, float* avgLuminance);
+
+/* ---- The temporal upscaling resolve: tracing below display resolution. The reference's realtime mode takes m_renderSize from the upscaler's optimal render size
+ * (Sample.cpp:1684-1776), keeps m_displaySize for everything after PostProcessAA (:1830, :2190), jitters the camera (ComputeCameraJitter, :2816) and biases the texture LOD
+ * by the resolution ratio (:1504-1506). Its upscaler is DLSS, which is not ours to run: this is a filter of the library's own (not compared with anybody's output; the
+ * formulas are stated in docs/WIDENING.md N8) — pt_taa_resolve's filter behind a jitter-aware resampling of the current frame. The context's frame size w x h (pt_resize) is
+ * the render size; the display size W x H is an argument, w <= W <= 4 w and h <= H <= 4 h, each axis on its own, the ratio need not be an integer. */
+typedef struct PtTaaUpscaleParams {
+    PtTaaParams taa;             /* as pt_taa_resolve: same fields, defaults and ranges */
+    float    kernelRadius;       /* 1.0; [1, 2] — ours: support of the resampling kernel, in render pixels */
+    uint32_t confidenceWeighted; /* 1       — ours: the new-frame weight is scaled by the best tap's weight */
+} PtTaaUpscaleParams;
+int32_t pt_taa_upscale_default_params(PtTaaUpscaleParams* out);
+/* Resolves the radiance buffer and the last build pass's motion vectors, both at the frame size, into one of two context-owned display-size RGBA32F buffers that swap on
+ * every call (the upscaled picture and its history); alpha 1. Per display pixel: the nine render pixels around the sample nearest to its centre are weighted by
+ * max(1 - d^2 / kernelRadius^2, 0)^2 of their distance d to the centre (in render pixels, the frame's jitter taken into account) and normalised; the result is blended with
+ * the history exactly as pt_taa_resolve blends (longest motion vector of the nine, scaled to display pixels; Catmull-Rom or bilinear history; the nine taps' mean +- k sigma
+ * clamp, relaxed by nrdCombinedHistoryClampRelax at the nearest sample; luminance weighting), with newFrameWeight x the best tap's weight when confidenceWeighted. At
+ * W x H = w x h, jitter (0, 0) and kernelRadius 1 the result equals pt_taa_resolve's bit for bit.
+ * jitter: the frame's camera offset in render pixels, the very pair given to pt_bridge_camera (what pt_taa_jitter returns); NULL reads as (0, 0); each component finite and in
+ * [-0.5, 0.5].
+ * None of pt_taa_resolve's or pt_bloom's buffers, flags or serials is touched, nor the radiance buffer. The history follows pt_taa_resolve's rule with a serial of its own
+ * (this build pass or the one before) and is dropped — the next call behaves as with resetHistory — by another display size, by pt_resize to another size, by
+ * pt_set_geometry, and by a build pass that was not upscaled.
+ * Allowed where pt_taa_resolve is: PT_ERROR_NOT_READY before a build pass of this size, or on a sharded context before the frame's planes arrived;
+ * PT_ERROR_INVALID_ARGUMENT for parameters outside their ranges (NaN and infinity included), a display size outside [w, 4 w] x [h, 4 h] or a bad jitter. A refused call
+ * changes nothing. gpuMs (NULL: not timed — no event is recorded and no extra synchronisation taken) receives the kernel's event-timed milliseconds. */
+int32_t pt_taa_upscale(pt_context* ctx, const PtTaaUpscaleParams* params, uint32_t displayWidth, uint32_t displayHeight, const float jitter[2], uint32_t resetHistory, float* gpuMs);
+/* the upscaled picture of the last pt_taa_upscale: its size, its device pointer and row pitch in bytes, a host copy (floats: the capacity of rgba, >= W x H x 4).
+ * PT_ERROR_NOT_READY without an upscaled picture made from a frame of the current frame size. */
+int32_t pt_upscaled_size(pt_context* ctx, uint32_t* width, uint32_t* height);
+int32_t pt_upscaled_device_buffer(pt_context* ctx, void** devicePtr, size_t* pitch);
+int32_t pt_get_upscaled(pt_context* ctx, float* rgba, size_t floats);
+/* The display tail at the display size. pt_bloom_upscaled is pt_bloom's pass (same parameters, ranges and skip rule, which copies the bytes) over the upscaled picture into a
+ * display-size bloomed picture of its own; pt_bloom's picture is not touched. The next pt_taa_upscale gives the bloomed picture up. pt_tonemap_upscaled and
+ * pt_average_luminance_upscaled point pt_tonemap's and pt_average_luminance's kernels at picture `bloomed` = 0 (the upscaled picture) or 1 (its bloom: PT_ERROR_NOT_READY
+ * without one); any other value is PT_ERROR_INVALID_ARGUMENT, as are buffers that are too small. */
+int32_t pt_bloom_upscaled(pt_context* ctx, const PtBloomParams* params, float* gpuMs);
+int32_t pt_get_upscaled_bloomed(pt_context* ctx, float* rgba, size_t floats);
+int32_t pt_tonemap_upscaled(pt_context* ctx, const PtToneMapParams* params, uint32_t bloomed, uint8_t* rgba8, size_t bytes);
+int32_t pt_average_luminance_upscaled(pt_context* ctx, uint32_t bloomed, float* avgLuminance);
+/* Host only: the texture LOD bias of a frame traced at renderW x renderH for a displayW x displayH display, as Sample.cpp:1504 computes it —
+ * -log2f(sqrtf((displayW * displayH) / float(renderW * renderH))), the products in uint32_t as there; the host adds it to PtSettings.texLODBias (:1506).
+ * PT_ERROR_INVALID_ARGUMENT for a size of 0. */
+int32_t pt_upscale_tex_lod_bias(uint32_t renderW, uint32_t renderH, uint32_t displayW, uint32_t displayH, float* bias);
 int32_t pt_neeat_reset(pt_context* ctx);                                                      /* LightsBaker::BakeSettings::ResetFeedback */
 int32_t pt_get_neeat_tables(pt_context* ctx, uint32_t tilesXY[2], uint32_t jitterXY[2], uint32_t* table, uint32_t tableCapacityWords);
 /* Tile-sharded frames (PtDeviceDesc.shardCount > 1; no reference analogue): a rank traces and feeds back for its own pixels, the baker's passes read whole neighbourhoods, so

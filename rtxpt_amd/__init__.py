@@ -41,6 +41,8 @@ EXPORTS = [
     "pt_denoise_default_settings", "pt_denoise_plane", "pt_denoised_device_buffers", "pt_get_denoised", "pt_denoise_frame", "pt_denoise_pass_times",
     "pt_taa_default_params", "pt_taa_resolve", "pt_resolved_device_buffer", "pt_get_resolved", "pt_tonemap_resolved", "pt_taa_jitter",
     "pt_bloom_default_params", "pt_bloom_kernel", "pt_bloom", "pt_bloomed_device_buffer", "pt_get_bloomed", "pt_tonemap_bloomed", "pt_average_luminance_bloomed",
+    "pt_taa_upscale_default_params", "pt_taa_upscale", "pt_upscaled_size", "pt_upscaled_device_buffer", "pt_get_upscaled", "pt_bloom_upscaled", "pt_get_upscaled_bloomed",
+    "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -720,6 +722,31 @@ def taa_jitter(sequence, frame_index, lib=None):
     return np.float32(out[0]), np.float32(out[1])
 
 
+# PtTaaUpscaleParams (include/mi355pt.h): the temporal upscaling resolve's parameters (pt_taa_upscale) — PtTaaParams, then the two fields of the resampling
+TAA_UPSCALE_PARAMS_DTYPE = np.dtype(TAA_PARAMS_DTYPE.descr + [("kernelRadius", "<f4"), ("confidenceWeighted", "<u4")])
+
+
+def taa_upscale_default_params(lib=None, **overrides):
+    """pt_taa_upscale_default_params: taa_default_params()'s fields, kernelRadius 1, confidenceWeighted 1; keywords override"""
+    L = lib or load_library()
+    out = np.zeros((), TAA_UPSCALE_PARAMS_DTYPE)
+    f = L.pt_taa_upscale_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_taa_upscale_default_params")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
+def upscale_tex_lod_bias(render_w, render_h, display_w, display_h, lib=None):
+    """pt_upscale_tex_lod_bias: what a frame traced at the render size for a display of the display size adds to PtSettings.texLODBias (Sample.cpp:1504). Does not need a device."""
+    L = lib or load_library()
+    v = ctypes.c_float(0.0)
+    f = L.pt_upscale_tex_lod_bias; f.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(int(render_w), int(render_h), int(display_w), int(display_h), ctypes.byref(v))
+    if r != PT_OK: raise PtError(r, "pt_upscale_tex_lod_bias")
+    return np.float32(v.value)
+
+
 # PtBloomParams (include/mi355pt.h): the bloom pass's parameters (pt_bloom)
 BLOOM_PARAMS_DTYPE = np.dtype([("radius", "<f4"), ("intensity", "<f4"), ("maxRadiance", "<f4"), ("enable", "<u4")])
 BLOOM_SOURCE_RADIANCE, BLOOM_SOURCE_RESOLVED = 0, 1
@@ -1094,6 +1121,72 @@ class PathTracer:
         v = ctypes.c_float(0.0)
         f = self.L.pt_average_luminance_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
         self._chk(f(self.h, ctypes.byref(v)), "pt_average_luminance_bloomed")
+        return float(v.value)
+
+    def taa_upscale(self, params=None, display=None, jitter=(0.0, 0.0), reset_history=False, timed=False):
+        """pt_taa_upscale: the radiance buffer (the frame size is the render size) resolved into the display-size history (TAA_UPSCALE_PARAMS_DTYPE; defaults if None).
+        display: (W, H), within [w, 4 w] x [h, 4 h]; jitter: the frame's camera offset in render pixels (None: the library's NULL). Returns upscaled(), or with timed
+        (upscaled, the kernel's event-timed milliseconds)"""
+        up = np.ascontiguousarray(taa_upscale_default_params(self.L) if params is None else params); assert up.dtype == TAA_UPSCALE_PARAMS_DTYPE
+        W, H = (self.width, self.height) if display is None else display
+        j = None if jitter is None else (ctypes.c_float * 2)(float(jitter[0]), float(jitter[1]))
+        ms = ctypes.c_float(0.0)
+        f = self.L.pt_taa_upscale; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(up), int(W), int(H), j, 1 if reset_history else 0, ctypes.byref(ms) if timed else None), "pt_taa_upscale")
+        return (self.upscaled(), float(ms.value)) if timed else self.upscaled()
+
+    def upscaled_size(self):
+        """pt_upscaled_size: (W, H) of the upscaled picture"""
+        W, H = ctypes.c_uint32(), ctypes.c_uint32()
+        f = self.L.pt_upscaled_size; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(W), ctypes.byref(H)), "pt_upscaled_size")
+        return int(W.value), int(H.value)
+
+    def _upscaled_picture(self, name):
+        W, H = self.upscaled_size()
+        out = np.empty((H, W, 4), np.float32)
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out), out.size), name)
+        return out
+
+    def upscaled(self):
+        """pt_get_upscaled: the upscaled picture of the last taa_upscale, [H, W, 4] f32, alpha 1"""
+        return self._upscaled_picture("pt_get_upscaled")
+
+    def upscaled_device_buffer(self):
+        """pt_upscaled_device_buffer: (device pointer, row pitch in bytes) of the upscaled picture"""
+        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
+        f = self.L.pt_upscaled_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_upscaled_device_buffer")
+        return d.value, int(pitch.value)
+
+    def bloom_upscaled(self, params=None, timed=False):
+        """pt_bloom_upscaled: bloom()'s pass over the upscaled picture at the display size, into a bloomed picture of its own. Returns upscaled_bloomed(), or with timed
+        (upscaled_bloomed, the pass's event-timed milliseconds)"""
+        bp = np.ascontiguousarray(bloom_default_params(self.L) if params is None else params); assert bp.dtype == BLOOM_PARAMS_DTYPE
+        ms = ctypes.c_float(0.0)
+        f = self.L.pt_bloom_upscaled; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(bp), ctypes.byref(ms) if timed else None), "pt_bloom_upscaled")
+        return (self.upscaled_bloomed(), float(ms.value)) if timed else self.upscaled_bloomed()
+
+    def upscaled_bloomed(self):
+        """pt_get_upscaled_bloomed: the bloomed picture of the last bloom_upscaled, [H, W, 4] f32"""
+        return self._upscaled_picture("pt_get_upscaled_bloomed")
+
+    def tonemap_upscaled(self, params=None, bloomed=False):
+        """pt_tonemap_upscaled: tonemap() over the upscaled picture, or with bloomed over its bloom -> (H, W, 4) uint8 at the display size"""
+        t = default_tonemap() if params is None else params
+        W, H = self.upscaled_size()
+        out = np.empty((H, W, 4), dtype=np.uint8)
+        f = self.L.pt_tonemap_upscaled; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(t), int(bloomed), _p(out), out.nbytes), "pt_tonemap_upscaled")
+        return out
+
+    def average_luminance_upscaled(self, bloomed=False):
+        """pt_average_luminance_upscaled: average_luminance() of the upscaled picture, or with bloomed of its bloom"""
+        v = ctypes.c_float(0.0)
+        f = self.L.pt_average_luminance_upscaled; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, int(bloomed), ctypes.byref(v)), "pt_average_luminance_upscaled")
         return float(v.value)
 
     def denoise_pass_times(self, enable=True):

@@ -604,7 +604,7 @@ int32_t pt_destroy(pt_context* c) {
     if (c->comm && g_rccl.lib) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
     c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
-    relax_free(c); taa_free(c); bloom_free(c);
+    relax_free(c); taa_free(c); bloom_free(c); taau_free(c);
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
     c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
     if (c->bvhAllocated) bvh_free(c->bvh);
@@ -642,7 +642,7 @@ int32_t pt_set_geometry(pt_context* c, const PtGeometryBuffers* b, const PtGeome
     c->geometries.resize(nGeoms); memcpy(c->geometries.data(), geoms, sizeof(GeometryDesc) * nGeoms);
     c->meshes.resize(nMeshes); memcpy(c->meshes.data(), meshes, sizeof(MeshDesc) * nMeshes);
     c->geomDirty = true;
-    relax_drop_history(c); taa_drop_history(c);      // a new scene: the denoiser's and the resolve's history are of another one
+    relax_drop_history(c); taa_drop_history(c); taau_drop_history(c);      // a new scene: the denoiser's and the two resolves' histories are of another one
     return PT_OK;
 }
 int32_t pt_set_instances(pt_context* c, const PtInstanceDesc* inst, uint32_t n) {
@@ -950,7 +950,7 @@ int32_t pt_set_settings(pt_context* c, const ::PtSettings* s) {
 int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
     if (!c || !w || !h || w > 65535 || h > 65535) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad size");
     (void)hipSetDevice(c->device);
-    if (w != c->width || h != c->height) { relax_drop_history(c); taa_drop_history(c); bloom_drop(c); }
+    if (w != c->width || h != c->height) { relax_drop_history(c); taa_drop_history(c); bloom_drop(c); taau_drop_history(c); }
     c->width = w; c->height = h; c->accumCount = 0; c->fbSamples = 0;
     build_shards(c);
     PT_CHECK_HIP(c, c->dAccum.resize((size_t)w * h));

@@ -207,6 +207,12 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // quarter-resolution images of the blur. bloomReady: a bloomed picture of bloomW x bloomH is there. bloomEvents: created by the first call that asks for its time.
     DevBuf<ptk::float4> dBloom, dBloomQ[2]; uint bloomW = 0, bloomH = 0; bool bloomReady = false;
     hipEvent_t bloomEvents[2] = {nullptr, nullptr};
+    // the temporal upscaling resolve (pt_taa_upscale; pt_taau.h): two display-size buffers that swap as dTaa's do (taauSide: the upscaled picture, the other one its history),
+    // of taauW x taauH pixels, resolved from a frame of taauRenderW x taauRenderH; a serial of its own under taaFrameSerial's rule. The display tail's bloomed picture
+    // (pt_bloom_upscaled) and its two quarter-resolution images: separate from dBloom. taauEvents / taauBloomEvents: created by the first call that asks for its time.
+    DevBuf<ptk::float4> dTaau[2], dTaauBloom, dTaauBloomQ[2]; uint taauW = 0, taauH = 0, taauRenderW = 0, taauRenderH = 0, taauSide = 0, taauFrameSerial = 0;
+    bool taauHistory = false, taauResolved = false, taauBloomReady = false;
+    hipEvent_t taauEvents[2] = {nullptr, nullptr}, taauBloomEvents[2] = {nullptr, nullptr};
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -247,6 +253,9 @@ int32_t taa_resolved_ready(pt_context* c);           // PT_OK with a resolved pi
 // ---- pt_bloom_api.hip: the bloomed picture is dropped (resize to another size) / the pass's buffers freed
 void bloom_drop(pt_context* c);
 void bloom_free(pt_context* c);
+// ---- pt_taau_api.hip: the upscaling resolve's history, picture and bloomed picture are dropped (resize to another size, new scene) / its buffers freed
+void taau_drop_history(pt_context* c);
+void taau_free(pt_context* c);
 // ---- pt_frame.hip
 // the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
 // passes that only address the buffers need: pack / unpack, merge, read-back)
