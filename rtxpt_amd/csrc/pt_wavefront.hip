@@ -286,11 +286,15 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
     else wave_add64(isHit ? 1ull : 0ull, &wc->hits);
 }
 
+// A visibility ray that ends visible leaves only this mark in the traversal loop (every writer of q2 leaves .w = 0): what the contribution does to its path is
+// not needed before the path's next vertex is shaded, and a read-modify-write of the path's radiance — two dependent round trips, the second a scattered one —
+// under a divergent branch between the stack pop and the next node loads holds the whole wave up. The resolve pass behind the launch applies the marks
+// (t8_resolve_shadow_body); the grouped queue's are folded by k_resolve_nee in sample order.
+__device__ __forceinline__ void shadow_mark_visible(ShadowQueue sq, uint i) { reinterpret_cast<float*>(sq.q2 + i)[3] = 1.0f; }
 template <bool GROUPED>
 // visible == the deferred NEE contribution lands (BridgeDonut:1026)
 __device__ __forceinline__ void shadow_visible(PathPool pool, ShadowQueue sq, uint i) {
-    // grouped queue: only mark, k_resolve_nee folds the group in sample order
-    if (GROUPED) { reinterpret_cast<float*>(sq.q2 + i)[3] = 1.0f; return; }
+    if (GROUPED) { shadow_mark_visible(sq, i); return; }
     float4 r = sq.q2[i];
     uint p = asuint(sq.q1[i].w);
     uint4 c = pool.s2[p];
@@ -319,8 +323,8 @@ __device__ __forceinline__ void shadow_visible(PathPool pool, ShadowQueue sq, ui
 
 // The visibility launch of a path vertex (Bridge::traceVisibilityRay for every entry of the shadow queue) as a device function: k_shadow, and k_trace_pair next
 // to the closest-hit rays of the next vertex.
-template <bool COUNT, bool GROUPED>
-__device__ __forceinline__ void t8_shadow_body(const DeviceScene& sc, const PathPool& pool, const ShadowQueue& sq, const uint count, WaveCounters* wc, const TravAux& aux, const uint rpc,
+template <bool COUNT>
+__device__ __forceinline__ void t8_shadow_body(const DeviceScene& sc, const ShadowQueue& sq, const uint count, WaveCounters* wc, const TravAux& aux, const uint rpc,
                                                uint2* stack, uint* rayBuf, const uint vBlock, const uint vGrid) {
     Traverse8Counters ctr; t8_counters_init(ctr);
     auto fetch = [&](uint i, float3& o, float3& d, float& tmin, float& tmax, uint& startRef, float& bestT0, uint& bestPrim0) -> uint {
@@ -328,17 +332,17 @@ __device__ __forceinline__ void t8_shadow_body(const DeviceScene& sc, const Path
         o = make_float3(a.x, a.y, a.z); d = make_float3(b.x, b.y, b.z); tmin = 0.0f; tmax = a.w; startRef = 0u; bestT0 = a.w; bestPrim0 = 0xFFFFFFFFu;
         return i;
     };
-    auto commit = [&](uint i, const HitInfo& h) { if (h.prim == 0xFFFFFFFFu) shadow_visible<GROUPED>(pool, sq, i); };      // occluded: nothing is committed
+    auto commit = [&](uint i, const HitInfo& h) { if (h.prim == 0xFFFFFFFFu) shadow_mark_visible(sq, i); };      // visible: a mark, one store; occluded: nothing is committed
     // a split shadow ray: "visible so far"; its sub-trees may set the flag, k_resolve_shadow applies the contribution if none did
     auto publish = [&](uint i, float, uint) { aux.bestKey[i] = 0ull; aux.resolveList[atomicAdd(&aux.counts[TRAV_RESOLVE], 1u)] = i; };
     T8_TRAVERSE<true, COUNT, false, false, true>(sc, count, rpc, stack, rayBuf, nullptr, fetch, commit, publish, TravTaskOut{aux.taskQ[0], &aux.counts[0], aux.taskCap}, ctr, &wc->overflow, vBlock, vGrid);
     if (COUNT) { wave_add64(ctr.nodeVisits, &wc->nodeVisitsSh); wave_add64(ctr.triTests, &wc->triTestsSh); wave_add64(ctr.leafVisits, &wc->leafVisitsSh); wave_add64(ctr.iters, &wc->itersSh); }
 }
-template <bool COUNT, bool GROUPED>
-__global__ void __launch_bounds__(T8_BLOCK, COUNT ? 1 : T8_SHADOW_MIN_WAVES) k_shadow(DeviceScene sc, PathPool pool, ShadowQueue sq, const uint* __restrict__ countPtr, WaveCounters* wc, TravAux aux, uint rpc) {
+template <bool COUNT>
+__global__ void __launch_bounds__(T8_BLOCK, COUNT ? 1 : T8_SHADOW_MIN_WAVES) k_shadow(DeviceScene sc, ShadowQueue sq, const uint* __restrict__ countPtr, WaveCounters* wc, TravAux aux, uint rpc) {
     __shared__ uint2 stack[T8_GROUPS_PER_BLOCK * BVH8_STACK_STRIDE];
     __shared__ uint rayBuf[T8_RAYBUF_WORDS];
-    t8_shadow_body<COUNT, GROUPED>(sc, pool, sq, *countPtr, wc, aux, rpc, stack, rayBuf, blockIdx.x, gridDim.x);
+    t8_shadow_body<COUNT>(sc, sq, *countPtr, wc, aux, rpc, stack, rayBuf, blockIdx.x, gridDim.x);
 }
 
 template <int STAGE, bool FINAL>
@@ -369,16 +373,26 @@ __global__ void __launch_bounds__(T8_BLOCK) k_shadow_tasks(DeviceScene sc, Shado
     t8_shadow_tasks_body<STAGE, FINAL>(sc, sq, wc, aux, stack, rayBuf, blockIdx.x, gridDim.x);
 }
 
+// The resolve pass of a visibility launch: the rays that were cut into sub-trees (resolve list) land if no sub-tree found an occluder, and — not GROUPED — a
+// sweep over the launch's `count` queue entries lands the contributions of the rays the traversal loop marked visible. Order: a later launch of the stream than
+// k_shadow / k_trace_pair and the task rounds (every mark is written), an earlier one than everything that reads or adds to a path's radiance or rewrites the
+// queue: the k_classify / k_shade of the next vertex, launch_sp_fill_resolve, k_accumulate, the tail kernel. A ray that was cut into sub-trees is published and
+// never committed, so the list and the marked set are disjoint; an entry names one path and a path has at most one pending entry, so no two threads touch one
+// slot. The sum is the fp16 addition the loop made, on the same operands: the image cannot change. `count` is the host's (k_resolve_pair zeroes the device's
+// word in this very launch); 0 is fine.
 template <bool GROUPED>
-__device__ __forceinline__ void t8_resolve_shadow_body(const PathPool& pool, const ShadowQueue& sq, const TravAux& aux, const uint vBlock, const uint vGrid) {
+__device__ __forceinline__ void t8_resolve_shadow_body(const PathPool& pool, const ShadowQueue& sq, const TravAux& aux, const uint count, const uint vBlock, const uint vGrid) {
     const uint n = aux.counts[TRAV_RESOLVE];
     for (uint k = vBlock * 256u + threadIdx.x; k < n; k += vGrid * 256u) {
         uint i = aux.resolveList[k];
         if (aux.bestKey[i] == 0ull) shadow_visible<GROUPED>(pool, sq, i);
     }
+    if (GROUPED) return;
+    for (uint i = vBlock * 256u + threadIdx.x; i < count; i += vGrid * 256u)
+        if (reinterpret_cast<const float*>(sq.q2 + i)[3] == 1.0f) shadow_visible<false>(pool, sq, i);
 }
 template <bool GROUPED>
-__global__ void __launch_bounds__(256) k_resolve_shadow(PathPool pool, ShadowQueue sq, TravAux aux) { t8_resolve_shadow_body<GROUPED>(pool, sq, aux, blockIdx.x, gridDim.x); }
+__global__ void __launch_bounds__(256) k_resolve_shadow(PathPool pool, ShadowQueue sq, TravAux aux, uint count) { t8_resolve_shadow_body<GROUPED>(pool, sq, aux, count, blockIdx.x, gridDim.x); }
 
 // ---- Fused traversal launches (round 6). The visibility rays of path vertex k and the closest-hit rays of vertex k + 1 are independent of each other — the
 // visibility results only have to be in the paths' radiance before vertex k + 1 is SHADED (the order of the fp16 additions into PathState::L: the light sample
@@ -393,7 +407,7 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_trace_pair(D
     __shared__ uint rayBuf[T8_RAYBUF_WORDS];
     __shared__ float2 mineUV[T8_BLOCK];
     if (blockIdx.x < blocksE) t8_extend_body<false, false>(sc, pool, queue, *extCountPtr, wc, auxE, rpcE, stack, rayBuf, mineUV, blockIdx.x, blocksE);
-    else t8_shadow_body<false, false>(sc, pool, sq, *shCountPtr, wc, auxS, rpcS, stack, rayBuf, blockIdx.x - blocksE, gridDim.x - blocksE);
+    else t8_shadow_body<false>(sc, sq, *shCountPtr, wc, auxS, rpcS, stack, rayBuf, blockIdx.x - blocksE, gridDim.x - blocksE);
 }
 template <int STAGE, bool FINAL = (STAGE == 3)>
 __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_tasks_pair(DeviceScene sc, PathPool pool, ShadowQueue sq, WaveCounters* wc, TravAux auxE, TravAux auxS) {
@@ -405,10 +419,9 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_tasks_pair(D
 }
 // ... and the two resolve passes; the shadow queue's counter is zeroed here for the k_shade that follows (every reader of it — k_trace_pair — is an earlier
 // launch of the stream)
-__global__ void __launch_bounds__(256) k_resolve_pair(DeviceScene sc, PathPool pool, ShadowQueue sq, TravAux auxE, TravAux auxS, uint* shadowCount) {
-    const uint half = gridDim.x >> 1;
-    if (blockIdx.x < half) t8_resolve_extend_body(sc, pool, auxE, blockIdx.x, half);
-    else { t8_resolve_shadow_body<false>(pool, sq, auxS, blockIdx.x - half, gridDim.x - half); if (blockIdx.x == half && threadIdx.x == 0u) *shadowCount = 0u; }
+__global__ void __launch_bounds__(256) k_resolve_pair(DeviceScene sc, PathPool pool, ShadowQueue sq, TravAux auxE, TravAux auxS, uint* shadowCount, uint shCount, uint blocksE) {
+    if (blockIdx.x < blocksE) t8_resolve_extend_body(sc, pool, auxE, blockIdx.x, blocksE);
+    else { t8_resolve_shadow_body<false>(pool, sq, auxS, shCount, blockIdx.x - blocksE, gridDim.x - blocksE); if (blockIdx.x == blocksE && threadIdx.x == 0u) *shadowCount = 0u; }
 }
 
 // NEEFullSamples != 1: NEEResult accumulates the visible samples of a path vertex in sample order (fp16, PathTracerTypes.hlsli:170-207), then the
@@ -760,6 +773,11 @@ void launch_generate(const PathKernelContext& k, PathPool pool, const uint* owne
 }
 // task rounds + resolve pass of one traversal launch; all counts live on the device, so the grids are fixed (empty rounds return at once)
 static const uint T8_TASK_BLOCKS = T8_TASK_BLOCKS_N, T8_RESOLVE_BLOCKS = 256;
+// ... except the visibility resolve's: its sweep over the launch's queue entries (t8_resolve_shadow_body) is sized by the host's count — one entry per thread
+// up to 2048 blocks (the 2048 threads a CU holds, on 256 CUs: chosen by that count, not by an A/B — all sweeps of a 4K step together take 0.34 ms), never
+// fewer blocks than the resolve list wants, and a zero count is a valid launch
+static const uint T8_SWEEP_BLOCKS = 2048;
+static inline uint shadow_resolve_grid(uint count) { const uint g = grid_for(count, 256u, T8_SWEEP_BLOCKS); return g < T8_RESOLVE_BLOCKS ? T8_RESOLVE_BLOCKS : g; }
 void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged) {
     const uint rpc = rays_per_chunk(count);
     uint g = grid_for(count, (T8_BLOCK / 64u) * rpc * T8_CHUNKS_PER_WAVE_MIN, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
@@ -783,7 +801,8 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
 }
 // One launch for the closest-hit rays of the extend queue AND the visibility rays the previous vertex left in the shadow queue (k_trace_pair), then the task
 // rounds and resolve passes of both. auxE / auxS: separate task queues, counters, merge keys and resolve lists. The grid is what the two launches would use if
-// it fits the bound, else the bound split by ray count (a visibility ray costs about what a closest-hit ray costs: 0.50 against 0.44 ns on C3). Zeroes
+// it fits the bound, else the bound split by ray count (a visibility ray costs about what a closest-hit ray costs: 0.47 against 0.44 ns on C3, its launch's
+// sweep included — 11.70 ms for 25.00 M against 44.41 ms for 101.73 M rays of a serial-kernel step, table 2 of profiles/r11a_deferred_visibility_ab.txt; within 10 %: no weights). Zeroes
 // *shCountPtr at its end. Precondition: the bound (auxE.maxBlocks, where set) is >= 2 — each half needs a block, and with a bound of 1 the visibility half
 // would get none while its count is zeroed all the same; pt_render clamps the only way in (MI355PT_MAX_BLOCKS).
 void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* extCountPtr, uint extCount, ShadowQueue sq, uint* shCountPtr, uint shCount, WaveCounters* wc, TravAux auxE, TravAux auxS, hipStream_t st) {
@@ -807,7 +826,7 @@ void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, 
         hipLaunchKernelGGL((k_tasks_pair<2>), tg, tb, 0, st, sc, pool, sq, wc, auxE, auxS);
         hipLaunchKernelGGL((k_tasks_pair<3>), tg, tb, 0, st, sc, pool, sq, wc, auxE, auxS);
     }
-    hipLaunchKernelGGL(k_resolve_pair, dim3(2u * T8_RESOLVE_BLOCKS), dim3(256), 0, st, sc, pool, sq, auxE, auxS, shCountPtr);
+    hipLaunchKernelGGL(k_resolve_pair, dim3(T8_RESOLVE_BLOCKS + shadow_resolve_grid(shCount)), dim3(256), 0, st, sc, pool, sq, auxE, auxS, shCountPtr, shCount, T8_RESOLVE_BLOCKS);
 }
 // k_classify for a caller in another translation unit (the stable-plane fill pass): classScratch 2 x countIn words, classCount 3 words (zero on entry)
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st) {
@@ -839,10 +858,9 @@ void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn
 void launch_shadow(const DeviceScene& sc, PathPool pool, ShadowQueue sq, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st) {
     const uint rpc = rays_per_chunk(count);
     uint g = grid_for(count, (T8_BLOCK / 64u) * rpc * T8_CHUNKS_PER_WAVE_MIN, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
-    // (no traversal counters in the grouped mode)
-    if (sq.group) hipLaunchKernelGGL((k_shadow<false, true>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, sq, countPtr, wc, aux, rpc);
-    else if (counters) hipLaunchKernelGGL((k_shadow<true, false>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, sq, countPtr, wc, aux, rpc);
-    else hipLaunchKernelGGL((k_shadow<false, false>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, sq, countPtr, wc, aux, rpc);
+    // (one loop for both queue layouts: it only marks. No traversal counters in the grouped mode)
+    if (counters && !sq.group) hipLaunchKernelGGL((k_shadow<true>), dim3(g), dim3(T8_BLOCK), 0, st, sc, sq, countPtr, wc, aux, rpc);
+    else hipLaunchKernelGGL((k_shadow<false>), dim3(g), dim3(T8_BLOCK), 0, st, sc, sq, countPtr, wc, aux, rpc);
     hipLaunchKernelGGL((k_shadow_tasks<0>), dim3(T8_TASK_BLOCKS), dim3(T8_BLOCK), 0, st, sc, sq, wc, aux);
     // (as launch_extend: two rounds for a small launch)
     if (count <= T8_SHORT_TAIL_BELOW) hipLaunchKernelGGL((k_shadow_tasks<1, true>), dim3(T8_TASK_BLOCKS), dim3(T8_BLOCK), 0, st, sc, sq, wc, aux);
@@ -851,8 +869,8 @@ void launch_shadow(const DeviceScene& sc, PathPool pool, ShadowQueue sq, const u
     hipLaunchKernelGGL((k_shadow_tasks<2>), dim3(T8_TASK_BLOCKS), dim3(T8_BLOCK), 0, st, sc, sq, wc, aux);
     hipLaunchKernelGGL((k_shadow_tasks<3>), dim3(T8_TASK_BLOCKS), dim3(T8_BLOCK), 0, st, sc, sq, wc, aux);
     }
-    if (sq.group) hipLaunchKernelGGL((k_resolve_shadow<true>), dim3(T8_RESOLVE_BLOCKS), dim3(256), 0, st, pool, sq, aux);
-    else hipLaunchKernelGGL((k_resolve_shadow<false>), dim3(T8_RESOLVE_BLOCKS), dim3(256), 0, st, pool, sq, aux);
+    if (sq.group) hipLaunchKernelGGL((k_resolve_shadow<true>), dim3(T8_RESOLVE_BLOCKS), dim3(256), 0, st, pool, sq, aux, 0u);      // (marks only; k_resolve_nee folds them)
+    else hipLaunchKernelGGL((k_resolve_shadow<false>), dim3(shadow_resolve_grid(count)), dim3(256), 0, st, pool, sq, aux, count);
     if (sq.group) hipLaunchKernelGGL(k_resolve_nee, dim3(grid_for(count / sq.group, 256, 4096)), dim3(256), 0, st, pool, sq, countPtr);
 }
 // start of a pass: the batch's PASS_COUNTERS words and the two queue counters the pass refills, zeroed by one launch (three memsets were three launches)

@@ -14,10 +14,10 @@ Formulas (gfx94x definitions, the ones rocprofv3 falls back to on gfx950, MI355X
 import os, csv, glob, json, sys, collections
 
 d = sys.argv[1]
-GROUPS = (("extend", ("k_extend<false, false>", "k_extend_tasks", "k_resolve_extend")), ("shadow", ("k_shadow<false, false>", "k_shadow_tasks", "k_resolve_shadow")), ("shade", ("k_shade<false", "k_classify")),
+GROUPS = (("extend", ("k_extend<false, false>", "k_extend_tasks", "k_resolve_extend")), ("shadow", ("k_shadow<false>", "k_shadow_tasks", "k_resolve_shadow")), ("shade", ("k_shade<false", "k_classify")),
           ("pair", ("k_trace_pair", "k_tasks_pair", "k_resolve_pair")),      # the fused traversal launches of a pipelined frame (PIPELINED=1 tools/profile_round.sh)
           ("generate", ("k_generate",)), ("accumulate", ("k_accumulate",)))
-MAIN = {"pair": "k_trace_pair", "extend": "k_extend<false, false>", "shadow": "k_shadow<false, false>", "shade": "k_shade<false", "generate": "k_generate", "accumulate": "k_accumulate"}
+MAIN = {"pair": "k_trace_pair", "extend": "k_extend<false, false>", "shadow": "k_shadow<false>", "shade": "k_shade<false", "generate": "k_generate", "accumulate": "k_accumulate"}
 
 
 def group_of(name):
