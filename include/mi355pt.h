@@ -854,7 +854,10 @@ int32_t pt_set_tail_paths(pt_context* ctx, uint32_t maxPaths);
    launches of a bounce, which is what a small frame (one rank of a tile-sharded frame) is bound by. mode 0 = off, 1 = on (default), 2 = by the size of the pt_render call
    (environment MI355PT_FUSED_TRAVERSAL overrides it at pt_create). Ignored for NEEFullSamples > 1, serial-kernel and counter frames.
    The same frames keep the live paths' state compacted by queue position from the second bounce on (on by default; environment MI355PT_COMPACT_POOL=0 switches it off at
-   pt_create; not with NEE-AT). It costs memory: five more uint4 arrays per path, 80 bytes on top of the pool's 96. */
+   pt_create; not with NEE-AT). It costs memory: five more uint4 arrays per path, 80 bytes on top of the pool's 96.
+   A compacted batch whose first pass is a wavefront pass (not the tail kernel) starts without a generation launch: the launches of that pass form a path's vertex-0 state — camera ray,
+   pixel, sample index, constants of the frame — where they use it instead of reading back what a generation launch stored (on by default; environment
+   MI355PT_FIRST_VERTEX_IN_PLACE=0 at pt_create: every batch starts with k_generate, as before). Same operations on the same operands: no image depends on it (tests/test_gpu_first_vertex.py). */
 int32_t pt_set_fused_traversal(pt_context* ctx, uint32_t mode);
 
 #ifdef __cplusplus

@@ -1299,7 +1299,9 @@ class PathTracer:
 
     def set_fused_traversal(self, mode):
         """pt_set_fused_traversal: 0 = visibility rays in launches of their own, 1 = in the next bounce's closest-hit launch (k_trace_pair), 2 = by the size of the call. Default 1.
-        The same frames keep the live paths compacted by queue position (environment MI355PT_COMPACT_POOL=0 at pt_create: off), at five more uint4 arrays per path."""
+        The same frames keep the live paths compacted by queue position (environment MI355PT_COMPACT_POOL=0 at pt_create: off), at five more uint4 arrays per path.
+        A compacted batch starts without a generation launch: its first pass forms the vertex-0 state where it is used (environment MI355PT_FIRST_VERTEX_IN_PLACE=0 at pt_create:
+        k_generate in front of every batch, as before). No image depends on either switch."""
         self._chk(self.L.pt_set_fused_traversal(self.h, int(mode)), "pt_set_fused_traversal")
 
     def tonemap(self, params=None):

@@ -83,6 +83,11 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 // pt_render keeps the live paths' state compacted by queue position (ptk::PathPool::home; environment MI355PT_COMPACT_POOL overrides)
 #define PT_COMPACT_POOL 1
 #endif
+#ifndef PT_FIRST_VERTEX_IN_PLACE
+// pt_render's compacted batches start without k_generate: the first pass's launches form the vertex-0 state where they use it (ptk::FirstVertex;
+// environment MI355PT_FIRST_VERTEX_IN_PLACE overrides)
+#define PT_FIRST_VERTEX_IN_PLACE 1
+#endif
 #ifndef PT_FREE_RUN_BELOW
 // pt_render: once every live batch holds fewer paths than this, the batches stop advancing in lockstep (0: lockstep to the end)
 #define PT_FREE_RUN_BELOW (1u << 22)
@@ -98,7 +103,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     int device = 0; hipStream_t stream = nullptr; uint shardRank = 0, shardCount = 1;
     // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
     hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
-    uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0;
+    uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
     std::string lastError;
     // host copies of the scene (kept for re-bake / animation)
     std::vector<uint> indices; std::vector<float> positions; std::vector<ptk::float2> uvs; std::vector<uint> normals, tangents;

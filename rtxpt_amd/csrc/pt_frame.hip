@@ -160,6 +160,7 @@ struct RenderBatch : Batch {
     uint tailLaunches = 0; bool afterTail = false, inTail = false;
     uint pendingShadow = 0; TravAux auxSh;                          // fused traversal launches (enable_fused)
     PathPool poolSet[2]; uint set = 0; bool compact = false;        // the compacted pool (enable_compact_pool)
+    bool firstInPlace = false;                                      // no k_generate: the first pass forms the vertex-0 state itself (enable_first_vertex_in_place)
     bool timed = false; Events marks; size_t t0 = 0, t1 = 0;
     struct Span { size_t a, b; int kind; uint items; }; std::vector<Span> spans;      // kind: 0 extend, 1 shade, 2 shadow, 3 tail
     size_t mark() { return timed ? marks.mark(st) : 0; }
@@ -208,7 +209,10 @@ struct RenderFrame {
         if (fuse) { int32_t r = enable_fused(); if (r != PT_OK) return r; }
         // (the compacted pool is not for NEE-AT either: its visibility resolve patches the path's flags)
         const bool neeatShade = c->dsc.lights.LocalSamplingBuffer != nullptr || c->dsc.lights.TemporalFeedbackRequired != 0u;
-        if (composed && c->compactPool && !neeatShade && !feedback) return enable_compact_pool();
+        if (composed && c->compactPool && !neeatShade && !feedback) {
+            int32_t r = enable_compact_pool(); if (r != PT_OK) return r;
+            if (c->firstVertexInPlace) enable_first_vertex_in_place();
+        }
         return PT_OK;
     }
     // Fused traversal launches (pt_set_fused_traversal, k_trace_pair): the visibility rays a bounce's shading leaves in the shadow queue are not
@@ -246,12 +250,30 @@ struct RenderFrame {
         }
         return PT_OK;
     }
+    // Vertex 0 in place (ptk::FirstVertex). k_generate writes 80 bytes of state and a queue word per path, and the first pass reads them back: the
+    // ray in k_extend, the flags word in k_classify, everything in k_shade — none of which holds information: at vertex 0 a path's state is its
+    // camera ray, its pixel id and sample index, and constants of the frame. A compacted batch whose first pass is a wavefront pass therefore
+    // starts without k_generate, and that pass launches k_extend_first, k_classify<UNIFORM> and k_shade<..., FIRST>, which form what they
+    // need. Who else reads vertex-0 state, and why each is covered:
+    //  - the task rounds and the resolve pass behind k_extend_first read s0 / s1 of rays cut into sub-trees: k_extend_first writes those;
+    //  - k_shade's survivors and every s2 go where PathCompactIO's go, so pass 1 and the visibility resolve find what they always found;
+    //  - k_accumulate reads s2 at the home slots: every path is shaded at vertex 0, alive or not, and k_shade writes its s2 there;
+    //  - the tail kernel and k_uncompact read the pool: a batch small enough to START in the tail kernel keeps k_generate (below); a batch
+    //    that gets there later is past vertex 0;
+    //  - the extend queue (pool.home) of pass 0 would be the identity: the three launches use the position instead.
+    // Serial-kernel and counter frames, grouped NEE samples, NEE-AT and feedback frames are not compacted and keep k_generate as well.
+    void enable_first_vertex_in_place() {
+        for (uint b = 0; b < numBatches; b++) {
+            RenderBatch& t = B[b]; t.firstInPlace = t.compact && !(tailBelow && t.total <= tailBelow);
+            t.hwc->firstCamera.cam = t.k.cam; t.hwc->firstCamera.perPixelJitterAAScale = t.k.S.perPixelJitterAAScale;      // (uploaded with the block by start())
+        }
+    }
     int32_t start() {
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b];
             t.t0 = t.mark();
             PT_CHECK_HIP(c, hipMemcpyAsync(t.wc, t.hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, t.st));
-            launch_generate(t.k, t.pool, c->dOwned.p + t.pixFirst, t.numPix, first, count, 0u, t.total, t.queue[0], nullptr, t.st);
+            if (!t.firstInPlace) launch_generate(t.k, t.pool, c->dOwned.p + t.pixFirst, t.numPix, first, count, 0u, t.total, t.queue[0], nullptr, t.st);
         }
         return PT_OK;
     }
@@ -269,7 +291,11 @@ struct RenderFrame {
         PathPool pin = t.pool, pout = PathPool{};
         if (t.compact) { pin = t.poolSet[t.set]; pin.home = t.queue[t.cur]; pout = t.poolSet[t.set ^ 1u]; t.set ^= 1u; }
         const uint* countIn = &t.wc->extendCount[t.cur];
-        if (t.pendingShadow) {
+        // (pass 0 of a batch has no visibility rays pending)
+        const bool vertex0 = t.firstInPlace && t.iterations == 0u;
+        const FirstVertex fv{c->dOwned.p + t.pixFirst, t.numPix, first, count};
+        if (vertex0) launch_extend_first(t.k, pin, fv, countIn, t.active, t.wc, t.aux, t.st);
+        else if (t.pendingShadow) {
             launch_trace_pair(t.sc, pin, t.queue[t.cur], countIn, t.active, t.sq, &t.wc->shadowCount, t.pendingShadow, t.wc, t.aux, t.auxSh, t.st);
             t.pendingShadow = 0;
         } else launch_extend(t.sc, pin, t.queue[t.cur], countIn, t.active, t.wc, c->countersEnabled, t.aux, t.st);
@@ -278,7 +304,7 @@ struct RenderFrame {
         // queue order: one launch fewer
         uint* classScratch = t.active >= PT_CLASSIFY_FROM ? reinterpret_cast<uint*>(t.aux.bestKey) : nullptr;
         launch_shade(t.k, pin, t.queue[t.cur], countIn, t.active, t.queue[nxt], &t.wc->extendCount[nxt], t.sq, t.wc, classScratch,
-                     t.aux.counts + PASS_CLASS_OFFSET, t.st, pout);
+                     t.aux.counts + PASS_CLASS_OFFSET, t.st, pout, vertex0 ? &fv : nullptr);
         const size_t e2 = t.mark(); t.span(e1, e2, 1, t.active);
         t.extendRays += t.active;
         PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));

@@ -231,13 +231,14 @@ template <bool LP16> struct PathKernelContextT {
         if (S.bounceCount < vertexIndex) return true;
         return diffuseBounces > S.diffuseBounceCount;
     }
-    // EmptyPathInitialize + SetupPathPrimaryRay + Bridge::computeCameraRay (PathTracer.hlsli:47-119, BridgeDonut:543-564, PathTracerHelpers.hlsli:126-153)
     // Bridge::computeCameraRay (BridgeDonut:543-564) for a pixel and sample index: origin on the near plane and direction
-    void computeCameraRay(uint px, uint py, uint sampleIndex, float3& o, float3& d) const {
+    void computeCameraRay(uint px, uint py, uint sampleIndex, float3& o, float3& d) const { cameraRay(cam, S.perPixelJitterAAScale, px, py, sampleIndex, o, d); }
+    // (the text itself, as a function of the two inputs it has besides the pixel and the sample: k_extend_first, pt_wavefront.hip, reads them from memory where it forms a ray)
+    static void cameraRay(const PathTracerCameraData& cam, float perPixelJitterAAScale, uint px, uint py, uint sampleIndex, float3& o, float3& d) {
         SampleGeneratorVertexBase vb = SampleGeneratorVertexBase::make((px << 16) | py, 0, sampleIndex);
         SampleSequenceGenerator sg = SampleSequenceGenerator::make(vb);
         float2 r0 = sampleNext2D(sg);
-        float2 subPixelOffset = make_float2(cam.Jitter.x + (r0.x - 0.5f) * S.perPixelJitterAAScale, cam.Jitter.y + (r0.y - 0.5f) * S.perPixelJitterAAScale);
+        float2 subPixelOffset = make_float2(cam.Jitter.x + (r0.x - 0.5f) * perPixelJitterAAScale, cam.Jitter.y + (r0.y - 0.5f) * perPixelJitterAAScale);
         float2 dof = sampleNext2D(sg);
         float2 pp = make_float2(((float)px + 0.5f + -subPixelOffset.x) / (float)cam.ViewportSize.x, ((float)py + 0.5f + subPixelOffset.y) / (float)cam.ViewportSize.y);
         float2 ndc = make_float2(2.f * pp.x + -1.f, -2.f * pp.y + 1.f);
@@ -256,7 +257,10 @@ template <bool LP16> struct PathKernelContextT {
     void ExportDepth(const PathState& path, float3 virtualWorldPos) const {
         sc.lights.DepthExport[(path.id & 0xFFFFu) * sc.lights.DepthWidth + (path.id >> 16)] = LightTable_ClipDepth(sc.lights, virtualWorldPos);
     }
-    PathState generate(uint px, uint py, uint sampleIndex) const {
+    // EmptyPathInitialize + SetupPathPrimaryRay + Bridge::computeCameraRay (PathTracer.hlsli:47-119, BridgeDonut:543-564, PathTracerHelpers.hlsli:126-153), in two
+    // parts. The vertex-0 state of a path without its camera ray (origin and direction stay zero): constants of the frame, the pixel id and the sample index. A
+    // kernel that starts the path where it is first used (pt_wavefront_device.h PathFirstVertexIO) forms this instead of loading it
+    PathState generateState(uint px, uint py, uint sampleIndex) const {
         PathState p; __builtin_memset(&p, 0, sizeof(p));
         p.id = (px << 16) | py; p.sampleIndex = sampleIndex;
         p.SetThp(make_float3(1.f));
@@ -266,22 +270,11 @@ template <bool LP16> struct PathKernelContextT {
         p.SetFireflyFilterK_BsdfScatterPdf(1.0f, 0.0f);
         p.SetPackedMISInfo_ThpRuRuCorrection(NEEBSDFMISInfo::empty().Pack16bit(), 1.0f);
         if (HasFinishedSurfaceBounces(p.getVertexIndex() + 1, p.getCounter(PC_DiffuseBounces))) p.setFlag(PF_terminateAtNextBounce);
-        SampleGeneratorVertexBase vb = SampleGeneratorVertexBase::make((px << 16) | py, 0, sampleIndex);
-        SampleSequenceGenerator sg = SampleSequenceGenerator::make(vb);
-        float2 r0 = sampleNext2D(sg);
-        float2 subPixelOffset = make_float2(cam.Jitter.x + (r0.x - 0.5f) * S.perPixelJitterAAScale, cam.Jitter.y + (r0.y - 0.5f) * S.perPixelJitterAAScale);
-        float2 dof = sampleNext2D(sg);
-        float2 pp = make_float2(((float)px + 0.5f + -subPixelOffset.x) / (float)cam.ViewportSize.x, ((float)py + 0.5f + subPixelOffset.y) / (float)cam.ViewportSize.y);
-        float2 ndc = make_float2(2.f * pp.x + -1.f, -2.f * pp.y + 1.f);
-        float3 org = cam.PosW;
-        float3 dir = (ndc.x * cam.CameraU + ndc.y * cam.CameraV) + cam.CameraW;
-        float2 ap = sample_disk(dof);
-        float3 rayTarget = org + dir;
-        org = org + cam.ApertureRadius * (ap.x * normalize(cam.CameraU) + ap.y * normalize(cam.CameraV));
-        dir = normalize(rayTarget - org);
-        float invCos = 1.f / dot(normalize(cam.CameraW), dir);
-        float tMin = cam.NearZ * invCos;
-        p.origin = org + dir * tMin; p.dir = dir;
+        return p;
+    }
+    PathState generate(uint px, uint py, uint sampleIndex) const {
+        PathState p = generateState(px, py, sampleIndex);
+        computeCameraRay(px, py, sampleIndex, p.origin, p.dir);
         return p;
     }
 

@@ -25,12 +25,21 @@ struct PathPool { uint4* s0; uint4* s1; uint4* s2; uint4* s3; uint4* s4; uint4* 
 struct ShadowQueue { float4* q0; float4* q1; float4* q2; uint group;           // group: 0 = one entry per path vertex (NEEFullSamples 1), else entries come in groups of `group` (pt_path.h ShadowSink)
     // NEE-AT feedback (null: off): q3 = {weight, random, light | SSC flag, roulette fix-up} per entry (pt_path.h ShadowRequest); the sub-frame's feedback reservoirs, one slot per pixel
     float4* q3; float* fbTotalWeight; uint* fbCandidates; uint fbWidth, fbPlane, fbSampleFirst; };      // slot = (sample - fbSampleFirst) * fbPlane + y * fbWidth + x
+// Vertex 0 in place (pt_render's compacted batches, pt_frame.hip): the launches of a batch's first pass form a path's vertex-0 state where they use it instead of reading what
+// k_generate would have stored. Path i of the batch is sample sampleFirst + i % spp of owned pixel ownedPixels[i / spp] — k_generate's map (first_vertex_of,
+// pt_wavefront_device.h) — and everything else of the state follows from the frame's settings and camera (PathKernelContextT::generateState, computeCameraRay).
+struct FirstVertex { const uint* ownedPixels; uint numOwned, sampleFirst, spp; };
+// what a camera ray is a function of besides the pixel and the sample, in memory (WaveCounters::firstCamera) for k_extend_first
+struct FirstVertexCamera { PathTracerCameraData cam; float perPixelJitterAAScale, _pad[3]; };
 struct WaveCounters {           // device-resident counters / stats (one 256 B block)
     uint extendCount[2]; uint shadowCount; uint overflow;
     unsigned long long hits, nodeVisitsExt, triTestsExt, nodeVisitsSh, triTestsSh, leafVisitsExt, itersExt, leafVisitsSh, itersSh, phaseCycExt[4], leafBlocksExt, eventsExt[8], itersMaxExt, rayIterHistExt[16]; uint longRayCount, _padLong; float longRays[32][8];
     unsigned long long shadowValid;     // grouped shadow queue: entries that carry a light sample (= shadow rays in the reference's sense)
     unsigned long long tailExtendRays, tailShadowRays;      // rays the tail kernel traced itself (pt_tail.hip); what it hands back is counted by the launches that trace it
     unsigned long long tailHandedBack[3];                   // paths the tail kernel handed back: extend stragglers, visibility stragglers, still alive at the bounce bound
+    // not a counter — the frame's camera for k_extend_first, which reads it where it forms a ray instead of holding twenty more scalars across the traversal loop (it has none to
+    // spare): set by the host, it rides with the block's upload at the start of a frame
+    FirstVertexCamera firstCamera;
 };
 
 // straggler splitting (pt_traverse8.h): per pipelined batch, two task queues (ping-pong), the per-ray merge keys and the list of rays to resolve.
@@ -45,10 +54,14 @@ struct TravAux { TravTask* taskQ[2]; uint* counts; uint taskCap; unsigned long l
 // paths [first, first + n) of the pool region -> queue[0 .. n); countPtr (may be null): the counter of the queue `queue` is the end of, incremented by n (k_generate)
 void launch_generate(const PathKernelContext& k, PathPool pool, const uint* ownedPixels, uint numOwned, uint sampleFirst, uint spp, uint first, uint n, uint* queue, uint* countPtr, hipStream_t st);
 void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged = false);      // ranged: the rays' intervals wait in pool.hit[p].xy (k_extend)
+// launch_extend for the first pass of a batch whose paths were NOT generated: ray i is the camera ray of path i of `fv` (no queue, no read of pool.s0 / s1). The rays that are cut into
+// sub-trees get their origin | id and direction | length written to pool.s0 / s1 [i] by a launch over the resolve list (k_first_split_rays), for the task rounds and the resolve pass behind it. The camera: wc->firstCamera. Composed frames only (no counters).
+void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, hipStream_t st);
 // classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (3 words, zero on entry): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr,
-                  ShadowQueue sq, WaveCounters* wc, uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool = PathPool{});      // outPool: a compacted pool's other array set (pool.home != nullptr)
+                  ShadowQueue sq, WaveCounters* wc, uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool = PathPool{},      // outPool: a compacted pool's other array set (pool.home != nullptr)
+                  const FirstVertex* fv = nullptr);      // fv: vertex 0 of paths that were not generated — k_classify and k_shade form the state (pool.home is not read: position == home slot). Compacted pool, sq.group == 0, no NEE-AT
 // a compacted pool's live paths back to their home slots: out.s0 / s1 / s3 / s4 [home[i]] = in...[i] for the *countPtr positions (out: another array set than in's); the queue `in.home` is then an ordinary extend queue
 void launch_uncompact(PathPool in, PathPool out, const uint* countPtr, uint count, hipStream_t st);
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st);      // k_classify: {continuing hit, terminating hit, miss} made contiguous

@@ -11,9 +11,6 @@
 
 namespace ptk {
 
-#ifndef PT_SAMPLE_MINOR
-#define PT_SAMPLE_MINOR 1       // 1: the samples of a pixel are neighbours in the path pool (pixel-major), 0: all pixels of sample 0, then of sample 1, ...
-#endif
 #ifndef T8_CHUNKS_PER_WAVE_MIN
 #define T8_CHUNKS_PER_WAVE_MIN 1     // small launches: fewer waves, each working through this many 64-ray chunks (idle quads refill from the next chunk)
 #endif
@@ -30,13 +27,8 @@ __global__ void __launch_bounds__(256) k_generate(PathKernelContext k, PathPool 
     const uint t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n) return;
     const uint i = first + t;
-#if PT_SAMPLE_MINOR
-    // the samples of a pixel are neighbours in the pool: a 64-path chunk is 16 pixels x 4 samples
-    uint kpx = i / spp, s = i - kpx * spp, px = ownedPixels[kpx];
-#else
-    uint s = i / numOwned, px = ownedPixels[i - s * numOwned];
-#endif
-    PathState p = k.generate(px >> 16, px & 0xFFFFu, sampleFirst + s);
+    uint px, sample; first_vertex_of(FirstVertex{ownedPixels, numOwned, sampleFirst, spp}, i, px, sample);
+    PathState p = k.generate(px >> 16, px & 0xFFFFu, sample);
     store_path(pool, i, p);
     queue[t] = i;
     if (countPtr && t == 0u) atomicAdd(countPtr, n);
@@ -45,14 +37,28 @@ __global__ void __launch_bounds__(256) k_generate(PathKernelContext k, PathPool 
 // The closest-hit launch of a bounce (Bridge::traceScatterRay for every path of the extend queue) as a device function, so that two kernels can run it:
 // k_extend, and k_trace_pair next to the visibility rays of the previous vertex. vBlock / vGrid: this block's place among the blocks that work on the extend
 // queue (traverse8_pairs).
-template <bool COUNT, bool RANGED>
+// FIRST: the first pass of a batch whose paths were not generated (FirstVertex, pt_wavefront.h): ray i is the camera ray of path i, formed at the chunk refill from the owned
+// pixel and the sample index — no queue, no stored ray. The rays that end up cut into sub-trees (thousands of a launch, not millions) are on the resolve list: k_first_split_rays
+// writes their origin | id and direction | length to pool.s0 / s1 behind the launch, where the task rounds and the resolve pass read them as in every other pass.
+template <bool COUNT, bool RANGED, bool FIRST = false>
 __device__ __forceinline__ void t8_extend_body(const DeviceScene& sc, const PathPool& pool, const uint* __restrict__ queue, const uint count, WaveCounters* wc, const TravAux& aux, const uint rpc,
-                                               uint2* stack, uint* rayBuf, float2* mineUV, const uint vBlock, const uint vGrid) {
+                                               uint2* stack, uint* rayBuf, float2* mineUV, const uint vBlock, const uint vGrid, const FirstVertex* fv = nullptr) {
+    static_assert(!FIRST || (!COUNT && !RANGED), "vertex 0 in place: composed frames only");
     // RANGED: every ray brings its own interval in the first two words of its (not yet written) hit record — the stable-plane fill pass's first launch,
     // FirstHitFromVBuffer (pt_stableplanes.h firstHitInterval). A ray of such a launch that is cut into sub-trees continues over [0, best hit so far]: the
     // lower bound is a hint, not part of the query.
     Traverse8Counters ctr; t8_counters_init(ctr);
+    // FIRST: the camera comes from memory (WaveCounters::firstCamera) each time a ray is formed, behind a compiler barrier: as kernel arguments its twenty scalars, and what the
+    // compiler hoists of the ray's arithmetic, would be live across the traversal loop, which runs at its register bound
     auto fetch = [&](uint i, float3& o, float3& d, float& tmin, float& tmax, uint& startRef, float& bestT0, uint& bestPrim0) -> uint {
+        if (FIRST) {
+            asm volatile("" ::: "memory");
+            const FirstVertexCamera fc = wc->firstCamera;
+            uint px, sample; first_vertex_of(*fv, i, px, sample);
+            PathKernelContext::cameraRay(fc.cam, fc.perPixelJitterAAScale, px >> 16, px & 0xFFFFu, sample, o, d);
+            tmin = 0.0f; tmax = kMaxRayTravel; startRef = 0u; bestT0 = kMaxRayTravel; bestPrim0 = 0xFFFFFFFFu;
+            return i;
+        }
         uint p = pool.home ? i : queue[i];      // (a compacted pool's ray i is the path at position i)
         uint4 a = pool.s0[p], b = pool.s1[p];
         o = make_float3(asfloat(a.x), asfloat(a.y), asfloat(a.z)); d = make_float3(asfloat(b.x), asfloat(b.y), asfloat(b.z));
@@ -75,6 +81,26 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend(Devic
     __shared__ uint rayBuf[T8_RAYBUF_WORDS];
     __shared__ float2 mineUV[T8_BLOCK];
     t8_extend_body<COUNT, RANGED>(sc, pool, queue, *countPtr, wc, aux, rpc, stack, rayBuf, mineUV, blockIdx.x, gridDim.x);
+}
+
+// k_extend<false> for vertex 0 in place: the batch's pixels instead of a queue
+__global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first(DeviceScene sc, PathPool pool, FirstVertex fv, const uint* __restrict__ countPtr, WaveCounters* wc, TravAux aux, uint rpc) {
+    __shared__ uint2 stack[T8_GROUPS_PER_BLOCK * BVH8_STACK_STRIDE];
+    __shared__ uint rayBuf[T8_RAYBUF_WORDS];
+    __shared__ float2 mineUV[T8_BLOCK];
+    t8_extend_body<false, false, true>(sc, pool, nullptr, *countPtr, wc, aux, rpc, stack, rayBuf, mineUV, blockIdx.x, gridDim.x, &fv);
+}
+
+// ... and behind it, before the task rounds: the stored ray (origin | id, direction | length, as k_generate writes them) of every ray k_extend_first cut into sub-trees — the
+// launch's resolve list. Kept out of k_extend_first's publish: the two array pointers it needs there are two more scalar pairs across the traversal loop
+__global__ void __launch_bounds__(256) k_first_split_rays(PathKernelContext k, PathPool pool, FirstVertex fv, TravAux aux) {
+    const uint n = aux.counts[TRAV_RESOLVE];
+    for (uint i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint p = aux.resolveList[i];
+        uint px, sample; first_vertex_of(fv, p, px, sample);
+        float3 o, d; k.computeCameraRay(px >> 16, px & 0xFFFFu, sample, o, d);
+        pool.s0[p] = make_uint4(asuint(o.x), asuint(o.y), asuint(o.z), px); pool.s1[p] = make_uint4(asuint(d.x), asuint(d.y), asuint(d.z), asuint(0.0f));
+    }
 }
 
 // Task rounds hold hundreds to thousands of sub-trees, far fewer than the launch has quads. A 64-item chunk would put them on count/64 waves (one rank of
@@ -160,8 +186,11 @@ __global__ void __launch_bounds__(256) k_resolve_extend(DeviceScene sc, PathPool
 // Radiance, queues and counters do not depend on the order in which paths are shaded.
 // paths per thread: 4096 per block, one atomic per class and block (with 1024 per block the 32 000 blocks of a 4K bounce spent 0.3 ms queueing on three L2
 // lines)
+// UNIFORM: every path of the launch carries the flags word `uniformFlags` — vertex 0, where it follows from the settings alone (PathKernelContextT::generateState) and pool.s4
+// may not have been written (FirstVertex): only the hit's primitive is read
 #define PT_CLASSIFY_ITEMS 4u
-__global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr, uint* __restrict__ classQ, uint* __restrict__ classCount) {
+template <bool UNIFORM = false>
+__global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr, uint* __restrict__ classQ, uint* __restrict__ classCount, uint uniformFlags) {
     __shared__ uint waveCnt[PT_CLASSIFY_ITEMS][16][3]; __shared__ uint blockBase[3];
     const uint count = *countInPtr, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     // cls: 0 continuing hit, 1 terminating hit, 2 miss, 3 out of range
@@ -172,7 +201,7 @@ __global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __
         p[j] = 0u; cls[j] = 3u;
         if (i < count) {
             p[j] = pool.home ? i : queueIn[i];
-            const uint prim = reinterpret_cast<const uint*>(pool.hit)[4u * (size_t)p[j] + 1u], flags = reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)p[j] + 2u];
+            const uint prim = reinterpret_cast<const uint*>(pool.hit)[4u * (size_t)p[j] + 1u], flags = UNIFORM ? uniformFlags : reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)p[j] + 2u];
             cls[j] = (prim == 0xFFFFFFFFu) ? 2u : (((flags >> kVertexIndexBitCount) & PF_terminateAtNextBounce) ? 1u : 0u);
         }
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(cls[j] == 0u), m1 = __builtin_amdgcn_ballot_w64(cls[j] == 1u), m2 = __builtin_amdgcn_ballot_w64(cls[j] == 2u);
@@ -199,9 +228,11 @@ __global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __
 // PKC: PathKernelContextT<false> (lp types in fp32) or PathKernelContextT<true> (the reference's default build, lp types in binary16)
 // COMPACT: the pool is compacted (PathPool::home): the path at position p of this bounce's array set is written, if it survives, to the position it is appended at in `outPool`'s set;
 // its throughput | radiance word group stays at its home slot, which is also what the extend queue keeps and the shadow queue names
-template <bool MULTI, class PKC, bool NEEAT, bool COMPACT = false>
+// FIRST (with COMPACT): vertex 0 of paths that were not generated (FirstVertex fv): the state is formed, not loaded (PathFirstVertexIO); position == home slot, pool.home is not read
+template <bool MULTI, class PKC, bool NEEAT, bool COMPACT = false, bool FIRST = false>
 __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(PKC k, PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr,
-                                               uint* __restrict__ queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc, const uint* __restrict__ classCount, PathPool outPool) {
+                                               uint* __restrict__ queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc, const uint* __restrict__ classCount, PathPool outPool, FirstVertex fv) {
+    static_assert(!FIRST || (COMPACT && !MULTI && !NEEAT), "vertex 0 in place: the compacted pool of a composed frame");
     static_assert(!COMPACT || !PT_SHADE_PROBE, "the PT_SHADE_PROBE timing builds do not know the compacted pool: take the COMPACT launch out of launch_shade and run with MI355PT_COMPACT_POOL=0");
     const uint count = *countInPtr;
     uint i = blockIdx.x * (uint)PT_SHADE_BLOCK + threadIdx.x;
@@ -216,7 +247,7 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
             const uint nGo = classCount[0], nEnd = classCount[1];
             p = queueIn[i < nGo ? i : (i < nGo + nEnd ? count - 1u - (i - nGo) : count + (i - nGo - nEnd))];
         } else p = COMPACT ? i : queueIn[i];
-        hp = COMPACT ? pool.home[p] : p;
+        hp = (COMPACT && !FIRST) ? pool.home[p] : p;
         uint4 hr = pool.hit[p];
         HitInfo h; h.t = asfloat(hr.x); h.prim = hr.y; h.u = asfloat(hr.z); h.v = asfloat(hr.w);
 #if PT_SHADE_PROBE
@@ -229,7 +260,15 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
         store_path(pool, p, path);
         alive = path.isActive();
 #else
-        if (COMPACT) {
+        if (COMPACT && FIRST) {
+            uint px, sample; first_vertex_of(fv, p, px, sample);
+            const PathFirstVertexIO<PKC> io{k, px, sample};
+            if (h.prim == 0xFFFFFFFFu) { cpath = io.load_all(); k.template HandleMiss<NEEAT>(cpath, cpath.dir, kMaxRayTravel); }
+            else { isHit = true; cpath = io.load_first(); k.template HandleHit<false, NEEAT>(cpath, h, req, nullptr, io); }
+            alive = cpath.isActive();
+            pool.s2[hp] = make_uint4(cpath.pack23[0], cpath.pack23[1], cpath.pack45[0], cpath.pack45[1]);      // every home slot's throughput | radiance is written here before anything reads it
+        }
+        else if (COMPACT) {
             const PathCompactIO io{pool, p, hp};
             if (h.prim == 0xFFFFFFFFu) { cpath = io.load_all(); k.template HandleMiss<NEEAT>(cpath, cpath.dir, kMaxRayTravel); }
             else { isHit = true; cpath = io.load_first(); k.template HandleHit<false, NEEAT>(cpath, h, req, nullptr, io); }
@@ -778,6 +817,14 @@ static const uint T8_TASK_BLOCKS = T8_TASK_BLOCKS_N, T8_RESOLVE_BLOCKS = 256;
 // fewer blocks than the resolve list wants, and a zero count is a valid launch
 static const uint T8_SWEEP_BLOCKS = 2048;
 static inline uint shadow_resolve_grid(uint count) { const uint g = grid_for(count, 256u, T8_SWEEP_BLOCKS); return g < T8_RESOLVE_BLOCKS ? T8_RESOLVE_BLOCKS : g; }
+static void launch_extend_stragglers(const DeviceScene& sc, PathPool pool, uint count, WaveCounters* wc, TravAux aux, hipStream_t st);
+void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, hipStream_t st) {
+    const uint rpc = rays_per_chunk(count);
+    const uint g = grid_for(count, (T8_BLOCK / 64u) * rpc * T8_CHUNKS_PER_WAVE_MIN, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_extend_first, dim3(g), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, aux, rpc);
+    hipLaunchKernelGGL(k_first_split_rays, dim3(T8_RESOLVE_BLOCKS), dim3(256), 0, st, k, pool, fv, aux);
+    launch_extend_stragglers(k.sc, pool, count, wc, aux, st);
+}
 void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged) {
     const uint rpc = rays_per_chunk(count);
     uint g = grid_for(count, (T8_BLOCK / 64u) * rpc * T8_CHUNKS_PER_WAVE_MIN, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
@@ -785,6 +832,9 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
                   else hipLaunchKernelGGL((k_extend<false, true>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, queue, countPtr, wc, aux, rpc); }
     else if (counters) hipLaunchKernelGGL((k_extend<true>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, queue, countPtr, wc, aux, rpc);
     else hipLaunchKernelGGL((k_extend<false>), dim3(g), dim3(T8_BLOCK), 0, st, sc, pool, queue, countPtr, wc, aux, rpc);
+    launch_extend_stragglers(sc, pool, count, wc, aux, st);
+}
+static void launch_extend_stragglers(const DeviceScene& sc, PathPool pool, uint count, WaveCounters* wc, TravAux aux, hipStream_t st) {
     // a small launch holds few stragglers and short ones: two task rounds (split once more, then finish) instead of four — late bounces are
     if (count <= T8_SHORT_TAIL_BELOW) {
         // bound by the host's launch rate, not by the GPU
@@ -830,22 +880,27 @@ void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, 
 }
 // k_classify for a caller in another translation unit (the stable-plane fill pass): classScratch 2 x countIn words, classCount 3 words (zero on entry)
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st) {
-    hipLaunchKernelGGL(k_classify, dim3((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS)), dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount);
+    hipLaunchKernelGGL((k_classify<false>), dim3((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS)), dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u);
 }
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc,
-                  uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool) {
+                  uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool, const FirstVertex* fv) {
+    const FirstVertex fv0 = fv ? *fv : FirstVertex{nullptr, 0u, 0u, 0u};
     const dim3 g((countIn + PT_SHADE_BLOCK - 1) / PT_SHADE_BLOCK), b(PT_SHADE_BLOCK);
     // (scratch: 2 x countIn words, free between the extend and the shadow launches; classCount: 3 words, zeroed with the pass's traversal counters)
     if (PT_SHADE_CLASSES && classScratch) {
-        hipLaunchKernelGGL(k_classify, dim3((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS)), dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount);
+        const dim3 cg((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS));
+        // (vertex 0 in place: the flags word every path would have been generated with)
+        if (fv) hipLaunchKernelGGL((k_classify<true>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, k.generateState(0u, 0u, 0u).flagsAndVertexIndex);
+        else hipLaunchKernelGGL((k_classify<false>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u);
         queueIn = classScratch;
     } else classCount = nullptr;
     // NEE-AT (a local sampling table and / or temporal feedback, pt_set_local_light_sampling) runs its own instantiations: the frames without it keep their
     // kernels unchanged
     const bool neeat = k.sc.lights.LocalSamplingBuffer != nullptr || k.sc.lights.TemporalFeedbackRequired != 0u;
-#define PT_LAUNCH_SHADE(MULTI, PKC, CTX) do { if (neeat) hipLaunchKernelGGL((k_shade<MULTI, PKC, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool); \
-                                              else if (pool.home && !MULTI) hipLaunchKernelGGL((k_shade<false, PKC, false, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool); \
-                                              else hipLaunchKernelGGL((k_shade<MULTI, PKC, false>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool); } while (0)
+#define PT_LAUNCH_SHADE(MULTI, PKC, CTX) do { if (neeat) hipLaunchKernelGGL((k_shade<MULTI, PKC, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
+                                              else if (pool.home && !MULTI && fv) hipLaunchKernelGGL((k_shade<false, PKC, false, true, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
+                                              else if (pool.home && !MULTI) hipLaunchKernelGGL((k_shade<false, PKC, false, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
+                                              else hipLaunchKernelGGL((k_shade<MULTI, PKC, false>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); } while (0)
     if (k.S.useFp16Types) {          // the reference's default build of its lp types (binary16): same context data, the other instantiation of the shading code
         static_assert(sizeof(PathKernelContextT<true>) == sizeof(PathKernelContext), "the two lp builds share one context layout");
         PathKernelContextT<true> k16; __builtin_memcpy(&k16, &k, sizeof(k16));

@@ -23,6 +23,20 @@ __device__ __forceinline__ void wave_add64(unsigned long long v, unsigned long l
     if (lane_id() == 0 && v) atomicAdd(counter, v);
 }
 
+#ifndef PT_SAMPLE_MINOR
+#define PT_SAMPLE_MINOR 1       // 1: the samples of a pixel are neighbours in the path pool (pixel-major), 0: all pixels of sample 0, then of sample 1, ...
+#endif
+// path i of a batch -> its pixel (x << 16 | y, as ownedPixels holds it) and sample index: the one map k_generate and the vertex-0 launches share
+__device__ __forceinline__ void first_vertex_of(const FirstVertex& fv, uint i, uint& px, uint& sample) {
+#if PT_SAMPLE_MINOR
+    // the samples of a pixel are neighbours in the pool: a 64-path chunk is 16 pixels x 4 samples
+    const uint kpx = i / fv.spp, s = i - kpx * fv.spp; px = fv.ownedPixels[kpx];
+#else
+    const uint s = i / fv.numOwned; px = fv.ownedPixels[i - s * fv.numOwned];
+#endif
+    sample = fv.sampleFirst + s;
+}
+
 __device__ __forceinline__ void store_path(const PathPool& pool, uint i, const PathState& p) {
     pool.s0[i] = make_uint4(asuint(p.origin.x), asuint(p.origin.y), asuint(p.origin.z), p.id);
     pool.s1[i] = make_uint4(asuint(p.dir.x), asuint(p.dir.y), asuint(p.dir.z), asuint(p.sceneLength));
@@ -99,6 +113,32 @@ struct PathCompactIO {
         p.pack0 = e.x; p.pack1 = e.y; p.flagsAndVertexIndex = e.z; p.sampleIndex = e.w;
     }
     __device__ __forceinline__ PathState load_all() const { PathState p = load_first(); load_rest(p); return p; }
+    __device__ __forceinline__ void store_front(const PathState&) const {}
+    __device__ __forceinline__ void store_back(const PathState&) const {}
+    __device__ __forceinline__ void store_all(const PathState&) const {}
+};
+
+// ... and of a path that was never stored (FirstVertex, pt_wavefront.h): vertex 0 of a compacted batch. Nothing is loaded: load_first forms the generated state and the camera
+// ray's direction, load_rest forms the state and the ray AGAIN for the origin (px and sample pass through an empty asm so that the compiler cannot keep the first ray's values across
+// the surface phase — the load order of these policies exists for that phase's register pressure); the other words are constants of the frame. Position == home slot, and the stores
+// are PathCompactIO's (k_shade)
+template <class PKC> struct PathFirstVertexIO {
+    static constexpr bool streams = true;
+    const PKC& k; uint px, sample;
+    __device__ __forceinline__ void mark(int) const {}
+    __device__ __forceinline__ PathState load_first() const {
+        PathState p = k.generateState(px >> 16, px & 0xFFFFu, sample); float3 o;
+        k.computeCameraRay(px >> 16, px & 0xFFFFu, sample, o, p.dir);
+        return p;
+    }
+    __device__ __forceinline__ void load_rest(PathState& p) const {
+        uint q = px, s = sample; asm volatile("" : "+v"(q), "+v"(s) :: "memory");
+        const PathState g = k.generate(q >> 16, q & 0xFFFFu, s);
+        p.origin = g.origin; p.id = g.id;
+        p.pack23[0] = g.pack23[0]; p.pack23[1] = g.pack23[1]; p.pack45[0] = g.pack45[0]; p.pack45[1] = g.pack45[1];
+        p.pack0 = g.pack0; p.pack1 = g.pack1; p.flagsAndVertexIndex = g.flagsAndVertexIndex; p.sampleIndex = g.sampleIndex;
+    }
+    __device__ __forceinline__ PathState load_all() const { return k.generate(px >> 16, px & 0xFFFFu, sample); }
     __device__ __forceinline__ void store_front(const PathState&) const {}
     __device__ __forceinline__ void store_back(const PathState&) const {}
     __device__ __forceinline__ void store_all(const PathState&) const {}
