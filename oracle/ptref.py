@@ -22,10 +22,35 @@ def build(quiet=True):
         print(r.stdout)
 
 
-def _load(path):
-    if not os.path.exists(path):
+def _source_digest():
+    """oracle/Makefile's digest of the sources of libptref.so / libptref_lp16.so (its `digest` target), or None where make cannot say."""
+    r = subprocess.run(["make", "-s", "--no-print-directory", "-C", _HERE, "digest"], capture_output=True, text=True)
+    d = r.stdout.strip().split("\n")[-1].strip() if r.returncode == 0 else ""
+    return d if len(d) == 16 else None
+
+
+def _built_digest(L):
+    try: f = L.ptref_source_digest
+    except AttributeError: return ""
+    f.restype = ctypes.c_char_p
+    return (f() or b"").decode()
+
+
+def _load(path, check_sources=False):
+    """dlopen a library of oracle/_ref/, building it first where it is missing. check_sources (the two libptref libraries): the library must have been built from the sources
+    that lie here — by content, since file times say nothing after a checkout or where _ref/ was restored from a copy; one of other sources is rebuilt and loaded again."""
+    want = _source_digest() if check_sources else None
+    if not os.path.exists(path) or (want and not os.path.exists(os.path.join(_HERE, "_ref", ".ptref_src_" + want))):
         build()
-    return ctypes.CDLL(path)
+    L = ctypes.CDLL(path)
+    if want and _built_digest(L) != want:
+        import _ctypes
+        _ctypes.dlclose(L._handle); del L
+        r = subprocess.run(["make", "-B", "-C", _HERE, "_ref/libptref.so", "_ref/libptref_lp16.so"], capture_output=True, text=True)
+        if r.returncode != 0: raise RuntimeError("oracle build failed:\n" + r.stdout + r.stderr)
+        L = ctypes.CDLL(path)
+        if _built_digest(L) != want: raise RuntimeError("%s was not built from the sources in %s (digest %s, sources %s)" % (path, _HERE, _built_digest(L), want))
+    return L
 
 
 _lib = None
@@ -37,7 +62,7 @@ def lib16():
     """The restatement of the reference's DEFAULT build: lp types in 16 bits (oracle/Makefile: -DPT_LP16=1). Same API as lib()."""
     global _lib16
     if _lib16 is None:
-        L = _load(_LIB16)
+        L = _load(_LIB16, check_sources=True)
         L.ptref_create.restype = ctypes.c_void_p
         L.ptref_radiance.restype = ctypes.POINTER(ctypes.c_float)
         L.ptref_num_tris.restype = ctypes.c_uint32
@@ -48,7 +73,7 @@ def lib16():
 def lib():
     global _lib
     if _lib is None:
-        L = _load(_LIB)
+        L = _load(_LIB, check_sources=True)
         L.ptref_create.restype = ctypes.c_void_p
         L.ptref_radiance.restype = ctypes.POINTER(ctypes.c_float)
         for n in ("ptref_hash32", "ptref_hash32_combine", "ptref_sobol", "ptref_owen_scramble", "ptref_f32tof16", "ptref_num_tris"):
@@ -694,6 +719,16 @@ class Oracle:
         prims = np.ascontiguousarray(prims, np.uint32); a = np.ascontiguousarray(uv_dir_cone, np.float32).reshape(-1, 7)
         out = np.zeros((len(prims), 45), np.uint32)
         self.L.ptref_surface_probe(self.h, ctypes.c_uint32(len(prims)), _p(prims), _p(a), _p(out))
+        return out
+
+    def texture_probe(self, rows):
+        """The texture samplers on given rows, float32 [n, 4] — the rows of the device's probe 11 (include/mi355pt_testhooks.h): uint32 [n, 8] = (mode, texture, u, v, four mode words);
+        mode 0 sampleTexture (packed texture word; lambdaNoDims), 1 sample_bilinear (texture index; mip), 2 sample_grad_anisotropic (texture index; gx.xy, gy.xy)."""
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, 8)
+        out = np.zeros((len(rows), 4), np.float32)
+        f = self.L.ptref_texture_probe; f.restype = ctypes.c_uint32
+        bad = f(self.h, ctypes.c_uint32(len(rows)), _p(rows), _p(out))
+        if bad: raise ValueError("texture_probe: mode, texture or mip of row %d is out of range" % (bad - 1))
         return out
 
     def camera_ray(self, px, py, sample_index):

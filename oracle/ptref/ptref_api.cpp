@@ -440,6 +440,12 @@ struct Context {
 
 extern "C" {
 
+// the digest of the sources this library was built from (oracle/Makefile SRCSUM; empty where a build does not say): oracle/ptref.py refuses a library of other sources
+#ifndef PTREF_SOURCE_DIGEST
+#define PTREF_SOURCE_DIGEST ""
+#endif
+const char* ptref_source_digest() { return PTREF_SOURCE_DIGEST; }
+
 void* ptref_create() {
     Context* c = new Context();
     memset(&c->S, 0, sizeof(c->S)); memset(&c->cam, 0, sizeof(c->cam)); memset(&c->ctr, 0, sizeof(c->ctr));
@@ -956,6 +962,25 @@ void ptref_surface_probe(void* h, uint32_t n, const uint32_t* prims, const float
         put3(b.diffuse); *o++ = asuint(b.roughness); put3(b.specular); *o++ = asuint(b.metallic); put3(b.transmission);
         *o++ = asuint(b.diffuseTransmission); *o++ = asuint(b.specularTransmission); *o++ = asuint(b.eta); *o++ = asuint(q.interiorIoR); *o++ = q.neeTriangleLightIndex;
     }
+}
+// the texture samplers on given rows — the layout of the device's probe 11 (include/mi355pt_testhooks.h): (mode, texture, u, v, four mode words) -> float4; mode 0 the material
+// path's sampleTexture (packed texture word, lambdaNoDims), 1 sample_bilinear at an integer mip, 2 sample_grad_anisotropic (gx, gy). Returns 0, or 1 + the first row out of range.
+uint32_t ptref_texture_probe(void* h, uint32_t n, const uint32_t* rows, float* out) {
+    Context* c = (Context*)h; prepare(c);
+    PathTracer svc(c->sc, c->S, c->cam, 0, nullptr);
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t* a = rows + 8 * k; const uint32_t tex = a[0] == 0u ? (a[1] & 0xFFFFu) : a[1];
+        if (a[0] > 2u || tex >= c->sc.textures.size() || (a[0] == 1u && a[4] >= c->sc.textures[tex].mipLevels)) return k + 1u;
+    }
+    #pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < (int64_t)n; k++) {
+        const uint32_t* a = rows + 8 * k; const float2 uv = make_float2(asfloat(a[2]), asfloat(a[3])); float4 r;
+        if (a[0] == 0u) r = svc.sampleTexture(a[1], asfloat(a[4]), uv);
+        else if (a[0] == 1u) r = sample_bilinear(c->sc.textures[a[1]], a[4], uv);
+        else r = sample_grad_anisotropic(c->sc.textures[a[1]], uv, make_float2(asfloat(a[4]), asfloat(a[5])), make_float2(asfloat(a[6]), asfloat(a[7])));
+        out[4 * k] = r.x; out[4 * k + 1] = r.y; out[4 * k + 2] = r.z; out[4 * k + 3] = r.w;
+    }
+    return 0u;
 }
 void ptref_pin_call(int fn, const float* in, unsigned n, float* out) {
     const int ni = kPinArity[fn][0], no = kPinArity[fn][1];

@@ -101,8 +101,11 @@ static inline float4 sample_bilinear(const Texture& t, uint mip, float2 uv) {
     float fx = uv.x * (float)mw - 0.5f, fy = uv.y * (float)mh - 0.5f;
     float flx = floorf(fx), fly = floorf(fy);
     float ax = fx - flx, ay = fy - fly;
-    // keep the integer conversion in range for huge |uv|
-    flx = flx - floorf(flx / (float)mw) * (float)mw; fly = fly - floorf(fly / (float)mh) * (float)mh;
+    // keep the integer conversion in range for huge |uv|: the exact remainder of the integer-valued coordinate by the side. The rounded quotient is off by a few units once
+    // |flx| >= 2^25; the fused x - q * side is exact all the same (a small integer), and a second reduction brings it into [0, side). Below 2^24 the second step subtracts 0.
+    { const float fw = (float)mw, fh = (float)mh;
+      flx = fmaf(-floorf(flx / fw), fw, flx); flx = flx - floorf(flx / fw) * fw;
+      fly = fmaf(-floorf(fly / fh), fh, fly); fly = fly - floorf(fly / fh) * fh; }
     int x0 = (int)flx, y0 = (int)fly;
     float4 a = lerp4(t.texel(mip, x0, y0), t.texel(mip, x0 + 1, y0), ax);
     float4 b = lerp4(t.texel(mip, x0, y0 + 1), t.texel(mip, x0 + 1, y0 + 1), ax);

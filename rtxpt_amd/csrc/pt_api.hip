@@ -1525,7 +1525,15 @@ int32_t pt_probe(pt_context* c, int32_t kind, const void* in, size_t inBytes, vo
     if (!c || !in || !out || !n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
     (void)hipSetDevice(c->device);
     // the surface, environment and alpha-test probes read the scene
-    if (kind == 8 || kind == 9 || kind == 10) { int r = prepare(c); if (r != PT_OK) return r; }
+    if (kind == 8 || kind == 9 || kind == 10 || kind == 11) { int r = prepare(c); if (r != PT_OK) return r; }
+    if (kind == 11) {      // the texture probe indexes the texture table and a texture's mip offsets with what its rows say: hold both to the scene here, the kernel does not
+        if (inBytes < (size_t)n * 32u || outBytes < (size_t)n * 16u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture probe: 8 words in and 4 floats out per row");
+        const uint32_t* a = (const uint32_t*)in;
+        for (uint32_t i = 0; i < n; i++, a += 8) {
+            const uint32_t tex = a[0] == 0u ? (a[1] & 0xFFFFu) : a[1];
+            if (a[0] > 2u || tex >= c->textures.size() || (a[0] == 1u && a[4] >= c->textures[tex].mipLevels)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture probe: mode, texture or mip out of range");
+        }
+    }
     DevBuf<unsigned char> di, dout;
     PT_CHECK_HIP(c, di.upload((const unsigned char*)in, inBytes, c->stream)); PT_CHECK_HIP(c, dout.resize(outBytes));
     PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;

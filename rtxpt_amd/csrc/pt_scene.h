@@ -173,17 +173,25 @@ static inline const float4& tex_texel(const DeviceScene& sc, const TexInfo& t, u
     yi = yi < 0 ? 0 : (yi >= (int)mh ? (int)mh - 1 : yi);
     return sc.texels[t.base + t.mipOffset[mip] + (unsigned long long)yi * mw + (uint)xi];
 }
+// the wrap of an integer-valued texel coordinate on a side that is no power of two: the EXACT remainder of x by the side, in [0, side). The rounded quotient is off by a few
+// units once |x| >= 2^25 (its error is |x| / side * 2^-24), and x - q * side formed with a rounded product then leaves the period — by up to 64 at 2^30. The fused form is exact
+// whenever q is off by a small count (the true x - q * side is a small integer), and one more reduction of that small remainder lands in the period. Below 2^24 the first
+// step already is the remainder and the second subtracts 0: the same floats as the plain form.
+static inline float wrap_texel_npot(float x, float side) {
+    const float r = fmaf(-floorf(x / side), side, x);
+    return r - floorf(r / side) * side;
+}
 static inline float4 sample_bilinear(const DeviceScene& sc, const TexInfo& t, uint mip, float2 uv) {
     uint mw = t.w >> mip; if (mw < 1u) mw = 1u;
     uint mh = t.h >> mip; if (mh < 1u) mh = 1u;
     float fx = uv.x * (float)mw - 0.5f, fy = uv.y * (float)mh - 0.5f;
     float flx = floorf(fx), fly = floorf(fy);
     float ax = fx - flx, ay = fy - fly;
-    // the wrap: flx - floorf(flx / mw) * mw. For a power-of-two side the quotient is an exact scaling: the product with the exact reciprocal (2^-k from 2^k by exponent arithmetic) is the
+    // the wrap: the remainder of flx by the side, flx - floorf(flx / mw) * mw (wrap_texel_npot). For a power-of-two side the quotient is an exact scaling: the product with the exact reciprocal (2^-k from 2^k by exponent arithmetic) is the
     // same float as the correctly rounded division (as in alpha_test_slot); k_shade is bound by its VALU instructions and a trilinear fetch holds four of these divisions
     const float fmw = (float)mw, fmh = (float)mh;
     if (((mw & (mw - 1u)) | (mh & (mh - 1u))) == 0u) { flx = flx - floorf(flx * asfloat(0x7F000000u - asuint(fmw))) * fmw; fly = fly - floorf(fly * asfloat(0x7F000000u - asuint(fmh))) * fmh; }
-    else { flx = flx - floorf(flx / fmw) * fmw; fly = fly - floorf(fly / fmh) * fmh; }
+    else { flx = wrap_texel_npot(flx, fmw); fly = wrap_texel_npot(fly, fmh); }
     int x0 = (int)flx, y0 = (int)fly;
     float4 a = lerp4(tex_texel(sc, t, mip, x0, y0), tex_texel(sc, t, mip, x0 + 1, y0), ax);
     float4 b = lerp4(tex_texel(sc, t, mip, x0, y0 + 1), tex_texel(sc, t, mip, x0 + 1, y0 + 1), ax);
@@ -340,7 +348,7 @@ static inline bool alpha_test_slot(const DeviceScene& sc, uint slot, float u, fl
     const float fmw = (float)mw, fmh = (float)mh;
     if (((mw & (mw - 1u)) | (mh & (mh - 1u))) == 0u) {
         flx = flx - floorf(flx * asfloat(0x7F000000u - asuint(fmw))) * fmw; fly = fly - floorf(fly * asfloat(0x7F000000u - asuint(fmh))) * fmh;
-    } else { flx = flx - floorf(flx / fmw) * fmw; fly = fly - floorf(fly / fmh) * fmh; }
+    } else { flx = wrap_texel_npot(flx, fmw); fly = wrap_texel_npot(fly, fmh); }
     int x0 = (int)flx, y0 = (int)fly, x1 = x0 + 1, y1 = y0 + 1;
     if (x0 < 0) x0 += (int)mw; if (x1 >= (int)mw) x1 -= (int)mw;
     if (y0 < 0) y0 += (int)mh; if (y1 >= (int)mh) y1 -= (int)mh;

@@ -760,6 +760,12 @@ __global__ void __launch_bounds__(64) k_probe(PathKernelContext k, int kind, con
     case 9: { const float* a = in + 4 * i; float* o = out + 3 * i;
         float3 r = k.sc.envEnabled ? env_eval_local(k.sc, make_float3(a[0], a[1], a[2]), a[3]) : make_float3(0.f);
         o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
+    // the texture samplers: (mode, texture, u, v, four mode words) -> float4 (include/mi355pt_testhooks.h; pt_probe has checked texture and mip against the scene)
+    case 11: { const uint* a = reinterpret_cast<const uint*>(in) + 8 * i; const float2 uv = make_float2(asfloat(a[2]), asfloat(a[3])); float4 r;
+        if (a[0] == 0u) r = k.sampleTexture(a[1], asfloat(a[4]), uv);                                                   // the material path: packed texture word, lambdaNoDims
+        else if (a[0] == 1u) r = sample_bilinear(k.sc, k.sc.textures[a[1]], a[4], uv);                                   // one integer mip
+        else r = sample_grad_anisotropic(k.sc, k.sc.textures[a[1]], uv, make_float2(asfloat(a[4]), asfloat(a[5])), make_float2(asfloat(a[6]), asfloat(a[7])));
+        out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w; } break;
     default: break;
     }
 }

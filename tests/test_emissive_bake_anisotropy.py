@@ -4,11 +4,14 @@ formulation of EXT_texture_filter_anisotropic: Px, Py = the gradients' lengths i
 longer gradient and averaged. A reference quirk shapes the result: the bake's two gradients are shortEdge * 2/3 and (longEdge1 + longEdge2) / 3 = -shortEdge / 3 (the UV edges sum to
 zero), i.e. collinear with a 2 : 1 length ratio — so the sampler always takes TWO taps, a sixth of the short edge to either side of the centroid, one level finer than a single tap at
 the longer gradient's LOD (rounds 1 and 2's restatement). On a stretched-UV emitter over a striped texture the two restatements differ by ~20 %; the light table follows the new one."""
+import os, sys
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from rtxpt_amd import scenes
 from oracle import ptref
+from texture_ref import numpy_anisotropic as _numpy_anisotropic      # the float64 N-tap filter (tests/texture_ref.py)
 
 
 def _scene():
@@ -34,25 +37,6 @@ def _unpack_radiance(rec):
     c = rec[3]; col = np.array([c & 0xFF, (c >> 8) & 0xFF, (c >> 16) & 0xFF], np.float64) / 255.0
     lr = int(rec[7]) & 0xFFFF
     return col * (0.0 if lr == 0 else 2.0 ** ((lr - 1) / 65534.0 * 48.0 - 8.0))
-
-
-def _numpy_anisotropic(tex, uv, gx, gy):
-    """Independent float64 evaluation of the N-tap filter (wrap addressing, texel centres at (i + 0.5) / dim, box-filtered mips)."""
-    mips = [tex[..., :3].astype(np.float64)]
-    while mips[-1].shape[0] > 1: a = mips[-1]; mips.append(0.25 * (a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2]))
-    h, w = tex.shape[:2]
-    lx, ly = np.hypot(gx[0] * w, gx[1] * h), np.hypot(gy[0] * w, gy[1] * h)
-    pmax, pmin = max(lx, ly), min(lx, ly); major = np.array(gx if lx >= ly else gy)
-    n = min(max(np.ceil(pmax / pmin), 1.0), 16.0); lod = min(max(np.log2(pmax / n), 0.0), len(mips) - 1.0)
-    def bilinear(m, u, v):
-        hh, ww = m.shape[:2]; fx, fy = u * ww - 0.5, v * hh - 0.5; x0, y0 = int(np.floor(fx)), int(np.floor(fy)); ax, ay = fx - x0, fy - y0
-        g = lambda x, y: m[y % hh, x % ww]
-        return (g(x0, y0) * (1 - ax) + g(x0 + 1, y0) * ax) * (1 - ay) + (g(x0, y0 + 1) * (1 - ax) + g(x0 + 1, y0 + 1) * ax) * ay
-    def trilinear(u, v):
-        l0 = int(np.floor(lod)); f = lod - l0; a = bilinear(mips[l0], u, v)
-        return a if f == 0 or l0 + 1 >= len(mips) else a * (1 - f) + bilinear(mips[l0 + 1], u, v) * f
-    taps = [trilinear(uv[0] + major[0] * ((i + 0.5) / n - 0.5), uv[1] + major[1] * ((i + 0.5) / n - 0.5)) for i in range(int(n))]
-    return np.mean(taps, 0), n, lod
 
 
 def _expected(tex):
