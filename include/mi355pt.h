@@ -857,7 +857,12 @@ int32_t pt_set_tail_paths(pt_context* ctx, uint32_t maxPaths);
    pt_create; not with NEE-AT). It costs memory: five more uint4 arrays per path, 80 bytes on top of the pool's 96.
    A compacted batch whose first pass is a wavefront pass (not the tail kernel) starts without a generation launch: the launches of that pass form a path's vertex-0 state — camera ray,
    pixel, sample index, constants of the frame — where they use it instead of reading back what a generation launch stored (on by default; environment
-   MI355PT_FIRST_VERTEX_IN_PLACE=0 at pt_create: every batch starts with k_generate, as before). Same operations on the same operands: no image depends on it (tests/test_gpu_first_vertex.py). */
+   MI355PT_FIRST_VERTEX_IN_PLACE=0 at pt_create: every batch starts with k_generate, as before). Same operations on the same operands: no image depends on it (tests/test_gpu_first_vertex.py).
+   Every pt_render pass that shades in class order (65 536 paths and more) leaves out the hits of terminating paths — paths shaded at their next hit for that hit's emission term
+   alone — on primitives whose material can neither emit (EmissiveColor exactly zero) nor stand in for an analytic light, and whose hit the nested-dielectric check cannot reject
+   (nestedDielectricsQuality 0, or a thin surface): such a vertex adds no radiance and ends the path, so nothing that is read again depends on it. The hit is still counted in
+   PtFrameStats::hits. Not with NEE-AT (its shading exports a depth per hit) and not in the realtime passes. On by default; environment MI355PT_DROP_INERT_TERMINAL=0 at pt_create:
+   every terminal hit is shaded, as before. No image and no ray or hit count depends on it (tests/test_gpu_inert_terminal.py). */
 int32_t pt_set_fused_traversal(pt_context* ctx, uint32_t mode);
 
 #ifdef __cplusplus

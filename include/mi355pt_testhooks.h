@@ -19,6 +19,12 @@ extern "C" {
  *   mode 2  sample_grad_anisotropic:          word 1 = the texture index, words 4-5 = gx, words 6-7 = gy (floats)
  * pt_probe refuses rows whose mode, texture or mip the scene does not have. uv, lambda and the gradients must be finite: the samplers' data contract. */
 int32_t pt_probe(pt_context* ctx, int32_t kind, const void* in, size_t inBytes, void* out, size_t outBytes, uint32_t n);
+/* The "inert when terminal" table of the prepared scene (rtxpt_amd/csrc/pt_scene.h inert_bits_of; built on the device by k_inert_bits) and what the last pt_render call did with
+ * it. Two bits per global primitive, sixteen primitives a word, primitive p in bits 2 (p % 16) and 2 (p % 16) + 1 of word p / 16: bit 0 = the material can neither emit (all three
+ * components of EmissiveColor exactly zero) nor stand in for an analytic light, bit 1 = thin surface. numPrims (may be null): the scene's primitives; words (may be null):
+ * capacityWords >= (numPrims + 15) / 16 words; lastDropped (may be null): the terminating hits the last pt_render call left unshaded (0 with MI355PT_DROP_INERT_TERMINAL=0, with
+ * NEE-AT, and in frames whose passes are all below the classification threshold). */
+int32_t pt_get_inert_terminal(pt_context* ctx, uint32_t* numPrims, uint32_t* words, uint32_t capacityWords, uint64_t* lastDropped);
 #ifdef __cplusplus
 }
 #endif

@@ -45,7 +45,7 @@ EXPORTS = [
     "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
-TEST_HOOK_EXPORTS = ["pt_probe"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
+TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
 
 
 class PtError(RuntimeError):
@@ -1414,3 +1414,15 @@ class PathTracer:
         out = np.zeros(out_shape, out_dtype)
         self._chk(self.L.pt_probe(self.h, kind, _p(inp), inp.nbytes, _p(out), out.nbytes, out_shape[0]), "pt_probe")
         return out
+
+    def inert_terminal(self):
+        """pt_get_inert_terminal (include/mi355pt_testhooks.h): (bits, dropped) — bits[p] = the two "inert when terminal" bits of global primitive p (1: cannot emit and is no
+        light proxy, 2: thin surface) as the device built them, dropped = the terminating hits the last render() left unshaded. Only on a PathTracer(test_hooks=True)."""
+        if not self.test_hooks: raise RuntimeError("pt_get_inert_terminal is not part of the shipped library: PathTracer(test_hooks=True)")
+        n, dropped = ctypes.c_uint32(), ctypes.c_uint64()
+        self.L.pt_get_inert_terminal.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        self._chk(self.L.pt_get_inert_terminal(self.h, ctypes.byref(n), None, 0, ctypes.byref(dropped)), "pt_get_inert_terminal")
+        words = np.zeros((n.value + 15) // 16, np.uint32)
+        if n.value: self._chk(self.L.pt_get_inert_terminal(self.h, None, _p(words), words.size, None), "pt_get_inert_terminal")
+        prim = np.arange(n.value, dtype=np.uint32)
+        return ((words[prim // 16] >> (2 * (prim % 16))) & 3).astype(np.uint32), int(dropped.value)

@@ -226,7 +226,7 @@ int finalize_geometry(pt_context* c) {
     // BVH_BUILDER_PLOC_OPT: parallel re-insertion passes (MI355X, C3: 8 passes = 1463 Mrays/s in 63 ms, 12 = 1477 in 81 ms, 16 = 1476 in 98 ms; host SAH +
     // re-insertion 1479 in 1824 ms — profiles/r03k_device_reinsertion_sweep.txt)
     { const char* e = getenv("MI355PT_REINSERT_PASSES"); c->bvh.riPasses = e ? (uint)atoi(e) : 12u; }
-    PT_CHECK_HIP(c, c->dShadeTris.resize(c->numTris));
+    PT_CHECK_HIP(c, c->dShadeTris.resize(c->numTris)); PT_CHECK_HIP(c, c->dInertBits.resize(inert_words(c->numTris)));
     // traversal stack tails, one region per pipelined batch (4 x 302 MB of 288 GB)
     if (!c->dTravSpill.p) PT_CHECK_HIP(c, c->dTravSpill.resize(PT_PIPELINE_BATCHES * (size_t)T8_MAX_BLOCKS * T8_GROUPS_PER_BLOCK * T8_SPILL_DEPTH));
     refresh_scene_view(c);
@@ -235,6 +235,7 @@ int finalize_geometry(pt_context* c) {
     PT_CHECK_HIP(c, bvh_build(c->bvh, c->dsc, c->numTris, st));
     PT_CHECK_HIP(c, hipEventRecord(e1, st));
     launch_shade_tris(c->dsc, 0u, c->numTris, c->dShadeTris.p, st);
+    launch_inert_bits(c->dsc, c->numTris, c->dInertBits.p, st);      // (every material edit comes through here: pt_set_materials marks the geometry dirty)
     PT_CHECK_HIP(c, hipStreamSynchronize(st));
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); c->buildMs = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     c->geomDirty = false; c->lightsDirty = true;
@@ -404,6 +405,7 @@ int bake_lights(pt_context* c, bool geometryOnly = false) {
     } else { PT_CHECK_HIP(c, c->dLights.resize(1)); PT_CHECK_HIP(c, c->dLightsEx.resize(1)); }
     if (!keepEnv) PT_CHECK_HIP(c, c->dEnvLookup.upload(c->envLookup, c->stream));
     PT_CHECK_HIP(c, c->dSubInstances.upload(c->subInstances, c->stream));
+    if (c->dInertBits.p) launch_inert_bits(c->dsc, c->numTris, c->dInertBits.p, c->stream);      // the light links were re-baked: the table follows them (pt_scene.h)
     PT_CHECK_HIP(c, hipEventRecord(e1, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); c->lightBakeMs = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -590,6 +592,7 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
     { const char* e = getenv("MI355PT_COMPACT_POOL"); if (e) c->compactPool = atoi(e) != 0; }      // developer A/B / test switch, read at pt_create like the others
     { const char* e = getenv("MI355PT_FIRST_VERTEX_IN_PLACE"); if (e) c->firstVertexInPlace = atoi(e) != 0; }      // (0: k_generate in front of every batch, as before)
     { const char* e = getenv("MI355PT_FUSED_TRAVERSAL"); if (e) c->fusedTraversal = (uint)strtoul(e, nullptr, 10); }
+    { const char* e = getenv("MI355PT_DROP_INERT_TERMINAL"); if (e) c->dropInertTerminal = atoi(e) != 0; }      // developer A/B / test switch (0: every terminal hit is shaded, as before)
     // test switch: iterations after which the tail kernel hands a ray back (0: T8_TAIL_DEFER); a small value sends most rays through the hand-back path
     { const char* e = getenv("MI355PT_TAIL_DEFER"); if (e) c->tailDefer = (uint)strtoul(e, nullptr, 10); }
     memset(&c->dsc, 0, sizeof(c->dsc)); memset(&c->cam, 0, sizeof(c->cam)); memset(&c->bvh, 0, sizeof(c->bvh));
@@ -611,7 +614,7 @@ int32_t pt_destroy(pt_context* c) {
     if (c->bvhAllocated) bvh_free(c->bvh);
     c->dIndices.free(); c->dNormals.free(); c->dTangents.free(); c->dProxyCounters.free(); c->dProxyIndices.free(); c->dEnvLookup.free(); c->dOwned.free(); c->dQueue[0].free(); c->dQueue[1].free();
     c->dPrevPositions.free(); c->dPrevInstances.free(); c->dEmissiveList.free(); c->dEmissiveOffsets.free(); c->dPositions.free(); c->dUvs.free(); c->dGeometries.free(); c->dInstances.free(); c->dSubInstances.free(); c->dSubInstToInstGeom.free();
-    c->dPrimInfo.free(); c->dShadeTris.free(); c->dAlphaPlanes.free(); c->dAlphaPool.free(); c->dMaterials.free(); c->dTexInfos.free(); c->dTexels.free(); c->dEnvCube.free(); c->dEnvCubeSource.free(); c->dEnvImageCube.free(); c->dEnvDirLights.free(); c->dLights.free(); c->dLightsEx.free(); c->dS0.free(); c->dS1.free(); c->dS2.free(); c->dS3.free(); c->dS4.free();
+    c->dPrimInfo.free(); c->dShadeTris.free(); c->dInertBits.free(); c->dAlphaPlanes.free(); c->dAlphaPool.free(); c->dMaterials.free(); c->dTexInfos.free(); c->dTexels.free(); c->dEnvCube.free(); c->dEnvCubeSource.free(); c->dEnvImageCube.free(); c->dEnvDirLights.free(); c->dLights.free(); c->dLightsEx.free(); c->dS0.free(); c->dS1.free(); c->dS2.free(); c->dS3.free(); c->dS4.free();
     c->dHit.free(); c->dS0b.free(); c->dS1b.free(); c->dS3b.free(); c->dS4b.free(); c->dHitb.free(); c->dSq0.free(); c->dSq1.free(); c->dSq2.free(); c->dAccum.free(); c->dScratch4.free(); c->dCounters.free(); c->dTravSpill.free(); c->dTaskQ.free(); c->dTravCounts.free(); c->dResolveList.free(); c->dBestKey.free(); c->dResolveListSh.free(); c->dBestKeySh.free(); c->dTaskQSh.free();
     for (uint b = 1; b < PT_PIPELINE_BATCHES; b++) (void)hipStreamDestroy(c->streams[b]);
     (void)hipStreamDestroy(c->stream); (void)hipHostFree(c->hostCounters);
@@ -1542,6 +1545,18 @@ int32_t pt_probe(pt_context* c, int32_t kind, const void* in, size_t inBytes, vo
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     PT_CHECK_HIP(c, hipGetLastError());
     di.free(); dout.free();
+    return PT_OK;
+}
+int32_t pt_get_inert_terminal(pt_context* c, uint32_t* numPrims, uint32_t* words, uint32_t capacityWords, uint64_t* lastDropped) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    int r = prepare(c); if (r != PT_OK) return r;
+    if (numPrims) *numPrims = c->numTris;
+    if (lastDropped) *lastDropped = c->droppedTerminal;
+    if (words && c->numTris) {
+        if (capacityWords < inert_words(c->numTris)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "inert-terminal table: (numPrims + 15) / 16 words");
+        PT_CHECK_HIP(c, hipMemcpy(words, c->dInertBits.p, 4 * (size_t)inert_words(c->numTris), hipMemcpyDeviceToHost));
+    }
     return PT_OK;
 }
 #endif

@@ -77,6 +77,8 @@ void bvh_free(BvhBuildBuffers& b);
 hipError_t bvh_build(BvhBuildBuffers& b, const DeviceScene& sc, uint numTris, hipStream_t stream);
 // flat per-primitive shading records (pt_scene.h ShadeTri) of primitives [firstPrim, firstPrim + numTris); rebuilt when the geometry is (re)set or its vertices are deformed
 void launch_shade_tris(const DeviceScene& sc, uint firstPrim, uint numTris, ShadeTri* out, hipStream_t stream);
+// the two "inert when terminal" bits of every primitive (pt_scene.h inert_bits_of), inert_words(numTris) words; rebuilt with the records and whenever materials or light links change
+void launch_inert_bits(const DeviceScene& sc, uint numTris, uint* out, hipStream_t stream);
 hipError_t bvh_refit(BvhBuildBuffers& b, const DeviceScene& sc, uint numTris, hipStream_t stream);
 
 } // namespace ptk

@@ -536,6 +536,17 @@ void launch_shade_tris(const DeviceScene& sc, uint firstPrim, uint numTris, Shad
     if (numTris) hipLaunchKernelGGL(k_shade_tris, dim3((numTris + 255u) / 256u), dim3(256), 0, st, sc, firstPrim, numTris, out);
 }
 
+// the "inert when terminal" table (pt_scene.h inert_bits_of): one thread per word of sixteen primitives, each primitive's material through primInfo -> sub-instance. The whole
+// table every time (tens of microseconds): it follows the materials, which have no per-primitive dirty range
+__global__ void __launch_bounds__(256) k_inert_bits(DeviceScene sc, uint numTris, uint* __restrict__ out) {
+    const uint w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= inert_words(numTris)) return;
+    out[w] = inert_word(w, numTris, [&](uint p) -> const PTMaterialData& { return sc.materials[sc.subInstances[sc.primInfo[p].x].GlobalGeometryIndex_PTMaterialDataIndex & 0xFFFFu]; });
+}
+void launch_inert_bits(const DeviceScene& sc, uint numTris, uint* out, hipStream_t st) {
+    if (numTris) hipLaunchKernelGGL(k_inert_bits, dim3((inert_words(numTris) + 255u) / 256u), dim3(256), 0, st, sc, numTris, out);
+}
+
 // ---- cost-driven wide-node assignment on the device (pt_build_wide.h): the inner nodes above the wide tree's leaves are numbered breadth first (one launch per level,
 // children appended with one atomic per block), the dynamic programme runs over the levels bottom-up, the marking top-down. ~3 launches per level of a tree ~50 deep.
 __global__ void __launch_bounds__(256) k_wide_levels(const uint* __restrict__ levelIn, uint nIn, const uint* __restrict__ childL, const uint* __restrict__ childR,

@@ -88,6 +88,11 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 // environment MI355PT_FIRST_VERTEX_IN_PLACE overrides)
 #define PT_FIRST_VERTEX_IN_PLACE 1
 #endif
+#ifndef PT_DROP_INERT_TERMINAL
+// pt_render: k_classify leaves out the hits of terminating paths (PF_terminateAtNextBounce) on primitives that can neither emit nor stand in for an analytic light — their
+// vertex would change nothing anybody reads (pt_wavefront.hip k_classify; environment MI355PT_DROP_INERT_TERMINAL overrides)
+#define PT_DROP_INERT_TERMINAL 1
+#endif
 #ifndef PT_FREE_RUN_BELOW
 // pt_render: once every live batch holds fewer paths than this, the batches stop advancing in lockstep (0: lockstep to the end)
 #define PT_FREE_RUN_BELOW (1u << 22)
@@ -104,6 +109,8 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
     hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
     uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
+    // pt_render's classified passes drop the terminal hits that can add nothing (k_classify, pt_wavefront.hip); droppedTerminal: how many the last pt_render call dropped
+    bool dropInertTerminal = PT_DROP_INERT_TERMINAL != 0; unsigned long long droppedTerminal = 0;
     std::string lastError;
     // host copies of the scene (kept for re-bake / animation)
     std::vector<uint> indices; std::vector<float> positions; std::vector<ptk::float2> uvs; std::vector<uint> normals, tangents;
@@ -128,6 +135,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     DevBuf<float> dPositions; DevBuf<ptk::float2> dUvs; DevBuf<GeometryDesc> dGeometries; DevBuf<InstanceDesc> dInstances;
     DevBuf<SubInstanceData> dSubInstances;
     DevBuf<ptk::AlphaPlane> dAlphaPlanes; DevBuf<unsigned char> dAlphaPool; DevBuf<ptk::ShadeTri> dShadeTris;
+    DevBuf<uint> dInertBits;      // two bits per global primitive: "inert when terminal" (pt_scene.h inert_bits_of, pt_build.hip k_inert_bits)
     DevBuf<ptk::uint2> dSubInstToInstGeom, dPrimInfo; DevBuf<ptk::PTMaterialData> dMaterials; DevBuf<TexInfo> dTexInfos; DevBuf<ptk::float4> dTexels;
     // pt_set_procedural_sky
     bool skyEnabled = false; ptk::ProceduralSkyContext sky; DevBuf<ptk::float4> dSkyTex[4]; DevBuf<ptk::ProceduralSkyContext> dSky;

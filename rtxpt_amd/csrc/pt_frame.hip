@@ -304,7 +304,7 @@ struct RenderFrame {
         // queue order: one launch fewer
         uint* classScratch = t.active >= PT_CLASSIFY_FROM ? reinterpret_cast<uint*>(t.aux.bestKey) : nullptr;
         launch_shade(t.k, pin, t.queue[t.cur], countIn, t.active, t.queue[nxt], &t.wc->extendCount[nxt], t.sq, t.wc, classScratch,
-                     t.aux.counts + PASS_CLASS_OFFSET, t.st, pout, vertex0 ? &fv : nullptr);
+                     t.aux.counts + PASS_CLASS_OFFSET, t.st, pout, vertex0 ? &fv : nullptr, c->dropInertTerminal ? c->dInertBits.p : nullptr);
         const size_t e2 = t.mark(); t.span(e1, e2, 1, t.active);
         t.extendRays += t.active;
         PT_CHECK_HIP(c, hipMemcpyAsync(t.hwc, t.wc, 16, hipMemcpyDeviceToHost, t.st));
@@ -343,6 +343,9 @@ struct RenderFrame {
             uint pc[PASS_COUNTERS]; PT_CHECK_HIP(c, hipMemcpy(pc, t.aux.counts, sizeof(pc), hipMemcpyDeviceToHost));
             fprintf(stderr, "[pass log]   b%u pass %u: %u paths -> extend splits %u / %u / %u / %u sub-trees, %u rays resolved; %u visibility rays next\n",
                     b, t.iterations, t.active, pc[0], pc[1], pc[2], pc[3], pc[TRAV_RESOLVE], nShadow);
+            if (t.active >= PT_CLASSIFY_FROM)
+                fprintf(stderr, "[pass log]   b%u pass %u: classes %u continuing / %u terminating / %u misses, %u inert terminating hits dropped\n",
+                        b, t.iterations, pc[PASS_CLASS_OFFSET], pc[PASS_CLASS_OFFSET + 1], pc[PASS_CLASS_OFFSET + 2], pc[PASS_CLASS_OFFSET + 3]);
         }
         t.active = t.hwc->extendCount[nxt];
         if (fused && nShadow && live(t)) { t.pendingShadow = nShadow; t.shadowRays += nShadow; }      // they ride with the next closest-hit launch
@@ -651,6 +654,7 @@ int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* s
     c->accumCount += count;
     if (feedback) c->fbSamples = count;
     if (stats) f.harvest(*stats, frame.ms());
+    c->droppedTerminal = 0; for (uint b = 0; b < f.numBatches; b++) c->droppedTerminal += f.B[b].hwc->droppedTerminal;
     if (f.passLog) f.log_passes();
     return check_frame_end(c, f.B, f.numBatches,
                            "pt_render: paths still alive at the pass bound (bounceCount + 2 + the nested-dielectric allowance): the bound must be raised");

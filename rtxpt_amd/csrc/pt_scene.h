@@ -133,6 +133,35 @@ struct ShadeTri {
 };
 static_assert(sizeof(ShadeTri) == 128, "ShadeTri must be one 128-byte line");
 
+// "Inert when terminal": what k_classify needs to know of a primitive to drop a hit that only exists for its emission term (a path with PF_terminateAtNextBounce set,
+// pt_wavefront.hip). Two bits per global primitive, sixteen primitives a word (pt_context::dInertBits; 0.7 MB at 2.8 M triangles: it stays in the L2; not a field of DeviceScene, which every traversal kernel carries), built by k_inert_bits
+// next to the ShadeTri records and again whenever the materials or the sub-instances' light links are (re)written.
+//   INERT_NO_LIGHT  the vertex can add no radiance: the material's EmissiveColor is exactly zero in all three components — LP::r3 of it, times any texel, is then never
+//                   > 0 in either lp build, so sd.emission stays zero and neeTriangleLightIndex is not used (loadSurface, pt_path.h) — and the material is no analytic light
+//                   proxy (PTMaterialFlags_EnableAsAnalyticLightProxy clear: neeAnalyticLightIndex stays invalid, HandleHit's proxy term is not evaluated). The colour is
+//                   tested as the material holds it, BEFORE the lp rounding: 1e-9 rounds to zero in binary16 but is > 0 in the fp32 build.
+//   INERT_THIN      PTMaterialFlags_ThinSurface: HandleNestedDielectrics never rejects the hit.
+// The quality is a setting of the frame, so it is not baked in: inert_when_terminal() takes it at launch time. A rejected hit (nestedDielectricsQuality > 0, a material that
+// is not thin) lets the path go on, so such a hit is never inert.
+enum : uint { INERT_NO_LIGHT = 1u, INERT_THIN = 2u, INERT_PRIMS_PER_WORD = 16u };
+static inline uint inert_bits_of(const PTMaterialData& m) {
+    const bool noLight = m.EmissiveColor.x == 0.0f && m.EmissiveColor.y == 0.0f && m.EmissiveColor.z == 0.0f && (m.Flags & PTMaterialFlags_EnableAsAnalyticLightProxy) == 0u;
+    return (noLight ? (uint)INERT_NO_LIGHT : 0u) | ((m.Flags & PTMaterialFlags_ThinSurface) ? (uint)INERT_THIN : 0u);
+}
+static inline bool inert_when_terminal(uint bits, uint nestedDielectricsQuality) { return (bits & INERT_NO_LIGHT) != 0u && (nestedDielectricsQuality == 0u || (bits & INERT_THIN) != 0u); }
+static inline uint inert_words(uint numPrims) { return (numPrims + INERT_PRIMS_PER_WORD - 1u) / INERT_PRIMS_PER_WORD; }
+// word w of the table: primitives [16 w, 16 w + 16) below numPrims; materialOf(p): the material of global primitive p (k_inert_bits: through primInfo and the sub-instance)
+template <class MaterialOf> static inline uint inert_word(uint w, uint numPrims, MaterialOf materialOf) {
+    uint word = 0u;
+    for (uint j = 0; j < INERT_PRIMS_PER_WORD; j++) {
+        const uint p = w * INERT_PRIMS_PER_WORD + j;
+        if (p >= numPrims) break;
+        word |= inert_bits_of(materialOf(p)) << (2u * j);
+    }
+    return word;
+}
+static inline uint inert_bits_at(const uint* __restrict__ table, uint prim) { return (table[prim / INERT_PRIMS_PER_WORD] >> (2u * (prim % INERT_PRIMS_PER_WORD))) & 3u; }
+
 struct DeviceScene {
     const uint* indices; const float* positions; const float2* uvs; const uint* normals; const uint* tangents;
     const float* prevPositions; const InstanceDesc* prevInstances;      // the previous frame's pose (pt_set_motion_history / pt_set_previous_pose), or null: the stable-plane build pass's object motion

@@ -37,6 +37,7 @@ struct WaveCounters {           // device-resident counters / stats (one 256 B b
     unsigned long long shadowValid;     // grouped shadow queue: entries that carry a light sample (= shadow rays in the reference's sense)
     unsigned long long tailExtendRays, tailShadowRays;      // rays the tail kernel traced itself (pt_tail.hip); what it hands back is counted by the launches that trace it
     unsigned long long tailHandedBack[3];                   // paths the tail kernel handed back: extend stragglers, visibility stragglers, still alive at the bounce bound
+    unsigned long long droppedTerminal;                     // terminating hits k_classify dropped as inert (counted in `hits` too)
     // not a counter — the frame's camera for k_extend_first, which reads it where it forms a ray instead of holding twenty more scalars across the traversal loop (it has none to
     // spare): set by the host, it rides with the block's upload at the start of a frame
     FirstVertexCamera firstCamera;
@@ -47,7 +48,7 @@ struct WaveCounters {           // device-resident counters / stats (one 256 B b
 // lower primitive id); occlusion = 0 visible so far / 1 occluded.
 // counts: TRAV_COUNTERS words per traversal launch, one counter per producer so that nothing has to be reset between the launches of a pass —
 //   [0] sub-trees split off by k_extend / k_shadow (task queue 0), [1..3] by task rounds 0..2 (queues 1, 0, 1), [TRAV_RESOLVE] rays to resolve.
-// pt_render keeps one PASS_COUNTERS block per batch — {extend launch, shadow launch, k_classify's three class counts} — and zeroes it once per pass.
+// pt_render keeps one PASS_COUNTERS block per batch — {extend launch, shadow launch, k_classify's three class counts and its count of dropped hits} — and zeroes it once per pass.
 static const uint TRAV_COUNTERS = 5, TRAV_RESOLVE = 4, PASS_COUNTERS = 16, PASS_SHADOW_OFFSET = 5, PASS_CLASS_OFFSET = 10;
 struct TravAux { TravTask* taskQ[2]; uint* counts; uint taskCap; unsigned long long* bestKey; uint* resolveList; const uint* primToSlot; uint maxBlocks; };      // maxBlocks: grid bound of the traversal launches (0: T8_MAX_BLOCKS)
 
@@ -57,11 +58,11 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
 // launch_extend for the first pass of a batch whose paths were NOT generated: ray i is the camera ray of path i of `fv` (no queue, no read of pool.s0 / s1). The rays that are cut into
 // sub-trees get their origin | id and direction | length written to pool.s0 / s1 [i] by a launch over the resolve list (k_first_split_rays), for the task rounds and the resolve pass behind it. The camera: wc->firstCamera. Composed frames only (no counters).
 void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, hipStream_t st);
-// classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (3 words, zero on entry): k_classify's output; null = shade in queue order
+// classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (4 words, zero on entry: three classes and the dropped hits): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr,
                   ShadowQueue sq, WaveCounters* wc, uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool = PathPool{},      // outPool: a compacted pool's other array set (pool.home != nullptr)
-                  const FirstVertex* fv = nullptr);      // fv: vertex 0 of paths that were not generated — k_classify and k_shade form the state (pool.home is not read: position == home slot). Compacted pool, sq.group == 0, no NEE-AT
+                  const FirstVertex* fv = nullptr, const uint* inertBits = nullptr);      // inertBits: pt_scene.h's two bits per primitive — k_classify drops the terminating hits that are inert (null: none; never with NEE-AT or at vertex 0). fv: vertex 0 of paths that were not generated — k_classify and k_shade form the state (pool.home is not read: position == home slot). Compacted pool, sq.group == 0, no NEE-AT
 // a compacted pool's live paths back to their home slots: out.s0 / s1 / s3 / s4 [home[i]] = in...[i] for the *countPtr positions (out: another array set than in's); the queue `in.home` is then an ordinary extend queue
 void launch_uncompact(PathPool in, PathPool out, const uint* countPtr, uint count, hipStream_t st);
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st);      // k_classify: {continuing hit, terminating hit, miss} made contiguous

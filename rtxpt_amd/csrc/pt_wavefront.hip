@@ -188,24 +188,38 @@ __global__ void __launch_bounds__(256) k_resolve_extend(DeviceScene sc, PathPool
 // lines)
 // UNIFORM: every path of the launch carries the flags word `uniformFlags` — vertex 0, where it follows from the settings alone (PathKernelContextT::generateState) and pool.s4
 // may not have been written (FirstVertex): only the hit's primitive is read
+// DROP (pt_render, not vertex 0): the fourth outcome — a terminating hit that is INERT is written into no class and counted in classCount[3]. Such a vertex exists for its
+// emission term alone (HandleHit, pt_path.h: loadSurface<LEAN>, the nested-dielectric check, the emission and the analytic-light-proxy terms, path.terminate()), and on a
+// primitive whose material can neither emit nor stand in for a light, and whose hit the nested-dielectric check cannot reject (inert_when_terminal, pt_scene.h: quality 0
+// or a thin surface), it adds no radiance and ends the path. Why the image cannot change when k_shade never sees it:
+//  - the only stores the vertex would make are the path's own state, which nothing reads again — the path is not appended to the next queue, and the tail kernel, k_uncompact
+//    and the next pass read the pool through that queue — and s2[home], whose radiance words would be rewritten with the value they hold (k_accumulate and the visibility
+//    resolve read those; the throughput words, which volumeTransmittance may scale, die with the path like the ray cone and the scene length);
+//  - no random number is drawn, no queue entry is made, and no counter but the hit count depends on it: k_shade adds classCount[3] to WaveCounters::hits.
+// The launcher asks for it only where nothing else observes a terminal hit: no NEE-AT instantiation (ExportSurface writes a depth for every hit) and not the stable-plane
+// fill pass, which has its own shading kernel. The lane reads the table only once it knows it is a terminating hit: both words it needs for that are loaded anyway.
 #define PT_CLASSIFY_ITEMS 4u
-template <bool UNIFORM = false>
-__global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr, uint* __restrict__ classQ, uint* __restrict__ classCount, uint uniformFlags) {
-    __shared__ uint waveCnt[PT_CLASSIFY_ITEMS][16][3]; __shared__ uint blockBase[3];
+template <bool UNIFORM = false, bool DROP = false>
+__global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __restrict__ queueIn, const uint* __restrict__ countInPtr, uint* __restrict__ classQ, uint* __restrict__ classCount, uint uniformFlags,
+                                                   const uint* __restrict__ inertBits, uint nestedDielectricsQuality) {
+    static_assert(!(UNIFORM && DROP), "vertex 0 has no terminating paths");
+    __shared__ uint waveCnt[PT_CLASSIFY_ITEMS][16][4]; __shared__ uint blockBase[3];
     const uint count = *countInPtr, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    // cls: 0 continuing hit, 1 terminating hit, 2 miss, 3 out of range
+    // cls: 0 continuing hit, 1 terminating hit, 2 miss, 3 terminating hit that is dropped, 4 out of range
     uint p[PT_CLASSIFY_ITEMS], cls[PT_CLASSIFY_ITEMS]; unsigned long long mine[PT_CLASSIFY_ITEMS];
 #pragma unroll
     for (uint j = 0; j < PT_CLASSIFY_ITEMS; j++) {
         const uint i = (blockIdx.x * PT_CLASSIFY_ITEMS + j) * 1024u + threadIdx.x;
-        p[j] = 0u; cls[j] = 3u;
+        p[j] = 0u; cls[j] = 4u;
         if (i < count) {
             p[j] = pool.home ? i : queueIn[i];
             const uint prim = reinterpret_cast<const uint*>(pool.hit)[4u * (size_t)p[j] + 1u], flags = UNIFORM ? uniformFlags : reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)p[j] + 2u];
             cls[j] = (prim == 0xFFFFFFFFu) ? 2u : (((flags >> kVertexIndexBitCount) & PF_terminateAtNextBounce) ? 1u : 0u);
+            if (DROP && cls[j] == 1u && inert_when_terminal(inert_bits_at(inertBits, prim), nestedDielectricsQuality)) cls[j] = 3u;
         }
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(cls[j] == 0u), m1 = __builtin_amdgcn_ballot_w64(cls[j] == 1u), m2 = __builtin_amdgcn_ballot_w64(cls[j] == 2u);
         if (lane == 0u) { waveCnt[j][wave][0] = (uint)__popcll(m0); waveCnt[j][wave][1] = (uint)__popcll(m1); waveCnt[j][wave][2] = (uint)__popcll(m2); }
+        if (DROP) { const unsigned long long m3 = __builtin_amdgcn_ballot_w64(cls[j] == 3u); if (lane == 0u) waveCnt[j][wave][3] = (uint)__popcll(m3); }
         mine[j] = cls[j] == 0u ? m0 : (cls[j] == 1u ? m1 : m2);
     }
     __syncthreads();
@@ -213,6 +227,10 @@ __global__ void __launch_bounds__(1024) k_classify(PathPool pool, const uint* __
         uint tot = 0;
         for (uint j = 0; j < PT_CLASSIFY_ITEMS; j++) for (uint w = 0; w < 16u; w++) { const uint c = waveCnt[j][w][threadIdx.x]; waveCnt[j][w][threadIdx.x] = tot; tot += c; }
         blockBase[threadIdx.x] = tot ? atomicAdd(&classCount[threadIdx.x], tot) : 0u;
+    } else if (DROP && threadIdx.x == 3u) {      // the dropped hits: a count, no place
+        uint tot = 0;
+        for (uint j = 0; j < PT_CLASSIFY_ITEMS; j++) for (uint w = 0; w < 16u; w++) tot += waveCnt[j][w][3];
+        if (tot) atomicAdd(&classCount[3], tot);
     }
     __syncthreads();
 #pragma unroll
@@ -245,8 +263,11 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
         // queueIn = k_classify's arrays: thread i takes the i-th path of the order {continuing, terminating, miss}
         if (classCount) {
             const uint nGo = classCount[0], nEnd = classCount[1];
-            p = queueIn[i < nGo ? i : (i < nGo + nEnd ? count - 1u - (i - nGo) : count + (i - nGo - nEnd))];
+            inRange = i < nGo + nEnd + classCount[2];      // fewer than `count` where k_classify dropped inert terminal hits: those threads leave here
+            p = inRange ? queueIn[i < nGo ? i : (i < nGo + nEnd ? count - 1u - (i - nGo) : count + (i - nGo - nEnd))] : 0u;
         } else p = COMPACT ? i : queueIn[i];
+    }
+    if (inRange) {
         hp = (COMPACT && !FIRST) ? pool.home[p] : p;
         uint4 hr = pool.hit[p];
         HitInfo h; h.t = asfloat(hr.x); h.prim = hr.y; h.u = asfloat(hr.z); h.v = asfloat(hr.w);
@@ -321,7 +342,9 @@ __global__ void __launch_bounds__(PT_SHADE_BLOCK, PT_SHADE_MIN_BLOCKS) k_shade(P
         sq.q2[sslot] = make_float4(req.radiance.x, req.radiance.y, req.radiance.z, 0.f);
         if (NEEAT && sq.q3) sq.q3[sslot] = make_float4(req.fbWeight, req.fbRandom, asfloat(req.fbLight), asfloat(req.rrFix));
     }
-    if (classCount) { if (blockIdx.x == 0u && threadIdx.x == 0u) atomicAdd(&wc->hits, (unsigned long long)classCount[0] + classCount[1]); }
+    if (classCount) {      // (classCount[3]: the terminating hits k_classify dropped — hits all the same)
+        if (blockIdx.x == 0u && threadIdx.x == 0u) { const uint nDropped = classCount[3]; atomicAdd(&wc->hits, ((unsigned long long)classCount[0] + classCount[1]) + nDropped); if (nDropped) atomicAdd(&wc->droppedTerminal, (unsigned long long)nDropped); }
+    }
     else wave_add64(isHit ? 1ull : 0ull, &wc->hits);
 }
 
@@ -886,23 +909,26 @@ void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, 
 }
 // k_classify for a caller in another translation unit (the stable-plane fill pass): classScratch 2 x countIn words, classCount 3 words (zero on entry)
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st) {
-    hipLaunchKernelGGL((k_classify<false>), dim3((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS)), dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u);
+    hipLaunchKernelGGL((k_classify<false>), dim3((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS)), dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u, (const uint*)nullptr, 0u);
 }
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc,
-                  uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool, const FirstVertex* fv) {
+                  uint* classScratch, uint* classCount, hipStream_t st, PathPool outPool, const FirstVertex* fv, const uint* inertBits) {
     const FirstVertex fv0 = fv ? *fv : FirstVertex{nullptr, 0u, 0u, 0u};
     const dim3 g((countIn + PT_SHADE_BLOCK - 1) / PT_SHADE_BLOCK), b(PT_SHADE_BLOCK);
+    // NEE-AT (a local sampling table and / or temporal feedback, pt_set_local_light_sampling) runs its own instantiations: the frames without it keep their
+    // kernels unchanged
+    const bool neeat = k.sc.lights.LocalSamplingBuffer != nullptr || k.sc.lights.TemporalFeedbackRequired != 0u;
     // (scratch: 2 x countIn words, free between the extend and the shadow launches; classCount: 3 words, zeroed with the pass's traversal counters)
     if (PT_SHADE_CLASSES && classScratch) {
         const dim3 cg((countIn + 1024u * PT_CLASSIFY_ITEMS - 1u) / (1024u * PT_CLASSIFY_ITEMS));
         // (vertex 0 in place: the flags word every path would have been generated with)
-        if (fv) hipLaunchKernelGGL((k_classify<true>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, k.generateState(0u, 0u, 0u).flagsAndVertexIndex);
-        else hipLaunchKernelGGL((k_classify<false>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u);
+        // (inert terminal hits are dropped only where nothing else observes a hit: the NEE-AT instantiations export a depth per hit)
+        const bool drop = inertBits && !neeat && k.sc.lights.DepthExport == nullptr;
+        if (fv) hipLaunchKernelGGL((k_classify<true>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, k.generateState(0u, 0u, 0u).flagsAndVertexIndex, (const uint*)nullptr, 0u);
+        else if (drop) hipLaunchKernelGGL((k_classify<false, true>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u, inertBits, (uint)k.S.nestedDielectricsQuality);
+        else hipLaunchKernelGGL((k_classify<false>), cg, dim3(1024), 0, st, pool, queueIn, countInPtr, classScratch, classCount, 0u, (const uint*)nullptr, 0u);
         queueIn = classScratch;
     } else classCount = nullptr;
-    // NEE-AT (a local sampling table and / or temporal feedback, pt_set_local_light_sampling) runs its own instantiations: the frames without it keep their
-    // kernels unchanged
-    const bool neeat = k.sc.lights.LocalSamplingBuffer != nullptr || k.sc.lights.TemporalFeedbackRequired != 0u;
 #define PT_LAUNCH_SHADE(MULTI, PKC, CTX) do { if (neeat) hipLaunchKernelGGL((k_shade<MULTI, PKC, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
                                               else if (pool.home && !MULTI && fv) hipLaunchKernelGGL((k_shade<false, PKC, false, true, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
                                               else if (pool.home && !MULTI) hipLaunchKernelGGL((k_shade<false, PKC, false, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
