@@ -818,7 +818,12 @@ int32_t pt_exchange_planes_host(uint32_t width, uint32_t height, uint32_t rank, 
 
 /* --- probes used by the parity tests and bench.py (not part of the reference seam) --------------------------------- */
 /* closest-hit / any-hit queries through the same BVH + kernels the renderer uses. rays: n x 8 floats (o.xyz,tmin,d.xyz,tmax);
- * closest out: n x 4 (t, prim bits, u, v) with prim 0xFFFFFFFF on miss; visibility out: n x u32 (1 = visible) */
+ * closest out: n x 4 (t, prim bits, u, v) with prim 0xFFFFFFFF on miss; visibility out: n x u32 (1 = visible). A hit has tmin < t < tmax, both strict. tmin must be >= +0
+ * (DXR's rule; the traversal orders nodes by the bit pattern of their entry distance): a negative tmin, -0 or NaN is refused with PT_ERROR_INVALID_ARGUMENT.
+ * Contract of the hit test (both queries, and the renderer's rays): a ray whose origin lies within 8 scene diagonals of the surface it meets finds it — wherever the scene sits,
+ * |coordinates| up to 1e5 included — with t, u, v within a few float32 spacings of the exact values (tests/hit_ref.py states the bounds). Farther out the triangle's padded box, which
+ * does not grow with t, takes hits back once the pad (>= 2e-6 scene diagonals) falls below ~2 float32 spacings of t: from ~30 diagonals on for axis-aligned triangles much smaller
+ * than the scene, from ~100 for triangles as large as the scene (there: 4 % of the aimed rays at 300 diagonals, a quarter at 1 000, half at 10 000). */
 int32_t pt_trace_closest(pt_context* ctx, const float* rays, uint32_t n, float* out, double* kernelMs);
 int32_t pt_trace_visibility(pt_context* ctx, const float* rays, uint32_t n, uint32_t* out, double* kernelMs);
 /* light table / sub-instance read-back; pass NULL pointers to query sizes */

@@ -251,11 +251,15 @@ static inline bool intersect_tri_wt(float3 v0, float3 v1, float3 v2, float3 o, f
 }
 // The second half of the hit definition (see rtxpt_amd/csrc/pt_scene.h for the argument): whether a box above the triangle lets the ray through must not decide the closest
 // hit. A hit only counts if t lies in the slab interval of the triangle's own padded bounding box, computed as every box test above it computes its interval:
-// (plane - o) * inv, inv = ray_safe_rcp(d). Monotone rounding + nested boxes => no conservative BVH can cull an accepted hit. (The watertight test places t within a few
-// roundings of the triangle's plane, the pad is 10 - 100 x wider: the box never takes back what the first half found — tests/test_gpu_watertight.py counts escapes: 0.)
+// (plane - o) * inv, inv = ray_safe_rcp(d). Monotone rounding + nested boxes => no conservative BVH can cull an accepted hit.
+// The pad is absolute: it covers the few float32 spacings by which t and the slab interval disagree only while it is several spacings of the coordinates it is added to (second
+// term of tri_pad: at least 4 spacings of the box's largest |coordinate|; below the first term wherever max|coordinate| <= ~4 scene diagonals) and while the ray's origin is
+// within 8 scene diagonals of the surface (pad >= 2 spacings of t; the contract stated at pt_trace_closest, include/mi355pt.h); beyond that the box takes back hits the first half found. tests/test_hit_reference.py
+// holds this text to an exhaustive float64 restatement (tests/hit_ref.py).
 static inline float tri_pad(float3 mn, float3 mx, float scenePad) {
     float3 e = mx - mn;
-    return 2e-5f * fmaxf_(e.x, fmaxf_(e.y, e.z)) + scenePad;
+    const float m = fmaxf_(fmaxf_(fmaxf_(fabsf(mn.x), fabsf(mx.x)), fmaxf_(fabsf(mn.y), fabsf(mx.y))), fmaxf_(fabsf(mn.z), fabsf(mx.z)));
+    return fmaxf_(2e-5f * fmaxf_(e.x, fmaxf_(e.y, e.z)) + scenePad, 4.0f * 1.1920929e-7f * m);      // 4 float32 spacings (2^-23 relative) of the box's largest |coordinate|
 }
 static inline float scene_pad(float3 smn, float3 smx) { return 2e-6f * length(smx - smn); }
 static inline bool tri_box_accepts(const Triangle& tr, float3 o, float3 inv, float t) {

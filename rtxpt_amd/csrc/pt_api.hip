@@ -1462,6 +1462,13 @@ int32_t pt_device_radiance(pt_context* c, void** p) { if (!c || !p || !c->width)
 
 static int trace_probe(pt_context* c, const float* rays, uint32_t n, float* outClosest, uint32_t* outVisible, double* kernelMs) {
     if (!c || !rays || !n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
+    // TMin is non-negative (DXR's rule for TraceRay; every ray the renderer forms obeys it). The traversal relies on it: a node's entry distance is max(slab, tmin) >= +0, and
+    // the front-to-back order of the children is taken from its BIT PATTERN (pt_traverse8p.h). A negative one (-0 included) orders behind "not hit", and the push that follows
+    // indexes the stack with a wrapped count — a store far outside the stack's tail in global memory. Refused here (a NaN too), before anything reaches the device.
+    for (uint32_t i = 0; i < n; i++) {
+        const float tmin = rays[8 * (size_t)i + 3];
+        if (!(tmin >= 0.0f) || std::signbit(tmin)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_closest / pt_trace_visibility: ray " + std::to_string(i) + " has tmin < 0 (or -0, or NaN); tmin must be >= +0");
+    }
     (void)hipSetDevice(c->device);
     int r = prepare(c); if (r != PT_OK) return r;
     DevBuf<ptk::float4> dr, dc; DevBuf<uint> dv;

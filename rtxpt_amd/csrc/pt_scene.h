@@ -319,11 +319,22 @@ static inline bool intersect_tri_wt(float3 v0, float3 v1, float3 v2, float3 o, f
 // only counts if it lies inside the triangle's own padded bounding box AS THE RAY SEES IT: the slab interval [tn, tf] of that box, computed with exactly the arithmetic every BVH
 // node above it uses ((plane - o) * inv with inv = ray_safe_rcp(d), correctly rounded), must contain t. Rounding is monotone, every ancestor box contains this box (pad grows with
 // the extent, see tri_pad / pad_box), hence every ancestor's interval contains [tn, tf] and therefore t: no conservative BVH over these boxes can cull an accepted hit, and the
-// result equals the exhaustive loop bit for bit. (The watertight test places t within a few
-// roundings of the triangle's plane, the pad is 10 - 100 x wider: the box never takes back what the first half found — tests/test_gpu_watertight.py counts escapes: 0.)
+// result equals the exhaustive loop bit for bit.
+// What the pad has to cover: t of the first half and tn / tf of the slab arithmetic come by different routes, each with an error of a few float32 spacings of |plane - o| along
+// the dominant axis. The pad is absolute, so it covers them only while it is several spacings of the COORDINATES it is added to — fl(mn - pad) absorbs a pad below half a
+// spacing of |mn|, and on the axis where an axis-aligned triangle has no extent the "padded" box was then 0 or 1 spacing thick and threw away about half of the hits (a unit
+// quad at z = 1000: 95 439 of 200 000). Hence the second term: never less than 4 spacings of the box's largest |coordinate|. It is below the first term wherever
+// max|coordinate| <= ~4 scene diagonals (2e-6 * diagonal >= 4.8e-7 * max|coordinate|), i.e. for every scene that sits near its origin the pads are the floats they were; and it
+// is monotone under box containment, so the boxes stay nested.
+// Where it stops: the pad does not grow with t. A ray whose origin lies far from the scene carries errors of a few spacings of t on both routes; the box keeps the hit while the
+// pad is at least ~2 spacings of t, t <= 2^22 pad, and with pad >= 2e-6 scene diagonals that is 8 scene diagonals of travel for any geometry (the contract stated at
+// pt_trace_closest, include/mi355pt.h). Beyond it the box does take back hits the first half found: small axis-aligned triangles from ~30 diagonals on,
+// triangles as large as the scene from ~100. Up to the contract's distance tests/test_hit_reference.py and
+// tests/test_gpu_hit_reference.py hold the whole hit test — hits, misses, t, barycentrics, interval ends, visibility — to an exhaustive float64 restatement (tests/hit_ref.py).
 static inline float tri_pad(float3 mn, float3 mx, float scenePad) {
     float3 e = mx - mn;
-    return 2e-5f * fmaxf_(e.x, fmaxf_(e.y, e.z)) + scenePad;
+    const float m = fmaxf_(fmaxf_(fmaxf_(fabsf(mn.x), fabsf(mx.x)), fmaxf_(fabsf(mn.y), fabsf(mx.y))), fmaxf_(fabsf(mn.z), fabsf(mx.z)));
+    return fmaxf_(2e-5f * fmaxf_(e.x, fmaxf_(e.y, e.z)) + scenePad, 4.0f * 1.1920929e-7f * m);      // 4 float32 spacings (2^-23 relative) of the box's largest |coordinate|
 }
 static inline float scene_pad(float3 smn, float3 smx) { return 2e-6f * length(smx - smn); }
 static inline bool tri_box_accepts(const TriRecord& tr, float3 o, float3 inv, float t) {

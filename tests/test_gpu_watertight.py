@@ -9,7 +9,9 @@ Measurement on a closed, shared-vertex icosphere (20 480 triangles under a rotat
     the worst case, where both neighbours see an edge function of 0 +- rounding;
   * the same with the target moved off the edge by k fp32 spacings of the coordinate;
   * 10^8 rays aimed at uniformly random surface points: what an image sees.
-The device and the oracle share the definition and must agree ray for ray (asserted). Every count must be ZERO (asserted); the numbers go to profiles/ (r05*_watertight.txt)."""
+The device and the oracle share the definition and must agree ray for ray (asserted). Every count must be ZERO (asserted); the numbers go to profiles/ (r05*_watertight.txt).
+This is one icosphere near the origin, and device and oracle share one text: scenes far from the origin, far ray origins, t / u / v and the interval ends against an independent
+float64 reference are in tests/test_hit_reference.py and tests/test_gpu_hit_reference.py."""
 import numpy as np
 import pytest
 
