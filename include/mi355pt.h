@@ -863,6 +863,10 @@ int32_t pt_set_tail_paths(pt_context* ctx, uint32_t maxPaths);
    A compacted batch whose first pass is a wavefront pass (not the tail kernel) starts without a generation launch: the launches of that pass form a path's vertex-0 state — camera ray,
    pixel, sample index, constants of the frame — where they use it instead of reading back what a generation launch stored (on by default; environment
    MI355PT_FIRST_VERTEX_IN_PLACE=0 at pt_create: every batch starts with k_generate, as before). Same operations on the same operands: no image depends on it (tests/test_gpu_first_vertex.py).
+   That pass's first traversal launch traces the camera rays as packets: the rays of 32 consecutive paths walk the tree together on one stack per wave, and the few packets that
+   take more than 128 steps are traced again ray by ray behind it (on by default; environment MI355PT_FIRST_VERTEX_PACKETS=0 at pt_create: every camera ray is traced on its own, as
+   before; MI355PT_PACKET_STEP_CAP / MI355PT_PACKET_STACK, also read at pt_create, set the step cap and the stack entries of a packet — test switches). The closest hit does not
+   depend on the order in which triangles are looked at: same hits, same image, same counts (tests/test_gpu_packet_first.py).
    Every pt_render pass that shades in class order (65 536 paths and more) leaves out the hits of terminating paths — paths shaded at their next hit for that hit's emission term
    alone — on primitives whose material can neither emit (EmissiveColor exactly zero) nor stand in for an analytic light, and whose hit the nested-dielectric check cannot reject
    (nestedDielectricsQuality 0, or a thin surface): such a vertex adds no radiance and ends the path, so nothing that is read again depends on it. The hit is still counted in

@@ -591,6 +591,10 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
     // developer A/B switch (pt_set_fused_traversal)
     { const char* e = getenv("MI355PT_COMPACT_POOL"); if (e) c->compactPool = atoi(e) != 0; }      // developer A/B / test switch, read at pt_create like the others
     { const char* e = getenv("MI355PT_FIRST_VERTEX_IN_PLACE"); if (e) c->firstVertexInPlace = atoi(e) != 0; }      // (0: k_generate in front of every batch, as before)
+    { const char* e = getenv("MI355PT_FIRST_VERTEX_PACKETS"); if (e) c->firstVertexPackets = atoi(e) != 0; }      // (0: k_extend_first, one ray per lane pair, as before)
+    // test switches: the steps after which a packet goes to the per-ray kernel, and the entries of its stack (small values send most packets there)
+    { const char* e = getenv("MI355PT_PACKET_STEP_CAP"); if (e) c->packetStepCap = (uint)strtoul(e, nullptr, 10); }
+    { const char* e = getenv("MI355PT_PACKET_STACK"); if (e) c->packetStack = (uint)strtoul(e, nullptr, 10); }
     { const char* e = getenv("MI355PT_FUSED_TRAVERSAL"); if (e) c->fusedTraversal = (uint)strtoul(e, nullptr, 10); }
     { const char* e = getenv("MI355PT_DROP_INERT_TERMINAL"); if (e) c->dropInertTerminal = atoi(e) != 0; }      // developer A/B / test switch (0: every terminal hit is shaded, as before)
     // test switch: iterations after which the tail kernel hands a ray back (0: T8_TAIL_DEFER); a small value sends most rays through the hand-back path
@@ -615,7 +619,7 @@ int32_t pt_destroy(pt_context* c) {
     c->dIndices.free(); c->dNormals.free(); c->dTangents.free(); c->dProxyCounters.free(); c->dProxyIndices.free(); c->dEnvLookup.free(); c->dOwned.free(); c->dQueue[0].free(); c->dQueue[1].free();
     c->dPrevPositions.free(); c->dPrevInstances.free(); c->dEmissiveList.free(); c->dEmissiveOffsets.free(); c->dPositions.free(); c->dUvs.free(); c->dGeometries.free(); c->dInstances.free(); c->dSubInstances.free(); c->dSubInstToInstGeom.free();
     c->dPrimInfo.free(); c->dShadeTris.free(); c->dInertBits.free(); c->dAlphaPlanes.free(); c->dAlphaPool.free(); c->dMaterials.free(); c->dTexInfos.free(); c->dTexels.free(); c->dEnvCube.free(); c->dEnvCubeSource.free(); c->dEnvImageCube.free(); c->dEnvDirLights.free(); c->dLights.free(); c->dLightsEx.free(); c->dS0.free(); c->dS1.free(); c->dS2.free(); c->dS3.free(); c->dS4.free();
-    c->dHit.free(); c->dS0b.free(); c->dS1b.free(); c->dS3b.free(); c->dS4b.free(); c->dHitb.free(); c->dSq0.free(); c->dSq1.free(); c->dSq2.free(); c->dAccum.free(); c->dScratch4.free(); c->dCounters.free(); c->dTravSpill.free(); c->dTaskQ.free(); c->dTravCounts.free(); c->dResolveList.free(); c->dBestKey.free(); c->dResolveListSh.free(); c->dBestKeySh.free(); c->dTaskQSh.free();
+    c->dHit.free(); c->dS0b.free(); c->dS1b.free(); c->dS3b.free(); c->dS4b.free(); c->dHitb.free(); c->dSq0.free(); c->dSq1.free(); c->dSq2.free(); c->dAccum.free(); c->dScratch4.free(); c->dCounters.free(); c->dTravSpill.free(); c->dTaskQ.free(); c->dTravCounts.free(); c->dResolveList.free(); c->dFirstLeftover.free(); c->dBestKey.free(); c->dResolveListSh.free(); c->dBestKeySh.free(); c->dTaskQSh.free();
     for (uint b = 1; b < PT_PIPELINE_BATCHES; b++) (void)hipStreamDestroy(c->streams[b]);
     (void)hipStreamDestroy(c->stream); (void)hipHostFree(c->hostCounters);
     delete c;

@@ -161,6 +161,7 @@ struct RenderBatch : Batch {
     uint pendingShadow = 0; TravAux auxSh;                          // fused traversal launches (enable_fused)
     PathPool poolSet[2]; uint set = 0; bool compact = false;        // the compacted pool (enable_compact_pool)
     bool firstInPlace = false;                                      // no k_generate: the first pass forms the vertex-0 state itself (enable_first_vertex_in_place)
+    FirstPackets packets = {nullptr, nullptr, 0u, 0u, 0u};          // ... and traces its camera rays as packets (leftover == nullptr: one by one)
     bool timed = false; Events marks; size_t t0 = 0, t1 = 0;
     struct Span { size_t a, b; int kind; uint items; }; std::vector<Span> spans;      // kind: 0 extend, 1 shade, 2 shadow, 3 tail
     size_t mark() { return timed ? marks.mark(st) : 0; }
@@ -211,7 +212,7 @@ struct RenderFrame {
         const bool neeatShade = c->dsc.lights.LocalSamplingBuffer != nullptr || c->dsc.lights.TemporalFeedbackRequired != 0u;
         if (composed && c->compactPool && !neeatShade && !feedback) {
             int32_t r = enable_compact_pool(); if (r != PT_OK) return r;
-            if (c->firstVertexInPlace) enable_first_vertex_in_place();
+            if (c->firstVertexInPlace) { enable_first_vertex_in_place(); if (c->firstVertexPackets) { r = enable_first_vertex_packets(); if (r != PT_OK) return r; } }
         }
         return PT_OK;
     }
@@ -268,6 +269,19 @@ struct RenderFrame {
             t.hwc->firstCamera.cam = t.k.cam; t.hwc->firstCamera.perPixelJitterAAScale = t.k.S.perPixelJitterAAScale;      // (uploaded with the block by start())
         }
     }
+    // Vertex 0 as packets (ptk::FirstPackets, pt_traverse8k.h). The camera rays of 32 consecutive paths — 8 x 1 pixels x 4 samples of an 8 x 8 block of the owned-pixel list at
+    // 4 spp — walk almost the same nodes, and one ray per lane pair repeats the per-ray bookkeeping 32 times over. k_extend_first_packets walks them on one stack per wave;
+    // the packets over the step cap leave their rays on the batch's slice of dFirstLeftover (count: word PASS_LEFTOVER of the pass's counter block, zeroed with it), and
+    // k_extend_first's loop traces those behind it, straggler machinery included. Same hits at the same positions: nothing else of the pass knows.
+    int32_t enable_first_vertex_packets() {
+        PT_CHECK_HIP(c, c->dFirstLeftover.resize(c->poolCapacity));
+        for (uint b = 0; b < numBatches; b++) {
+            RenderBatch& t = B[b]; if (!t.firstInPlace) continue;
+            t.packets = FirstPackets{c->dFirstLeftover.p + t.base, t.aux.counts + PASS_LEFTOVER, t.total,
+                                     c->packetStepCap ? c->packetStepCap : (uint)T8_PACKET_STEP_CAP, c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK};
+        }
+        return PT_OK;
+    }
     int32_t start() {
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b];
@@ -294,7 +308,7 @@ struct RenderFrame {
         // (pass 0 of a batch has no visibility rays pending)
         const bool vertex0 = t.firstInPlace && t.iterations == 0u;
         const FirstVertex fv{c->dOwned.p + t.pixFirst, t.numPix, first, count};
-        if (vertex0) launch_extend_first(t.k, pin, fv, countIn, t.active, t.wc, t.aux, t.st);
+        if (vertex0) launch_extend_first(t.k, pin, fv, countIn, t.active, t.wc, t.aux, t.packets, t.st);
         else if (t.pendingShadow) {
             launch_trace_pair(t.sc, pin, t.queue[t.cur], countIn, t.active, t.sq, &t.wc->shadowCount, t.pendingShadow, t.wc, t.aux, t.auxSh, t.st);
             t.pendingShadow = 0;
@@ -343,6 +357,8 @@ struct RenderFrame {
             uint pc[PASS_COUNTERS]; PT_CHECK_HIP(c, hipMemcpy(pc, t.aux.counts, sizeof(pc), hipMemcpyDeviceToHost));
             fprintf(stderr, "[pass log]   b%u pass %u: %u paths -> extend splits %u / %u / %u / %u sub-trees, %u rays resolved; %u visibility rays next\n",
                     b, t.iterations, t.active, pc[0], pc[1], pc[2], pc[3], pc[TRAV_RESOLVE], nShadow);
+            if (t.packets.leftover && t.iterations == 0u)
+                fprintf(stderr, "[pass log]   b%u pass 0: %u of %u camera rays left over by the packets (step cap %u, stack %u)\n", b, pc[PASS_LEFTOVER], t.active, t.packets.stepCap, t.packets.stackBound);
             if (t.active >= PT_CLASSIFY_FROM)
                 fprintf(stderr, "[pass log]   b%u pass %u: classes %u continuing / %u terminating / %u misses, %u inert terminating hits dropped\n",
                         b, t.iterations, pc[PASS_CLASS_OFFSET], pc[PASS_CLASS_OFFSET + 1], pc[PASS_CLASS_OFFSET + 2], pc[PASS_CLASS_OFFSET + 3]);

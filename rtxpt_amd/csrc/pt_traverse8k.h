@@ -1,0 +1,220 @@
+// mi355pt — BVH8 traversal of camera rays as PACKETS: the 32 rays of a wave walk the tree together on ONE stack. The lane-pair layout of pt_traverse8p.h stays — lane h of
+// a pair tests children 4h .. 4h + 3 of the current node and triangle h of a leaf, for the pair's own ray — but the current node, the stack and the stack pointer are
+// wave-uniform, so a step has no child ranking per ray, no per-ray stack, no pop loop and no refill.
+//
+// Why the result is the single-ray kernel's, bit for bit: the closest hit is the minimum of (t, primitive) over the triangles a ray ACCEPTS, and acceptance is a property of
+// the ray and the triangle alone (the watertight test, tri_box_accepts, the alpha test: pt_scene.h) — the tree only decides which triangles are looked at. Every expression
+// below that decides acceptance, and the slab test that decides what a ray enters, is traverse8_pairs' expression on the same operands. A packet looks at a SUPERSET of what
+// each of its rays would look at alone:
+//  - a child is visited if ANY ray's own slab test (against its own best t) enters it;
+//  - a stack entry carries the MINIMUM entry distance over the rays that entered it, and is dropped unvisited only if that exceeds the LARGEST best t of the packet — then
+//    every ray that entered it would have dropped it (its own entry distance is no smaller, its own best t no larger);
+//  - a leaf's triangles are tested by every ray of the packet.
+// Order and pruning change cost, never results.
+//
+// A packet that needs more than `stepCap` steps, or a deeper stack than `stackBound`, commits nothing: its rays go to a leftover list (one atomic per packet) that the
+// per-ray kernel traces from scratch behind this launch (pt_wavefront.hip launch_extend_first).
+#pragma once
+#include "pt_traverse8p.h"
+#include "pt_wavefront.h"
+
+namespace ptk {
+
+
+#define DPP_ROW_ROR(n) (0x120 + (n))
+__device__ __forceinline__ uint t8k_min(uint a, uint b) { return a < b ? a : b; }
+__device__ __forceinline__ uint t8k_max(uint a, uint b) { return a > b ? a : b; }
+__device__ __forceinline__ uint t8k_uniform(uint v) { return (uint)__builtin_amdgcn_readfirstlane((int)v); }
+
+// Ray: void form(uint i, float3& o, float3& d) — ray i of the launch (every lane of a pair forms its pair's ray). Dst: void commit(uint i, const HitInfo&), one lane per ray.
+template <class Ray, class Dst>
+__device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const uint count, uint2* stackBase, float2* mineUV, Ray form, Dst commit, const FirstPackets pk, uint* overflowFlag) {
+    static_assert(T8_LANES == 2u, "traverse8_packets keeps the lane-pair layout");
+    const uint lane = threadIdx.x & 63u, h = lane & 1u;
+    const uint wavesPerBlock = T8_BLOCK / 64u;
+    const uint waveId = t8k_uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), numWaves = t8k_uniform(gridDim.x * wavesPerBlock);
+    uint2* stack = stackBase + t8k_uniform(threadIdx.x >> 6) * T8_PACKET_STACK;
+    const char* nodesBase = reinterpret_cast<const char*>(sc.nodes8);
+    const char* trisBase = reinterpret_cast<const char*>(sc.tris);
+    const uint laneChildOff = 16u + 48u * h, laneTriOff = 48u * h;
+    const uint INF_BITS = 0x7F800000u;
+    const float tmin = 0.f, tmax = kMaxRayTravel;
+    // after the reduction over the packet, lane L answers for ONE child: 4h + kSel (a row of sixteen lanes holds every child twice)
+    const uint kSel = (lane >> 1) & 3u, myChild = 4u * h + kSel;
+    const uint stepCap = t8k_uniform(pk.stepCap), stackBound = t8k_uniform(pk.stackBound < T8_PACKET_STACK ? pk.stackBound : T8_PACKET_STACK);
+    const uint numPackets = (count + T8_PACKET_RAYS - 1u) / T8_PACKET_RAYS;
+
+    for (uint p = waveId; p < numPackets; p += numWaves) {
+        const uint i0 = p * T8_PACKET_RAYS, i = i0 + (lane >> 1);
+        const bool valid = i < count;      // (the launch's last packet may be short: its idle pairs form the last ray and enter nothing)
+        float3 o; float Sx, Sy, ix, iy, iz; uint axes, selN, selF;
+        {   float3 rd; form(valid ? i : count - 1u, o, rd);
+            // as the chunk refill of traverse8_pairs forms them
+            ix = t8_rcp_dir(rd.x); iy = t8_rcp_dir(rd.y); iz = t8_rcp_dir(rd.z);
+            const float adx = fabsf(rd.x), ady = fabsf(rd.y), adz = fabsf(rd.z);
+            const bool rk2 = adz > adx && adz > ady, rk1 = !rk2 && ady > adx;
+            const float rSz = rk2 ? iz : (rk1 ? iy : ix);
+            Sx = (rk2 ? rd.x : (rk1 ? rd.z : rd.y)) * rSz; Sy = (rk2 ? rd.y : (rk1 ? rd.x : rd.z)) * rSz;
+            axes = rk2 ? (0u | (16u << 8) | (32u << 16)) : (rk1 ? (32u | (0u << 8) | (16u << 16)) : (16u | (32u << 8) | (0u << 16)));
+            const uint nxb = ix < 0.f ? 3u : 0u, fxb = ix < 0.f ? 0u : 3u, nyb = iy < 0.f ? 4u : 1u, fyb = iy < 0.f ? 1u : 4u, nzb = iz < 0.f ? 5u : 2u, fzb = iz < 0.f ? 2u : 5u;
+            selN = nxb | (nyb << 8) | (nzb << 16) | (fxb << 24); selF = fyb | (fzb << 8);
+        }
+        // (an idle pair's best t is negative: its slab intervals are empty, it enters nothing, and no triangle is tested for it)
+        float bestT = valid ? tmax : -1.0f; uint bestPrim = 0xFFFFFFFFu, minePrim = 0xFFFFFFFFu;
+        // wave-uniform: the node in hand, the stack pointer, the steps so far, the largest best t of the packet (as bits: t > 0)
+        uint cur = sc.rootIsValid ? 0u : BVH_EMPTY, sp = 0u, steps = 0u, maxBest = __float_as_uint(tmax);
+        bool handOff = false;
+
+        for (;;) {
+            if (cur == BVH_EMPTY) {
+                while (sp > 0u) {
+                    sp--;
+                    const uint2 e = stack[sp];
+                    const uint er = t8k_uniform(e.x), et = t8k_uniform(e.y);
+                    if (__uint_as_float(et) <= __uint_as_float(maxBest)) { cur = er; break; }
+                }
+                if (cur == BVH_EMPTY) break;
+            }
+            if (++steps > stepCap) { handOff = true; break; }
+
+            if (!(cur & BVH_LEAF_BIT)) {
+                // ---- inner node: lane h tests children 4h .. 4h + 3 for its pair's ray
+                const uint nodeOff = cur * 128u;
+                const u32x4 hdr = *reinterpret_cast<const u32x4*>(nodesBase + nodeOff);
+                const u32x4 c0 = *reinterpret_cast<const u32x4*>(nodesBase + (nodeOff + laneChildOff));
+                const u32x4 c1 = *reinterpret_cast<const u32x4*>(nodesBase + (nodeOff + laneChildOff + 16u));
+                const u32x4 c2 = *reinterpret_cast<const u32x4*>(nodesBase + (nodeOff + laneChildOff + 32u));
+                const f32x4 scl = *reinterpret_cast<const f32x4*>(nodesBase + (nodeOff + 112u));
+                const float nx = __uint_as_float(hdr.x), ny = __uint_as_float(hdr.y), nz = __uint_as_float(hdr.z);
+                const float sx = scl.x, sy = scl.y, sz = scl.z;
+                auto slab = [&](uint q0, uint q1, float& tn, float& tf) {
+                    const uint N = __builtin_amdgcn_perm(q1, q0, selN), F = __builtin_amdgcn_perm(q1, q0, selF);
+                    f32x2 px = __builtin_elementwise_fma((f32x2){(float)(N & 0xFFu), (float)(N >> 24)}, (f32x2){sx, sx}, (f32x2){nx, nx});
+                    f32x2 py = __builtin_elementwise_fma((f32x2){(float)((N >> 8) & 0xFFu), (float)(F & 0xFFu)}, (f32x2){sy, sy}, (f32x2){ny, ny});
+                    f32x2 pz = __builtin_elementwise_fma((f32x2){(float)((N >> 16) & 0xFFu), (float)((F >> 8) & 0xFFu)}, (f32x2){sz, sz}, (f32x2){nz, nz});
+                    f32x2 tx = (px - (f32x2){o.x, o.x}) * (f32x2){ix, ix}, ty = (py - (f32x2){o.y, o.y}) * (f32x2){iy, iy}, tz = (pz - (f32x2){o.z, o.z}) * (f32x2){iz, iz};
+                    tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
+                    tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, bestT));
+                };
+                const uint ref[4] = {c0.x, c0.w, c1.z, c2.y};
+                // a ray's key for a child: its entry distance (tn >= 0: the bits order like the value; the sign is cleared with the index bits, so a -0 is a 0), +inf
+                // where the ray does not enter
+                uint key[4];
+                {   float tn, tf;
+                    slab(c0.y, c0.z, tn, tf); key[0] = T8_HIT(ref[0], tn, tf) ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS;
+                    slab(c1.x, c1.y, tn, tf); key[1] = T8_HIT(ref[1], tn, tf) ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS;
+                    slab(c1.w, c2.x, tn, tf); key[2] = T8_HIT(ref[2], tn, tf) ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS;
+                    slab(c2.z, c2.w, tn, tf); key[3] = T8_HIT(ref[3], tn, tf) ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS;
+                }
+                // the minimum over the eight pairs of a row of sixteen lanes; every exchange keeps the lane's parity, so a lane goes on holding children 4h .. 4h + 3
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    key[k] = t8k_min(key[k], dpp_u<DPP_QP_XOR2>(key[k]));
+                    key[k] = t8k_min(key[k], dpp_u<DPP_ROW_ROR(4)>(key[k]));
+                    key[k] = t8k_min(key[k], dpp_u<DPP_ROW_ROR(8)>(key[k]));
+                }
+                // my child's, then over the four rows (lane positions are kept: v_permlane16_swap, v_permlane32_swap)
+                uint mk = kSel == 0u ? key[0] : (kSel == 1u ? key[1] : (kSel == 2u ? key[2] : key[3]));
+                const uint mref = kSel == 0u ? ref[0] : (kSel == 1u ? ref[1] : (kSel == 2u ? ref[2] : ref[3]));
+                {   auto r = __builtin_amdgcn_permlane16_swap(mk, mk, false, false); mk = t8k_min(r[0], r[1]); }
+                {   auto r = __builtin_amdgcn_permlane32_swap(mk, mk, false, false); mk = t8k_min(r[0], r[1]); }
+                const bool hitC = mk < INF_BITS && mref != BVH_EMPTY;      // (an empty slot is an inverted box, which nothing enters: pt_traverse8p.h T8_EMPTY_SLOT_CHECK)
+                mk |= myChild;      // unique keys: ties to the lower child
+                // rank = children with a smaller key: rotations by 1 .. 7 within the row bring each of the other seven once
+                uint rank = 0u;
+                rank += (dpp_u<DPP_ROW_ROR(1)>(mk) < mk) ? 1u : 0u; rank += (dpp_u<DPP_ROW_ROR(2)>(mk) < mk) ? 1u : 0u; rank += (dpp_u<DPP_ROW_ROR(3)>(mk) < mk) ? 1u : 0u;
+                rank += (dpp_u<DPP_ROW_ROR(4)>(mk) < mk) ? 1u : 0u; rank += (dpp_u<DPP_ROW_ROR(5)>(mk) < mk) ? 1u : 0u; rank += (dpp_u<DPP_ROW_ROR(6)>(mk) < mk) ? 1u : 0u;
+                rank += (dpp_u<DPP_ROW_ROR(7)>(mk) < mk) ? 1u : 0u;
+                const uint hitMask = (uint)t8_ballot(hitC) & 0xFFu;
+                uint next = BVH_EMPTY;
+                if (hitMask) {
+                    const uint nhit = (uint)__popc(hitMask);
+                    const uint nearMask = (uint)t8_ballot(hitC && rank == 0u) & 0xFFu;
+                    next = (uint)__builtin_amdgcn_readlane((int)mref, (int)(__ffs((int)nearMask) - 1));
+                    if (nhit > 1u) {
+                        if (sp + nhit - 1u > stackBound) { handOff = true; break; }
+                        if (lane < 8u && hitC && rank > 0u) stack[sp + (nhit - 1u - rank)] = make_uint2(mref, mk & ~7u);      // far to near: nearest on top
+                        sp += nhit - 1u;
+                    }
+                }
+                cur = next;
+            } else {
+                // ---- leaf: lane h tests triangle h (h + 2, ...) for its pair's ray — the leaf block of traverse8_pairs
+                const uint cnt = (cur & 7u) + 1u;
+                const uint slot0 = (cur & 0x7FFFFFFFu) >> 3;
+                const uint triOff0 = slot0 * 48u + laneTriOff;
+                float lt = __uint_as_float(INF_BITS), lu = 0.f, lv = 0.f; uint lp = 0xFFFFFFFFu;
+                const uint gx = axes & 0xFFu, gy = (axes >> 8) & 0xFFu, gz = axes >> 16;
+                const bool k2 = gz == 32u, k1 = gz == 16u;
+                const float okx = k2 ? o.x : (k1 ? o.z : o.y), oky = k2 ? o.y : (k1 ? o.x : o.z), okz = k2 ? o.z : (k1 ? o.y : o.x);
+                const float Sz = k2 ? iz : (k1 ? iy : ix);
+#pragma unroll 1
+                for (uint r = 0; r < T8_LEAF_ROUNDS; r++) {
+                    const bool doit = valid && (h + T8_LANES * r) < cnt;
+                    if (r > 0u && t8_ballot(doit) == 0ull) break;
+                    if (doit) {
+                        const uint toff = triOff0 + (T8_LANES * 48u) * r;
+                        struct __attribute__((packed, aligned(4))) f32x3p { float x, y, z; };
+                        const f32x3p g0 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gx)), g1 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gy)), g2 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gz));
+                        const f32x2 ABkz = (f32x2){g2.x, g2.y} - (f32x2){okz, okz}; const float Ckz = g2.z - okz;
+                        const f32x2 ABx = __builtin_elementwise_fma((f32x2){-Sx, -Sx}, ABkz, (f32x2){g0.x, g0.y} - (f32x2){okx, okx}), ABy = __builtin_elementwise_fma((f32x2){-Sy, -Sy}, ABkz, (f32x2){g1.x, g1.y} - (f32x2){oky, oky});
+                        const float Cx = fmaf(-Sx, Ckz, g0.z - okx), Cy = fmaf(-Sy, Ckz, g1.z - oky);
+                        const float Ax = ABx.x, Bx = ABx.y, Ay = ABy.x, By = ABy.y, Akz = ABkz.x, Bkz = ABkz.y;
+                        const f32x2 m1 = ABx * (f32x2){Cy, Cy}, m2 = ABy * (f32x2){Cx, Cx};
+                        float V = m1.x - m2.x, U = m2.y - m1.y, W = Bx * Ay - By * Ax;
+                        if (U == 0.0f || V == 0.0f || W == 0.0f) {
+                            if (U == 0.0f) U = fmaf(Cx, By, -(Cx * By)) - fmaf(Cy, Bx, -(Cy * Bx));
+                            if (V == 0.0f) V = fmaf(Ax, Cy, -(Ax * Cy)) - fmaf(Ay, Cx, -(Ay * Cx));
+                            if (W == 0.0f) W = fmaf(Bx, Ay, -(Bx * Ay)) - fmaf(By, Ax, -(By * Ax));
+                        }
+                        const float det = (U + V) + W;
+                        const bool inside = (bool)(((int)(fminf(U, fminf(V, W)) >= 0.0f) | (int)(fmaxf(U, fmaxf(V, W)) <= 0.0f)) & (int)(det != 0.0f));
+                        if (inside) {
+                            const float T = fmaf(W, Sz * Ckz, fmaf(V, Sz * Bkz, U * (Sz * Akz)));
+                            const float inv = 1.0f / det;
+                            const float t = T * inv, u = V * inv, v = W * inv;
+                            if (t > tmin && t < tmax) {
+                                uint off2 = toff; asm volatile("" : "+v"(off2));
+                                const f32x4 rx = *reinterpret_cast<const f32x4*>(trisBase + off2), ry = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 16u)), rz = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 32u));
+                                const uint prim = __float_as_uint(rx.w), flags = __float_as_uint(ry.w);
+                                bool c = ((t < bestT) || (t == bestT && prim < bestPrim)) && ((t < lt) || (t == lt && prim < lp));
+                                if (c) c = t8_tri_box_accepts(rx, ry, rz, rz.w, o.x, o.y, o.z, ix, iy, iz, t);
+                                if (c && (flags & 1u)) c = alpha_test_slot(sc, slot0 + h + T8_LANES * r, u, v);
+                                if (c) { lt = t; lp = prim; lu = u; lv = v; }
+                            }
+                        }
+                    }
+                }
+                const bool cand = (lp != 0xFFFFFFFFu);
+                if (t8_ballot(cand) != 0ull) {
+                    if (cand) { minePrim = lp; mineUV[threadIdx.x] = make_float2(lu, lv); }
+                    float tk = lt; uint pkk = lp;      // lexicographic min of (t, prim) over the pair
+                    {   float ot = dpp_f<DPP_QP_XOR1>(tk); uint op = dpp_u<DPP_QP_XOR1>(pkk);
+                        bool take = (ot < tk) || (ot == tk && op < pkk); tk = take ? ot : tk; pkk = take ? op : pkk; }
+                    if (pkk != 0xFFFFFFFFu) { bestT = tk; bestPrim = pkk; }
+                    // the packet's largest best t (both lanes of a pair hold their ray's)
+                    uint m = valid ? __float_as_uint(bestT) : 0u;
+                    m = t8k_max(m, dpp_u<DPP_QP_XOR2>(m)); m = t8k_max(m, dpp_u<DPP_ROW_ROR(4)>(m)); m = t8k_max(m, dpp_u<DPP_ROW_ROR(8)>(m));
+                    maxBest = t8k_max(t8k_max((uint)__builtin_amdgcn_readlane((int)m, 0), (uint)__builtin_amdgcn_readlane((int)m, 16)),
+                                      t8k_max((uint)__builtin_amdgcn_readlane((int)m, 32), (uint)__builtin_amdgcn_readlane((int)m, 48)));
+                }
+                cur = BVH_EMPTY;
+            }
+        }
+
+        if (handOff) {
+            // nothing is committed: the packet's rays are traced again, one by one
+            const uint n = (count - i0 < T8_PACKET_RAYS) ? count - i0 : T8_PACKET_RAYS;
+            uint base = 0u;
+            if (lane == 0u) base = atomicAdd(pk.leftoverCount, n);
+            base = t8k_uniform(base);
+            if (base + n <= pk.capacity) { if (valid && h == 0u) pk.leftover[base + (lane >> 1)] = i; }
+            else if (lane == 0u) atomicOr(overflowFlag, 2u);
+        } else if (valid) {
+            if (bestPrim == 0xFFFFFFFFu) { if (h == 0u) { HitInfo hh; hh.t = bestT; hh.prim = 0xFFFFFFFFu; hh.u = hh.v = 0.f; commit(i, hh); } }
+            else if (minePrim == bestPrim) { const float2 uv = mineUV[threadIdx.x]; HitInfo hh; hh.t = bestT; hh.prim = bestPrim; hh.u = uv.x; hh.v = uv.y; commit(i, hh); }
+        }
+    }
+}
+
+} // namespace ptk

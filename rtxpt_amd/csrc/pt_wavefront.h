@@ -49,7 +49,7 @@ struct WaveCounters {           // device-resident counters / stats (one 256 B b
 // counts: TRAV_COUNTERS words per traversal launch, one counter per producer so that nothing has to be reset between the launches of a pass —
 //   [0] sub-trees split off by k_extend / k_shadow (task queue 0), [1..3] by task rounds 0..2 (queues 1, 0, 1), [TRAV_RESOLVE] rays to resolve.
 // pt_render keeps one PASS_COUNTERS block per batch — {extend launch, shadow launch, k_classify's three class counts and its count of dropped hits} — and zeroes it once per pass.
-static const uint TRAV_COUNTERS = 5, TRAV_RESOLVE = 4, PASS_COUNTERS = 16, PASS_SHADOW_OFFSET = 5, PASS_CLASS_OFFSET = 10;
+static const uint TRAV_COUNTERS = 5, TRAV_RESOLVE = 4, PASS_COUNTERS = 16, PASS_SHADOW_OFFSET = 5, PASS_CLASS_OFFSET = 10, PASS_LEFTOVER = 14;      // PASS_LEFTOVER: the rays the vertex-0 packets left to the per-ray kernel (FirstPackets)
 struct TravAux { TravTask* taskQ[2]; uint* counts; uint taskCap; unsigned long long* bestKey; uint* resolveList; const uint* primToSlot; uint maxBlocks; };      // maxBlocks: grid bound of the traversal launches (0: T8_MAX_BLOCKS)
 
 // paths [first, first + n) of the pool region -> queue[0 .. n); countPtr (may be null): the counter of the queue `queue` is the end of, incremented by n (k_generate)
@@ -57,7 +57,17 @@ void launch_generate(const PathKernelContext& k, PathPool pool, const uint* owne
 void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged = false);      // ranged: the rays' intervals wait in pool.hit[p].xy (k_extend)
 // launch_extend for the first pass of a batch whose paths were NOT generated: ray i is the camera ray of path i of `fv` (no queue, no read of pool.s0 / s1). The rays that are cut into
 // sub-trees get their origin | id and direction | length written to pool.s0 / s1 [i] by a launch over the resolve list (k_first_split_rays), for the task rounds and the resolve pass behind it. The camera: wc->firstCamera. Composed frames only (no counters).
-void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, hipStream_t st);
+// pk.leftover != null: the rays are traced as 32-ray packets on one shared stack per wave (k_extend_first_packets, pt_traverse8k.h); the packets that exceed pk.stepCap steps or
+// pk.stackBound stack entries leave their rays on pk.leftover (count: *pk.leftoverCount, zero on entry; capacity >= count), which the per-ray kernel traces behind them. Same hits.
+#ifndef T8_PACKET_STACK
+#define T8_PACKET_STACK 64        // entries of a wave's stack in LDS (a node pushes at most seven)
+#endif
+#ifndef T8_PACKET_STEP_CAP
+#define T8_PACKET_STEP_CAP 128    // node + leaf steps after which a packet is handed to the per-ray kernel (environment MI355PT_PACKET_STEP_CAP overrides)
+#endif
+static const uint T8_PACKET_RAYS = 32;
+struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound; };
+void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, FirstPackets pk, hipStream_t st);
 // classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (4 words, zero on entry: three classes and the dropped hits): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr,

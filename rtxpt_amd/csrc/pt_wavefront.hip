@@ -5,6 +5,7 @@
 #include "pt_wavefront.h"
 #include "pt_traverse8.h"
 #include "pt_traverse8p.h"
+#include "pt_traverse8k.h"
 #include "pt_wavefront_device.h"
 #include <cstdlib>
 #define T8_TRAVERSE traverse8_pairs
@@ -40,10 +41,12 @@ __global__ void __launch_bounds__(256) k_generate(PathKernelContext k, PathPool 
 // FIRST: the first pass of a batch whose paths were not generated (FirstVertex, pt_wavefront.h): ray i is the camera ray of path i, formed at the chunk refill from the owned
 // pixel and the sample index — no queue, no stored ray. The rays that end up cut into sub-trees (thousands of a launch, not millions) are on the resolve list: k_first_split_rays
 // writes their origin | id and direction | length to pool.s0 / s1 behind the launch, where the task rounds and the resolve pass read them as in every other pass.
-template <bool COUNT, bool RANGED, bool FIRST = false>
+// LISTED (with FIRST): ray i of the launch is the camera ray of path queue[i] — the rays the packet launch left over (k_extend_first_packets).
+template <bool COUNT, bool RANGED, bool FIRST = false, bool LISTED = false>
 __device__ __forceinline__ void t8_extend_body(const DeviceScene& sc, const PathPool& pool, const uint* __restrict__ queue, const uint count, WaveCounters* wc, const TravAux& aux, const uint rpc,
                                                uint2* stack, uint* rayBuf, float2* mineUV, const uint vBlock, const uint vGrid, const FirstVertex* fv = nullptr) {
     static_assert(!FIRST || (!COUNT && !RANGED), "vertex 0 in place: composed frames only");
+    static_assert(!LISTED || FIRST, "an index list: vertex 0 in place only");
     // RANGED: every ray brings its own interval in the first two words of its (not yet written) hit record — the stable-plane fill pass's first launch,
     // FirstHitFromVBuffer (pt_stableplanes.h firstHitInterval). A ray of such a launch that is cut into sub-trees continues over [0, best hit so far]: the
     // lower bound is a hint, not part of the query.
@@ -54,6 +57,7 @@ __device__ __forceinline__ void t8_extend_body(const DeviceScene& sc, const Path
         if (FIRST) {
             asm volatile("" ::: "memory");
             const FirstVertexCamera fc = wc->firstCamera;
+            if (LISTED) i = queue[i];
             uint px, sample; first_vertex_of(*fv, i, px, sample);
             PathKernelContext::cameraRay(fc.cam, fc.perPixelJitterAAScale, px >> 16, px & 0xFFFFu, sample, o, d);
             tmin = 0.0f; tmax = kMaxRayTravel; startRef = 0u; bestT0 = kMaxRayTravel; bestPrim0 = 0xFFFFFFFFu;
@@ -89,6 +93,30 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first
     __shared__ uint rayBuf[T8_RAYBUF_WORDS];
     __shared__ float2 mineUV[T8_BLOCK];
     t8_extend_body<false, false, true>(sc, pool, nullptr, *countPtr, wc, aux, rpc, stack, rayBuf, mineUV, blockIdx.x, gridDim.x, &fv);
+}
+
+// Vertex 0 as packets (pt_traverse8k.h): the 32 camera rays of a wave's packet — 32 consecutive paths: 8 x 1 pixels x 4 samples of an 8 x 8 block at 4 spp — walk the tree on one
+// shared stack. Hits are committed by position like k_extend_first's; a packet over its step cap or stack bound commits nothing and leaves its rays on pk.leftover. No task queue,
+// no resolve list: a wave walks its strided range of packets and ends.
+__global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first_packets(DeviceScene sc, PathPool pool, FirstVertex fv, const uint* __restrict__ countPtr, WaveCounters* wc, FirstPackets pk) {
+    __shared__ uint2 stack[(T8_BLOCK / 64u) * T8_PACKET_STACK];
+    __shared__ float2 mineUV[T8_BLOCK];
+    auto form = [&](uint i, float3& o, float3& d) {
+        asm volatile("" ::: "memory");      // (the camera from memory where a ray is formed, as t8_extend_body<..., FIRST> reads it)
+        const FirstVertexCamera fc = wc->firstCamera;
+        uint px, sample; first_vertex_of(fv, i, px, sample);
+        PathKernelContext::cameraRay(fc.cam, fc.perPixelJitterAAScale, px >> 16, px & 0xFFFFu, sample, o, d);
+    };
+    auto commit = [&](uint p, const HitInfo& h) { pool.hit[p] = make_uint4(asuint(h.t), h.prim, asuint(h.u), asuint(h.v)); };
+    traverse8_packets(sc, *countPtr, stack, mineUV, form, commit, pk, &wc->overflow);
+}
+// ... and the per-ray kernel over the rays the packets left over: k_extend_first reading i through the list (its count: what the packet launch appended)
+__global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first_listed(DeviceScene sc, PathPool pool, FirstVertex fv, FirstPackets pk, WaveCounters* wc, TravAux aux, uint rpc) {
+    __shared__ uint2 stack[T8_GROUPS_PER_BLOCK * BVH8_STACK_STRIDE];
+    __shared__ uint rayBuf[T8_RAYBUF_WORDS];
+    __shared__ float2 mineUV[T8_BLOCK];
+    uint n = *pk.leftoverCount; if (n > pk.capacity) n = pk.capacity;
+    t8_extend_body<false, false, true, true>(sc, pool, pk.leftover, n, wc, aux, rpc, stack, rayBuf, mineUV, blockIdx.x, gridDim.x, &fv);
 }
 
 // ... and behind it, before the task rounds: the stored ray (origin | id, direction | length, as k_generate writes them) of every ray k_extend_first cut into sub-trees — the
@@ -847,9 +875,15 @@ static const uint T8_TASK_BLOCKS = T8_TASK_BLOCKS_N, T8_RESOLVE_BLOCKS = 256;
 static const uint T8_SWEEP_BLOCKS = 2048;
 static inline uint shadow_resolve_grid(uint count) { const uint g = grid_for(count, 256u, T8_SWEEP_BLOCKS); return g < T8_RESOLVE_BLOCKS ? T8_RESOLVE_BLOCKS : g; }
 static void launch_extend_stragglers(const DeviceScene& sc, PathPool pool, uint count, WaveCounters* wc, TravAux aux, hipStream_t st);
-void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, hipStream_t st) {
+void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, FirstPackets pk, hipStream_t st) {
     const uint rpc = rays_per_chunk(count);
     const uint g = grid_for(count, (T8_BLOCK / 64u) * rpc * T8_CHUNKS_PER_WAVE_MIN, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
+    if (pk.leftover) {
+        // the packets, then the per-ray kernel over what they left (its count is on the device: the grid that would hold all of it, and the waves without a chunk end at once)
+        const uint gp = grid_for(count, (T8_BLOCK / 64u) * T8_PACKET_RAYS, (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_extend_first_packets, dim3(gp), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, pk);
+        hipLaunchKernelGGL(k_extend_first_listed, dim3(g), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, pk, wc, aux, rpc);
+    } else
     hipLaunchKernelGGL(k_extend_first, dim3(g), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, aux, rpc);
     hipLaunchKernelGGL(k_first_split_rays, dim3(T8_RESOLVE_BLOCKS), dim3(256), 0, st, k, pool, fv, aux);
     launch_extend_stragglers(k.sc, pool, count, wc, aux, st);

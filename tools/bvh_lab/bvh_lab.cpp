@@ -452,8 +452,67 @@ static Hit trace8(const Bvh8& w, const Ray& r, Ctr& c) {
     return h;
 }
 
-static uint32_t rng_state = 12345u;
 static inline float frand(uint32_t& s) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return (s >> 8) * (1.0f / 16777216.0f); }
+// LAB_PACKET: a packet of rays on ONE shared stack. A child is visited if any ray's own slab test (against its own best t) enters it; the children are ordered, and a stack
+// entry is culled, by the minimum entry distance over the rays that entered it — an entry is dropped only when that minimum lies beyond the largest best t of the packet. Every
+// ray tests every triangle of a visited leaf. Returns node steps and leaf steps.
+struct PacketSteps { int nodes = 0, leaves = 0; };
+static PacketSteps trace8_packet(const Bvh8& w, const std::vector<Ray>& rs, std::vector<Hit>& hits) {
+    const int R = (int)rs.size(); PacketSteps ps; hits.assign(R, Hit{1e30f, -1});
+    std::vector<V3> id(R); for (int i = 0; i < R; i++) id[i] = {1.f / rs[i].d.x, 1.f / rs[i].d.y, 1.f / rs[i].d.z};
+    struct E { int ref; float t; }; std::vector<E> stack; int cur = 0; bool have = true;
+    while (true) {
+        if (!have) { float far = 0.f; for (int i = 0; i < R; i++) far = std::max(far, hits[i].t);
+            bool got = false; while (!stack.empty()) { E e = stack.back(); stack.pop_back(); if (e.t <= far) { cur = e.ref; got = true; break; } } if (!got) break; }
+        have = false;
+        if (cur >= 0) {
+            const Wide& n = w.nodes[cur]; ps.nodes++;
+            E hs[8]; int nh = 0;
+            for (int k = 0; k < n.n; k++) {
+                const Box& b = n.cb[k]; float tmin = 3e38f;
+                for (int i = 0; i < R; i++) { const Ray& r = rs[i];
+                    float tx1 = (b.mn.x - r.o.x) * id[i].x, tx2 = (b.mx.x - r.o.x) * id[i].x, ty1 = (b.mn.y - r.o.y) * id[i].y, ty2 = (b.mx.y - r.o.y) * id[i].y, tz1 = (b.mn.z - r.o.z) * id[i].z, tz2 = (b.mx.z - r.o.z) * id[i].z;
+                    float tn = std::max(std::max(std::min(tx1, tx2), std::min(ty1, ty2)), std::max(std::min(tz1, tz2), 0.f));
+                    float tf = std::min(std::min(std::max(tx1, tx2), std::max(ty1, ty2)), std::min(std::max(tz1, tz2), hits[i].t));
+                    if (tn <= tf) tmin = std::min(tmin, tn); }
+                if (tmin < 3e38f) hs[nh++] = {n.ref[k], tmin};
+            }
+            if (!nh) continue;
+            std::sort(hs, hs + nh, [](const E& a, const E& b) { return a.t < b.t; });
+            for (int k = nh - 1; k >= 1; k--) stack.push_back(hs[k]);
+            cur = hs[0].ref; have = true;
+        } else {
+            int code = ~cur, first = code >> 4, cnt = (code & 15) + 1; ps.leaves++;
+            for (int k = 0; k < cnt; k++) { int t = w.order[first + k]; for (int i = 0; i < R; i++) { float tt; if (isect(tris[t], rs[i].o, rs[i].d, hits[i].t, tt)) { hits[i].t = tt; hits[i].prim = t; } } }
+        }
+    }
+    return ps;
+}
+// the table of packet shapes: `packets` random tiles of px x py pixels x 4 jittered samples of a 3840 x 2160 frame of the lab's camera
+static void packet_table(const Bvh8& w, int packets) {
+    const V3 pos{4.0f, 1.7f, 20.0f}, dir = normalize(V3{1.0f, 0.12f, 0.05f}), up{0, 1, 0}; const V3 U = normalize(cross(dir, up)), Vv = normalize(cross(U, dir));
+    const float th = std::tan(0.5f * 1.0471975512f), asp = 16.f / 9.f; const int W = 3840, H = 2160, spp = 4;
+    printf("%-28s %12s %12s %16s %10s | single ray: nodes leaves | mismatches\n", "packet", "node steps", "leaf steps", "over 64 steps %", "longest");
+    const int shapes[4][2] = {{8, 1}, {4, 2}, {2, 2}, {8, 2}};
+    for (auto& sh : shapes) {
+        const int px = sh[0], py = sh[1]; uint32_t s = 4242u;
+        uint64_t N = 0, L = 0, over = 0, sn = 0, sl = 0, rays = 0, mism = 0; int longest = 0;
+        for (int p = 0; p < packets; p++) {
+            const int x0 = (int)(frand(s) * (W / px)) * px, y0 = (int)(frand(s) * (H / py)) * py;
+            std::vector<Ray> rs;
+            for (int y = 0; y < py; y++) for (int x = 0; x < px; x++) for (int k = 0; k < spp; k++) {
+                const float fx = ((x0 + x + frand(s)) / W) * 2 - 1, fy = 1 - ((y0 + y + frand(s)) / H) * 2;
+                rs.push_back(Ray{pos, normalize(dir + U * (fx * th * asp) + Vv * (fy * th))}); }
+            std::vector<Hit> hp; const PacketSteps ps = trace8_packet(w, rs, hp);
+            N += ps.nodes; L += ps.leaves; if (ps.nodes + ps.leaves > 64) over++; longest = std::max(longest, ps.nodes + ps.leaves);
+            for (size_t i = 0; i < rs.size(); i++) { Ctr c; Hit h1 = trace8(w, rs[i], c); sn += c.nodes; sl += c.leaves; rays++; if (h1.prim != hp[i].prim) mism++; }      // (ties in t go to the visiting order here: not the product's rule)
+        }
+        char nm[64]; snprintf(nm, 64, "%d x %d px x %d (%d rays)", px, py, spp, px * py * spp);
+        printf("%-28s %12.1f %12.1f %16.1f %10d | %18.1f %6.1f | %.3f %%\n", nm, (double)N / packets, (double)L / packets, 100.0 * over / packets, longest, (double)sn / rays, (double)sl / rays, 100.0 * mism / rays);
+        fflush(stdout);
+    }
+}
+
 
 int main(int argc, char** argv) {
     const char* path = argc > 1 ? argv[1] : "/tmp/bvh_lab_tris.bin";
@@ -510,6 +569,8 @@ int main(int argc, char** argv) {
         for (int it = 0; it < 3; it++) { optimize_reinsert(s, 2, 0.25f); char nm[64]; snprintf(nm, 64, "sah + reinsertion x%d cost leaf4", 2 * (it + 1)); eval(nm, s, 4, 1); } }
     if (getenv("LAB_PARALLEL_REINS")) { Bvh2 s = build_ploc(32); eval("ploc r=32 cost-driven leaf4", s, 4, 1); const float frac = getenv("LAB_FRACTION") ? (float)atof(getenv("LAB_FRACTION")) : 1.0f;
         for (int it = 0; it < (getenv("LAB_ROUNDS") ? atoi(getenv("LAB_ROUNDS")) : 4); it++) { optimize_parallel_reinsert(s, 2, frac); char nm[64]; snprintf(nm, 64, "ploc + parallel reinsertion x%d", 2 * (it + 1)); eval(nm, s, 4, 1); } }
+    // LAB_PACKET=<packets>: shared-stack packets of camera rays over the binned-SAH tree, cost-driven collapse, leaves of at most two triangles (the product's leaf size)
+    if (getenv("LAB_PACKET")) { Bvh2 s = build_sah(32); Bvh8 w8 = collapse(s, 2, 1); const int np = atoi(getenv("LAB_PACKET")); packet_table(w8, np > 0 ? np : 40000); }
     if (getenv("LAB_SBVH_REINS")) { Bvh2 s = build_sbvh(32, 1e-5f, 1.5f); eval("sbvh cost-driven leaf4", s, 4, 1); optimize_reinsert(s, 2, 0.25f); eval("sbvh + reinsertion x2 cost leaf4", s, 4, 1); }
     if (getenv("LAB_SBVH")) for (float al : {1e-5f, 1e-6f}) { Bvh2 s = build_sbvh(32, al, 1.5f); char nm[64]; snprintf(nm, 64, "sbvh a=%g cost-driven leaf4", al); eval(nm, s, 4, 1); }
     return 0;
