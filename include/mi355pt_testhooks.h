@@ -25,6 +25,16 @@ int32_t pt_probe(pt_context* ctx, int32_t kind, const void* in, size_t inBytes, 
  * capacityWords >= (numPrims + 15) / 16 words; lastDropped (may be null): the terminating hits the last pt_render call left unshaded (0 with MI355PT_DROP_INERT_TERMINAL=0, with
  * NEE-AT, and in frames whose passes are all below the classification threshold). */
 int32_t pt_get_inert_terminal(pt_context* ctx, uint32_t* numPrims, uint32_t* words, uint32_t capacityWords, uint64_t* lastDropped);
+/* The wide tree of the prepared scene as the traversal reads it, for tests/bvh_ref.py (the checker of the tree's invariants). Synchronises the context's stream and copies
+ *   nodes           numNodes 128-byte records (rtxpt_amd/csrc/pt_scene.h Bvh8Node: origin, exps, eight 12-byte child slots, the three scales as floats), capacityNodes records
+ *   tris            numTris 48-byte leaf-order records (pt_scene.h TriRecord: x[3] prim y[3] flags z[3] pad — the stored pad included), capacityTris records
+ *   bounds          six floats, min xyz then max xyz: the scene bounds the pads were formed from
+ *   wideLevelStart  min(collapseLevels, 64) + 1 words: the wide nodes of collapse level L are [wideLevelStart[L], wideLevelStart[L + 1]); capacityLevels words
+ * Every pointer may be null: the counts alone come back, so a caller sizes its buffers with a first call. A non-null buffer whose capacity is below its count is
+ * PT_ERROR_INVALID_ARGUMENT and nothing is written to any buffer. A scene without triangles gives 0 nodes, 0 triangles, 0 levels and zero bounds. Only what the traversal reads is
+ * read: after a refit (pt_animate without rebuild) the binary tree, the primitive-order triangles and the range tables of the last full build hold an older pose and stay out. */
+int32_t pt_get_bvh8(pt_context* ctx, uint32_t* numNodes, void* nodes, uint32_t capacityNodes, uint32_t* numTris, void* tris, uint32_t capacityTris, float* bounds,
+                    uint32_t* collapseLevels, uint32_t* wideLevelStart, uint32_t capacityLevels);
 #ifdef __cplusplus
 }
 #endif

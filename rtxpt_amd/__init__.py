@@ -45,7 +45,7 @@ EXPORTS = [
     "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
-TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
+TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal", "pt_get_bvh8"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
 
 
 class PtError(RuntimeError):
@@ -1426,3 +1426,17 @@ class PathTracer:
         if n.value: self._chk(self.L.pt_get_inert_terminal(self.h, None, _p(words), words.size, None), "pt_get_inert_terminal")
         prim = np.arange(n.value, dtype=np.uint32)
         return ((words[prim // 16] >> (2 * (prim % 16))) & 3).astype(np.uint32), int(dropped.value)
+
+    def get_bvh8(self, short_by=0):
+        """pt_get_bvh8 (include/mi355pt_testhooks.h): the wide tree as the traversal reads it — dict of nodes [numNodes8, 32] uint32 (the 128-byte Bvh8Node records), tris
+        [numTris, 12] uint32 (the 48-byte leaf-order TriRecords, stored pad included), bounds [6] float32 (scene min xyz, max xyz), levels (collapseLevels) and level_start
+        [min(levels, 64) + 1] uint32. short_by: hand the node buffer over with that many records less than it needs (the refusal's test). Only on a PathTracer(test_hooks=True)."""
+        if not self.test_hooks: raise RuntimeError("pt_get_bvh8 is not part of the shipped library: PathTracer(test_hooks=True)")
+        f = self.L.pt_get_bvh8; f.restype = ctypes.c_int32
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+        nn, nt, nl = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(f(self.h, ctypes.byref(nn), None, 0, ctypes.byref(nt), None, 0, None, ctypes.byref(nl), None, 0), "pt_get_bvh8")
+        nodes = np.zeros((nn.value, 32), np.uint32); tris = np.zeros((nt.value, 12), np.uint32)
+        bounds = np.zeros(6, np.float32); start = np.zeros(min(nl.value, 64) + 1, np.uint32)
+        self._chk(f(self.h, None, _p(nodes) if nodes.size else None, max(nn.value - short_by, 0), None, _p(tris) if tris.size else None, nt.value, _p(bounds), None, _p(start), start.size), "pt_get_bvh8")
+        return dict(nodes=nodes, tris=tris, bounds=bounds, levels=int(nl.value), level_start=start)

@@ -1570,6 +1570,27 @@ int32_t pt_get_inert_terminal(pt_context* c, uint32_t* numPrims, uint32_t* words
     }
     return PT_OK;
 }
+// the wide tree as the traversal reads it: nodes8, triSorted, the scene bounds the pads were formed from and the level table the refit walks. Nothing else: after a fast refit
+// (pt_build.h bvh2Stale) the BVH2 nodes, triWorld and the range tables hold an older pose
+int32_t pt_get_bvh8(pt_context* c, uint32_t* numNodes, void* nodes, uint32_t capacityNodes, uint32_t* numTris, void* tris, uint32_t capacityTris, float* bounds,
+                    uint32_t* collapseLevels, uint32_t* wideLevelStart, uint32_t capacityLevels) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    int r = prepare(c); if (r != PT_OK) return r;
+    const uint32_t nt = c->numTris, nn = nt ? c->bvh.numNodes8 : 0u, nl = nt ? c->bvh.collapseLevels : 0u, stored = (nl < BVH_MAX_WIDE_LEVELS ? nl : BVH_MAX_WIDE_LEVELS) + 1u;
+    if (numNodes) *numNodes = nn; if (numTris) *numTris = nt; if (collapseLevels) *collapseLevels = nl;
+    if ((nodes && capacityNodes < nn) || (tris && capacityTris < nt) || (wideLevelStart && capacityLevels < stored)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_bvh8: a buffer is smaller than its count");
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+    if (nodes && nn) PT_CHECK_HIP(c, hipMemcpy(nodes, c->bvh.nodes8, sizeof(Bvh8Node) * (size_t)nn, hipMemcpyDeviceToHost));
+    if (tris && nt) PT_CHECK_HIP(c, hipMemcpy(tris, c->bvh.triSorted, sizeof(TriRecord) * (size_t)nt, hipMemcpyDeviceToHost));
+    if (bounds) {
+        uint32_t enc[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+        if (nt) PT_CHECK_HIP(c, hipMemcpy(enc, c->bvh.sceneBounds, sizeof(enc), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; k++) { const uint32_t b = nt ? ((enc[k] & 0x80000000u) ? (enc[k] & 0x7FFFFFFFu) : ~enc[k]) : 0u; memcpy(bounds + k, &b, 4); }      // (pt_build.hip dec_float)
+    }
+    if (wideLevelStart) for (uint32_t l = 0; l < stored; l++) wideLevelStart[l] = nt ? c->bvh.wideLevelStart[l] : 0u;
+    return PT_OK;
+}
 #endif
 // ---- the frame gather (include/mi355pt.h "the frame gather itself")
 int32_t pt_shard_layout(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, uint32_t* pixels, uint32_t capacity, uint32_t* count) {

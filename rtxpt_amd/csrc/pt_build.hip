@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) k_bounds(const TriRecord* __restrict__ tr
 // ---- PLOC (Meister & Bittner, "Parallel Locally-Ordered Clustering for Bounding Volume Hierarchy Construction", TVCG 2018), the default builder:
 // the Morton-sorted triangles are the initial clusters; every pass each cluster looks PT_PLOC_RADIUS neighbours to either side for the partner that
 // gives the smallest merged surface area, mutual nearest neighbours merge, and the cluster list is compacted with a prefix sum (order preserved), until
-// one cluster is left. Everything is deterministic: ties go to the lower index, node numbers come from the prefix sum, no atomics.
+// one cluster is left. Everything is deterministic: ties are settled by the slots' indices (k_ploc_nn), node numbers come from the prefix sum, no atomics.
 // Against the Karras tree over the same codes this halves the SAH cost on C3 (283 -> 143, tools/bvh_lab) because neighbours are chosen by the
 // boxes they actually produce, not by the bit pattern of their centroids.
 // Node ids while building: leaves 0..n-1 (Morton position), inner nodes n.. in creation order (children before parents; the last one is the root).
@@ -216,11 +216,19 @@ __global__ void __launch_bounds__(256) k_ploc_nn(const float4* __restrict__ cbMi
     const uint li = threadIdx.x + PT_PLOC_RADIUS;
     const float4 amn = smn[li], amx = smx[li];
     const int lo = ((int)i - PT_PLOC_RADIUS < 0) ? 0 : (int)i - PT_PLOC_RADIUS, hi = ((int)i + PT_PLOC_RADIUS > (int)m - 1) ? (int)m - 1 : (int)i + PT_PLOC_RADIUS;
-    float best = 3.0e38f; uint bj = i;
+    // ties go to the lower index — except that among tied partners slot i ^ 1 comes first where the pair is degenerate: the two boxes are the same box, or the merged box has no
+    // area (duplicated geometry; geometry on one axis-parallel line). There every area of a window is the same number, and with "the lower index wins" alone only slots 0 and 1 were
+    // mutual: one merge a pass, a chain n deep, n / 7 wide levels — beyond BVH_MAX_WIDE_LEVELS from 450 identical triangles on, which cost the scene its fast refit
+    // (tests/test_gpu_bvh_structure.py). Now such a list pairs up (2k, 2k + 1) and halves every pass. Both conditions read the same from either end of a pair, so all slots still
+    // choose by one order of the pairs (area, degenerate partner first, lower index, higher index) and the least pair of a pass is mutual, as before. Every other tie falls as it did.
+    float best = 3.0e38f; uint bj = i, bk = 1u;
     for (int j = lo; j <= hi; j++) {
         if (j == (int)i) continue;
-        const float a = merged_area(amn, amx, smn[j - base], smx[j - base]);
-        if (a < best) { best = a; bj = (uint)j; }           // strict: ties stay with the lower index
+        const float4 bmn = smn[j - base], bmx = smx[j - base];
+        const float a = merged_area(amn, amx, bmn, bmx);
+        const bool same = amn.x == bmn.x && amn.y == bmn.y && amn.z == bmn.z && amx.x == bmx.x && amx.y == bmx.y && amx.z == bmx.z;
+        const uint k = ((uint)j == (i ^ 1u) && (same || a == 0.f)) ? 0u : 1u;
+        if (a < best || (a == best && k < bk)) { best = a; bj = (uint)j; bk = k; }
     }
     nn[i] = bj;
 }
