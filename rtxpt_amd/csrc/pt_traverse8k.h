@@ -3,9 +3,10 @@
 // wave-uniform, so a step has no child ranking per ray, no per-ray stack, no pop loop and no refill.
 //
 // Why the result is the single-ray kernel's, bit for bit: the closest hit is the minimum of (t, primitive) over the triangles a ray ACCEPTS, and acceptance is a property of
-// the ray and the triangle alone (the watertight test, tri_box_accepts, the alpha test: pt_scene.h) — the tree only decides which triangles are looked at. Every expression
-// below that decides acceptance, and the slab test that decides what a ray enters, is traverse8_pairs' expression on the same operands. A packet looks at a SUPERSET of what
-// each of its rays would look at alone:
+// the ray and the triangle alone (the watertight test, tri_box_accepts, the alpha test: pt_scene.h) — the tree only decides which triangles are looked at. What decides
+// acceptance (t8_leaf_block), and the slab test that decides what a ray enters (t8_slab on t8_ray_frame's and t8_slab_selectors' values), are the functions of
+// pt_traverse8.h that traverse8_pairs calls, on the same operands: the same function, not the same expression restated. A packet looks at a SUPERSET of what each of its
+// rays would look at alone:
 //  - a child is visited if ANY ray's own slab test (against its own best t) enters it;
 //  - a stack entry carries the MINIMUM entry distance over the rays that entered it, and is dropped unvisited only if that exceeds the LARGEST best t of the packet — then
 //    every ray that entered it would have dropped it (its own entry distance is no smaller, its own best t no larger);
@@ -19,7 +20,6 @@
 #include "pt_wavefront.h"
 
 namespace ptk {
-
 
 #define DPP_ROW_ROR(n) (0x120 + (n))
 __device__ __forceinline__ uint t8k_min(uint a, uint b) { return a < b ? a : b; }
@@ -36,7 +36,7 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
     uint2* stack = stackBase + t8k_uniform(threadIdx.x >> 6) * T8_PACKET_STACK;
     const char* nodesBase = reinterpret_cast<const char*>(sc.nodes8);
     const char* trisBase = reinterpret_cast<const char*>(sc.tris);
-    const uint laneChildOff = 16u + 48u * h, laneTriOff = 48u * h;
+    const uint laneChildOff = 16u + 48u * h;
     const uint INF_BITS = 0x7F800000u;
     const float tmin = 0.f, tmax = kMaxRayTravel;
     // after the reduction over the packet, lane L answers for ONE child: 4h + kSel (a row of sixteen lanes holds every child twice)
@@ -48,17 +48,7 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
         const uint i0 = p * T8_PACKET_RAYS, i = i0 + (lane >> 1);
         const bool valid = i < count;      // (the launch's last packet may be short: its idle pairs form the last ray and enter nothing)
         float3 o; float Sx, Sy, ix, iy, iz; uint axes, selN, selF;
-        {   float3 rd; form(valid ? i : count - 1u, o, rd);
-            // as the chunk refill of traverse8_pairs forms them
-            ix = t8_rcp_dir(rd.x); iy = t8_rcp_dir(rd.y); iz = t8_rcp_dir(rd.z);
-            const float adx = fabsf(rd.x), ady = fabsf(rd.y), adz = fabsf(rd.z);
-            const bool rk2 = adz > adx && adz > ady, rk1 = !rk2 && ady > adx;
-            const float rSz = rk2 ? iz : (rk1 ? iy : ix);
-            Sx = (rk2 ? rd.x : (rk1 ? rd.z : rd.y)) * rSz; Sy = (rk2 ? rd.y : (rk1 ? rd.x : rd.z)) * rSz;
-            axes = rk2 ? (0u | (16u << 8) | (32u << 16)) : (rk1 ? (32u | (0u << 8) | (16u << 16)) : (16u | (32u << 8) | (0u << 16)));
-            const uint nxb = ix < 0.f ? 3u : 0u, fxb = ix < 0.f ? 0u : 3u, nyb = iy < 0.f ? 4u : 1u, fyb = iy < 0.f ? 1u : 4u, nzb = iz < 0.f ? 5u : 2u, fzb = iz < 0.f ? 2u : 5u;
-            selN = nxb | (nyb << 8) | (nzb << 16) | (fxb << 24); selF = fyb | (fzb << 8);
-        }
+        {   float3 rd; form(valid ? i : count - 1u, o, rd); t8_ray_frame(rd, ix, iy, iz, Sx, Sy, axes); t8_slab_selectors(ix, iy, iz, selN, selF); }
         // (an idle pair's best t is negative: its slab intervals are empty, it enters nothing, and no triangle is tested for it)
         float bestT = valid ? tmax : -1.0f; uint bestPrim = 0xFFFFFFFFu, minePrim = 0xFFFFFFFFu;
         // wave-uniform: the node in hand, the stack pointer, the steps so far, the largest best t of the packet (as bits: t > 0)
@@ -87,15 +77,7 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
                 const f32x4 scl = *reinterpret_cast<const f32x4*>(nodesBase + (nodeOff + 112u));
                 const float nx = __uint_as_float(hdr.x), ny = __uint_as_float(hdr.y), nz = __uint_as_float(hdr.z);
                 const float sx = scl.x, sy = scl.y, sz = scl.z;
-                auto slab = [&](uint q0, uint q1, float& tn, float& tf) {
-                    const uint N = __builtin_amdgcn_perm(q1, q0, selN), F = __builtin_amdgcn_perm(q1, q0, selF);
-                    f32x2 px = __builtin_elementwise_fma((f32x2){(float)(N & 0xFFu), (float)(N >> 24)}, (f32x2){sx, sx}, (f32x2){nx, nx});
-                    f32x2 py = __builtin_elementwise_fma((f32x2){(float)((N >> 8) & 0xFFu), (float)(F & 0xFFu)}, (f32x2){sy, sy}, (f32x2){ny, ny});
-                    f32x2 pz = __builtin_elementwise_fma((f32x2){(float)((N >> 16) & 0xFFu), (float)((F >> 8) & 0xFFu)}, (f32x2){sz, sz}, (f32x2){nz, nz});
-                    f32x2 tx = (px - (f32x2){o.x, o.x}) * (f32x2){ix, ix}, ty = (py - (f32x2){o.y, o.y}) * (f32x2){iy, iy}, tz = (pz - (f32x2){o.z, o.z}) * (f32x2){iz, iz};
-                    tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
-                    tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, bestT));
-                };
+                auto slab = [&](uint q0, uint q1, float& tn, float& tf) { t8_slab(q0, q1, selN, selF, nx, ny, nz, sx, sy, sz, o.x, o.y, o.z, ix, iy, iz, tmin, bestT, tn, tf); };
                 const uint ref[4] = {c0.x, c0.w, c1.z, c2.y};
                 // a ray's key for a child: its entry distance (tn >= 0: the bits order like the value; the sign is cleared with the index bits, so a -0 is a 0), +inf
                 // where the ray does not enter
@@ -118,7 +100,7 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
                 const uint mref = kSel == 0u ? ref[0] : (kSel == 1u ? ref[1] : (kSel == 2u ? ref[2] : ref[3]));
                 {   auto r = __builtin_amdgcn_permlane16_swap(mk, mk, false, false); mk = t8k_min(r[0], r[1]); }
                 {   auto r = __builtin_amdgcn_permlane32_swap(mk, mk, false, false); mk = t8k_min(r[0], r[1]); }
-                const bool hitC = mk < INF_BITS && mref != BVH_EMPTY;      // (an empty slot is an inverted box, which nothing enters: pt_traverse8p.h T8_EMPTY_SLOT_CHECK)
+                const bool hitC = mk < INF_BITS && mref != BVH_EMPTY;      // (an empty slot is an inverted box, which nothing enters: pt_traverse8.h T8_EMPTY_SLOT_CHECK)
                 mk |= myChild;      // unique keys: ties to the lower child
                 // rank = children with a smaller key: rotations by 1 .. 7 within the row bring each of the other seven once
                 uint rank = 0u;
@@ -139,58 +121,12 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
                 }
                 cur = next;
             } else {
-                // ---- leaf: lane h tests triangle h (h + 2, ...) for its pair's ray — the leaf block of traverse8_pairs
-                const uint cnt = (cur & 7u) + 1u;
-                const uint slot0 = (cur & 0x7FFFFFFFu) >> 3;
-                const uint triOff0 = slot0 * 48u + laneTriOff;
-                float lt = __uint_as_float(INF_BITS), lu = 0.f, lv = 0.f; uint lp = 0xFFFFFFFFu;
-                const uint gx = axes & 0xFFu, gy = (axes >> 8) & 0xFFu, gz = axes >> 16;
-                const bool k2 = gz == 32u, k1 = gz == 16u;
-                const float okx = k2 ? o.x : (k1 ? o.z : o.y), oky = k2 ? o.y : (k1 ? o.x : o.z), okz = k2 ? o.z : (k1 ? o.y : o.x);
-                const float Sz = k2 ? iz : (k1 ? iy : ix);
-#pragma unroll 1
-                for (uint r = 0; r < T8_LEAF_ROUNDS; r++) {
-                    const bool doit = valid && (h + T8_LANES * r) < cnt;
-                    if (r > 0u && t8_ballot(doit) == 0ull) break;
-                    if (doit) {
-                        const uint toff = triOff0 + (T8_LANES * 48u) * r;
-                        struct __attribute__((packed, aligned(4))) f32x3p { float x, y, z; };
-                        const f32x3p g0 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gx)), g1 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gy)), g2 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gz));
-                        const f32x2 ABkz = (f32x2){g2.x, g2.y} - (f32x2){okz, okz}; const float Ckz = g2.z - okz;
-                        const f32x2 ABx = __builtin_elementwise_fma((f32x2){-Sx, -Sx}, ABkz, (f32x2){g0.x, g0.y} - (f32x2){okx, okx}), ABy = __builtin_elementwise_fma((f32x2){-Sy, -Sy}, ABkz, (f32x2){g1.x, g1.y} - (f32x2){oky, oky});
-                        const float Cx = fmaf(-Sx, Ckz, g0.z - okx), Cy = fmaf(-Sy, Ckz, g1.z - oky);
-                        const float Ax = ABx.x, Bx = ABx.y, Ay = ABy.x, By = ABy.y, Akz = ABkz.x, Bkz = ABkz.y;
-                        const f32x2 m1 = ABx * (f32x2){Cy, Cy}, m2 = ABy * (f32x2){Cx, Cx};
-                        float V = m1.x - m2.x, U = m2.y - m1.y, W = Bx * Ay - By * Ax;
-                        if (U == 0.0f || V == 0.0f || W == 0.0f) {
-                            if (U == 0.0f) U = fmaf(Cx, By, -(Cx * By)) - fmaf(Cy, Bx, -(Cy * Bx));
-                            if (V == 0.0f) V = fmaf(Ax, Cy, -(Ax * Cy)) - fmaf(Ay, Cx, -(Ay * Cx));
-                            if (W == 0.0f) W = fmaf(Bx, Ay, -(Bx * Ay)) - fmaf(By, Ax, -(By * Ax));
-                        }
-                        const float det = (U + V) + W;
-                        const bool inside = (bool)(((int)(fminf(U, fminf(V, W)) >= 0.0f) | (int)(fmaxf(U, fmaxf(V, W)) <= 0.0f)) & (int)(det != 0.0f));
-                        if (inside) {
-                            const float T = fmaf(W, Sz * Ckz, fmaf(V, Sz * Bkz, U * (Sz * Akz)));
-                            const float inv = 1.0f / det;
-                            const float t = T * inv, u = V * inv, v = W * inv;
-                            if (t > tmin && t < tmax) {
-                                uint off2 = toff; asm volatile("" : "+v"(off2));
-                                const f32x4 rx = *reinterpret_cast<const f32x4*>(trisBase + off2), ry = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 16u)), rz = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 32u));
-                                const uint prim = __float_as_uint(rx.w), flags = __float_as_uint(ry.w);
-                                bool c = ((t < bestT) || (t == bestT && prim < bestPrim)) && ((t < lt) || (t == lt && prim < lp));
-                                if (c) c = t8_tri_box_accepts(rx, ry, rz, rz.w, o.x, o.y, o.z, ix, iy, iz, t);
-                                if (c && (flags & 1u)) c = alpha_test_slot(sc, slot0 + h + T8_LANES * r, u, v);
-                                if (c) { lt = t; lp = prim; lu = u; lv = v; }
-                            }
-                        }
-                    }
-                }
-                const bool cand = (lp != 0xFFFFFFFFu);
+                // ---- leaf: every ray of the packet tests its triangles — the shared leaf block (pt_traverse8.h t8_leaf_block), closest hit, no counters
+                const T8LeafHit lh = t8_leaf_block<false, false>(sc, trisBase, cur, h, valid, o.x, o.y, o.z, ix, iy, iz, Sx, Sy, axes, tmin, tmax, bestT, bestPrim, nullptr);
+                const bool cand = (lh.prim != 0xFFFFFFFFu);
                 if (t8_ballot(cand) != 0ull) {
-                    if (cand) { minePrim = lp; mineUV[threadIdx.x] = make_float2(lu, lv); }
-                    float tk = lt; uint pkk = lp;      // lexicographic min of (t, prim) over the pair
-                    {   float ot = dpp_f<DPP_QP_XOR1>(tk); uint op = dpp_u<DPP_QP_XOR1>(pkk);
-                        bool take = (ot < tk) || (ot == tk && op < pkk); tk = take ? ot : tk; pkk = take ? op : pkk; }
+                    if (cand) { minePrim = lh.prim; mineUV[threadIdx.x] = make_float2(lh.u, lh.v); }
+                    float tk = lh.t; uint pkk = lh.prim; t8_pair_min(tk, pkk);
                     if (pkk != 0xFFFFFFFFu) { bestT = tk; bestPrim = pkk; }
                     // the packet's largest best t (both lanes of a pair hold their ray's)
                     uint m = valid ? __float_as_uint(bestT) : 0u;
@@ -211,8 +147,7 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
             if (base + n <= pk.capacity) { if (valid && h == 0u) pk.leftover[base + (lane >> 1)] = i; }
             else if (lane == 0u) atomicOr(overflowFlag, 2u);
         } else if (valid) {
-            if (bestPrim == 0xFFFFFFFFu) { if (h == 0u) { HitInfo hh; hh.t = bestT; hh.prim = 0xFFFFFFFFu; hh.u = hh.v = 0.f; commit(i, hh); } }
-            else if (minePrim == bestPrim) { const float2 uv = mineUV[threadIdx.x]; HitInfo hh; hh.t = bestT; hh.prim = bestPrim; hh.u = uv.x; hh.v = uv.y; commit(i, hh); }
+            t8_report_closest(i, h, bestT, bestPrim, minePrim, mineUV, commit);
         }
     }
 }

@@ -8,26 +8,16 @@
 // lane of the ray's group repeats. Two lanes per ray halve the replicated share per ray: per lane the slab and triangle work doubles (four children, two
 // triangle rounds), per wave iteration the instruction count rises by about a third, and the iteration advances 32 rays instead of 16. The closest hit is
 // traversal-order free (min t, ties to the lower primitive id); an occlusion query reports whether any accepted hit exists. Straggler splitting, Src / Dst /
-// Pub and the template flags: pt_traverse8.h.
+// Pub and the template flags: pt_traverse8.h — and so are the slab test and the hit definition (ray frame, leaf block, pair minimum, closest-hit report), which this
+// traverser calls like every other: what is written here is policy — refill, child ranking, the stack, postponed leaves, splitting.
 #pragma once
 #include "pt_traverse8.h"
 
 namespace ptk {
 
 #define DPP_PAIR_LO 0xA0      // quad_perm [0,0,2,2]: lane 0 of the pair
-#define DPP_PAIR_HI 0xF5      // quad_perm [1,1,3,3]: lane 1 of the pair
 __device__ __forceinline__ uint pair_bits(unsigned long long m, uint pl) { return (uint)(m >> pl) & 0x3u; }
 
-#ifndef T8_EMPTY_SLOT_CHECK
-// 0: an empty child slot needs no test of its own — the builder writes it as an inverted box (lo = 255, hi = 0 on every axis: pt_build.hip k_collapse8),
-#define T8_EMPTY_SLOT_CHECK 0
-// which no ray's slab interval enters; were it ever "hit" (a node of zero extent), its reference is BVH_EMPTY, which the slot bookkeeping skips
-#endif
-#if T8_EMPTY_SLOT_CHECK
-#define T8_HIT(ref, tn, tf) (((ref) != BVH_EMPTY) && ((tn) <= (tf) * 1.0000012f))
-#else
-#define T8_HIT(ref, tn, tf) ((tn) <= (tf) * 1.0000012f)
-#endif
 // Measured and removed (history: commit af4c2b2 has the code; numbers in DESIGN.md §4): a dense leaf block (profiles/r04y_dense_leaf_ab.txt, +13 %), batched
 // refills (r04y_refill_batch_ab.txt), one pop trip per iteration (r04v_pop_once_ab.txt), two entries per pop trip, octant-ordered child slots
 // (r04u_octant_order_ab.txt, +25 %); round 5: a ray with nothing left but postponed leaves waiting one or three iterations (or for a second / fourth such ray)
@@ -50,7 +40,7 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
     const uint waveId = vBlock * wavesPerBlock + (threadIdx.x >> 6), numWaves = vGrid * wavesPerBlock;
     const char* nodesBase = reinterpret_cast<const char*>(sc.nodes8);
     const char* trisBase = reinterpret_cast<const char*>(sc.tris);
-    const uint laneChildOff = 16u + 48u * h, laneTriOff = 48u * h;
+    const uint laneChildOff = 16u + 48u * h;
     const uint INF_BITS = 0x7F800000u;
 
     const uint numWavesU = (uint)__builtin_amdgcn_readfirstlane((int)numWaves);
@@ -113,20 +103,12 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
                     uint rtag = fetch(chunkPos + lane, ro, rd, rtmin, rtmax, rstart, rbestT, rbestPrim);
                     uint* slot = rayBuf + lane * RAY_STRIDE;
                     slot[0] = __float_as_uint(ro.x); slot[1] = __float_as_uint(ro.y); slot[2] = __float_as_uint(ro.z);
-                    // what the leaf block needs of the direction (intersect_tri_wt, pt_scene.h), formed once by the fetching lane: kz = the axis of the largest
-                    // |d| (ties to the lower axis), kx / ky the next two in cyclic order; Sz = the reciprocal of d[kz], Sx = d[kx] * Sz, Sy = d[ky] * Sz. The
-                    // direction itself is not kept.
-                    const float rix = t8_rcp_dir(rd.x), riy = t8_rcp_dir(rd.y), riz = t8_rcp_dir(rd.z);
-                    const float adx = fabsf(rd.x), ady = fabsf(rd.y), adz = fabsf(rd.z);
-                    const bool rk2 = adz > adx && adz > ady, rk1 = !rk2 && ady > adx;
-                    const float rSz = rk2 ? riz : (rk1 ? riy : rix);
-                    slot[3] = __float_as_uint((rk2 ? rd.x : (rk1 ? rd.z : rd.y)) * rSz); slot[4] = __float_as_uint((rk2 ? rd.y : (rk1 ? rd.x : rd.z)) * rSz);
-                    slot[5] = rk2 ? (0u | (16u << 8) | (32u << 16)) : (rk1 ? (32u | (0u << 8) | (16u << 16)) : (16u | (32u << 8) | (0u << 16)));
+                    float rix, riy, riz, rSx, rSy; uint raxes; t8_ray_frame(rd, rix, riy, riz, rSx, rSy, raxes);      // (formed once, by the fetching lane)
+                    slot[3] = __float_as_uint(rSx); slot[4] = __float_as_uint(rSy); slot[5] = raxes;
                     slot[6] = rtag;
                     // the interval's two words are free (every ray of the launch has [0, kMaxRayTravel]): they carry the byte selectors of the slab test
                     if (FIXED_RANGE && !TASKS) {
-                        const uint nxb = rix < 0.f ? 3u : 0u, fxb = rix < 0.f ? 0u : 3u, nyb = riy < 0.f ? 4u : 1u, fyb = riy < 0.f ? 1u : 4u, nzb = riz < 0.f ? 5u : 2u, fzb = riz < 0.f ? 2u : 5u;
-                        slot[7] = nxb | (nyb << 8) | (nzb << 16) | (fxb << 24); slot[8] = fyb | (fzb << 8);
+                        uint rselN, rselF; t8_slab_selectors(rix, riy, riz, rselN, rselF); slot[7] = rselN; slot[8] = rselF;
                     } else { slot[7] = __float_as_uint(TASKS ? rtmax : rtmin); slot[8] = TASKS ? __float_as_uint(rbestT) : __float_as_uint(rtmax); }
                     if (TASKS) { slot[9] = rbestPrim; slot[10] = rstart; }
                     slot[RAY_STRIDE - 3u] = __float_as_uint(rix); slot[RAY_STRIDE - 2u] = __float_as_uint(riy); slot[RAY_STRIDE - 1u] = __float_as_uint(riz);
@@ -148,10 +130,7 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
                     tag = slot[6];
                     ix = __uint_as_float(slot[RAY_STRIDE - 3u]); iy = __uint_as_float(slot[RAY_STRIDE - 2u]); iz = __uint_as_float(slot[RAY_STRIDE - 1u]);
                     if (FIXED_RANGE && !TASKS) { selN = slot[7]; selF = slot[8]; }
-                    else {   // child bytes: q0 = lo.x lo.y lo.z hi.x (selector values 0..3), q1 = hi.y hi.z (4, 5)
-                        const uint nxb = ix < 0.f ? 3u : 0u, fxb = ix < 0.f ? 0u : 3u, nyb = iy < 0.f ? 4u : 1u, fyb = iy < 0.f ? 1u : 4u, nzb = iz < 0.f ? 5u : 2u, fzb = iz < 0.f ? 2u : 5u;
-                        selN = nxb | (nyb << 8) | (nzb << 16) | (fxb << 24); selF = fyb | (fzb << 8);
-                    }
+                    else t8_slab_selectors(ix, iy, iz, selN, selF);
                     if (TASKS) {
                         if (!FIXED_RANGE) tmax = __uint_as_float(slot[7]);
                         bestT = taskT0 = __uint_as_float(slot[8]); bestPrim = taskPrim0 = slot[9]; cur = slot[10];
@@ -228,15 +207,7 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
             if (COUNT && h == 0u) ctr.nodeVisits++;
             const float nx = __uint_as_float(hdr.x), ny = __uint_as_float(hdr.y), nz = __uint_as_float(hdr.z);
             const float sx = scl.x, sy = scl.y, sz = scl.z;
-            auto slab = [&](uint q0, uint q1, float& tn, float& tf) {
-                const uint N = __builtin_amdgcn_perm(q1, q0, selN), F = __builtin_amdgcn_perm(q1, q0, selF);
-                f32x2 px = __builtin_elementwise_fma((f32x2){(float)(N & 0xFFu), (float)(N >> 24)}, (f32x2){sx, sx}, (f32x2){nx, nx});
-                f32x2 py = __builtin_elementwise_fma((f32x2){(float)((N >> 8) & 0xFFu), (float)(F & 0xFFu)}, (f32x2){sy, sy}, (f32x2){ny, ny});
-                f32x2 pz = __builtin_elementwise_fma((f32x2){(float)((N >> 16) & 0xFFu), (float)((F >> 8) & 0xFFu)}, (f32x2){sz, sz}, (f32x2){nz, nz});
-                f32x2 tx = (px - (f32x2){o.x, o.x}) * (f32x2){ix, ix}, ty = (py - (f32x2){o.y, o.y}) * (f32x2){iy, iy}, tz = (pz - (f32x2){o.z, o.z}) * (f32x2){iz, iz};
-                tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
-                tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, bestT));
-            };
+            auto slab = [&](uint q0, uint q1, float& tn, float& tf) { t8_slab(q0, q1, selN, selF, nx, ny, nz, sx, sy, sz, o.x, o.y, o.z, ix, iy, iz, tmin, bestT, tn, tf); };
             uint ref[4] = {c0.x, c0.w, c1.z, c2.y};
             // integer sort keys: tn >= 0 so its bits order like the value; the low 3 mantissa bits carry the child index (unique keys, ties to the lower
             // child); a child that is not hit gets +inf. The stack entry's distance is the key without its index bits.
@@ -290,90 +261,23 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
         }
 
         if (COUNT) { tc2 = __builtin_readcyclecounter(); if (t8_ballot(leaf) != 0ull && lane == 0u) ctr.leafBlocks++; }
-        // ---- postponed leaf: lane h tests triangle h (h + 2, ... when leaves hold more than two). The watertight test of pt_scene.h (intersect_tri_wt) on the
-        // same operands: the axis permutation (kx, ky, kz) is the ORDER in which the record's three 16-byte groups are loaded; the ray's own quantities are
-        // selected once per leaf block.
+        // ---- postponed leaf: the shared leaf block (pt_traverse8.h t8_leaf_block), every lane of the wave that holds a ray with a postponed leaf
         if (leaf) {
-            const uint cnt = (pend & 7u) + 1u;
-            const uint slot0 = (pend & 0x7FFFFFFFu) >> 3;
-            const uint triOff0 = slot0 * 48u + laneTriOff;
-            float lt = __uint_as_float(INF_BITS), lu = 0.f, lv = 0.f; uint lp = 0xFFFFFFFFu;
-            bool alphaRan = false;
-            const uint gx = axes & 0xFFu, gy = (axes >> 8) & 0xFFu, gz = axes >> 16;          // byte offsets of the groups of axes kx, ky, kz
-            const bool k2 = gz == 32u, k1 = gz == 16u;                                      // kz = 2 / 1 / 0
-            const float okx = k2 ? o.x : (k1 ? o.z : o.y), oky = k2 ? o.y : (k1 ? o.x : o.z), okz = k2 ? o.z : (k1 ? o.y : o.x);
-            const float Sz = k2 ? iz : (k1 ? iy : ix);                                       // ix / iy / iz = ray_safe_rcp of the direction's components
-#pragma unroll 1
-            for (uint r = 0; r < T8_LEAF_ROUNDS; r++) {
-                const bool doit = (h + T8_LANES * r) < cnt;
-                if (r > 0u && t8_ballot(doit) == 0ull) break;
-                if (doit) {
-                    const uint toff = triOff0 + (T8_LANES * 48u) * r;      // (32-bit byte offsets from the SGPR base: global_load ... saddr)
-                    // twelve bytes per group (global_load_dwordx3): the fourth word is not needed here, and a 16-byte destination whose last register the
-                    // allocator then reuses for the next load's address makes that load wait for this one — two memory latencies in a row instead of one (seen
-                    // in the ISA, measured: +10 % on k_extend)
-                    struct __attribute__((packed, aligned(4))) f32x3p { float x, y, z; };
-                    const f32x3p g0 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gx)), g1 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gy)), g2 = *reinterpret_cast<const f32x3p*>(trisBase + (toff + gz));
-                    if (COUNT) ctr.triTests++;
-                    // intersect_tri_wt's arithmetic, two values per instruction where the operands already sit in neighbouring registers (vertices 0 and 1 of a
-                    // loaded group): packed fp32 operations round each half like the scalar ones
-                    const f32x2 ABkz = (f32x2){g2.x, g2.y} - (f32x2){okz, okz}; const float Ckz = g2.z - okz;
-                    const f32x2 ABx = __builtin_elementwise_fma((f32x2){-Sx, -Sx}, ABkz, (f32x2){g0.x, g0.y} - (f32x2){okx, okx}), ABy = __builtin_elementwise_fma((f32x2){-Sy, -Sy}, ABkz, (f32x2){g1.x, g1.y} - (f32x2){oky, oky});
-                    const float Cx = fmaf(-Sx, Ckz, g0.z - okx), Cy = fmaf(-Sy, Ckz, g1.z - oky);
-                    const float Ax = ABx.x, Bx = ABx.y, Ay = ABy.x, By = ABy.y, Akz = ABkz.x, Bkz = ABkz.y;
-                    const f32x2 m1 = ABx * (f32x2){Cy, Cy}, m2 = ABy * (f32x2){Cx, Cx};      // (Ax Cy, Bx Cy), (Ay Cx, By Cx)
-                    float V = m1.x - m2.x, U = m2.y - m1.y, W = Bx * Ay - By * Ax;            // U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax
-                    // on an edge or a vertex (or a degenerate triangle): the exact sign from the products' rounding errors (wt_edge)
-                    if (U == 0.0f || V == 0.0f || W == 0.0f) {
-                        if (U == 0.0f) U = fmaf(Cx, By, -(Cx * By)) - fmaf(Cy, Bx, -(Cy * Bx));
-                        if (V == 0.0f) V = fmaf(Ax, Cy, -(Ax * Cy)) - fmaf(Ay, Cx, -(Ay * Cx));
-                        if (W == 0.0f) W = fmaf(Bx, Ay, -(Bx * Ay)) - fmaf(By, Ax, -(By * Ax));
-                    }
-                    const float det = (U + V) + W;
-                    // no edge function negative, or none positive (pt_scene.h writes it as !((U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0)): the same
-                    // boolean for numbers; a NaN ends as "no hit" either way, through t); without short-circuits: v_min3, v_max3 and three compares, no branch
-                    const bool inside = (bool)(((int)(fminf(U, fminf(V, W)) >= 0.0f) | (int)(fmaxf(U, fmaxf(V, W)) <= 0.0f)) & (int)(det != 0.0f));
-                    if (inside) {
-                        const float T = fmaf(W, Sz * Ckz, fmaf(V, Sz * Bkz, U * (Sz * Akz)));
-                        const float inv = 1.0f / det;
-                        const float t = T * inv, u = V * inv, v = W * inv;
-                        if (t > tmin && t < tmax) {
-                            // a candidate (about one test in six): the record again, in its own order this time — prim rides with the x group, flags with y,
-                            // pad with z. Reloaded (the line is in the L1) instead of kept: twelve registers that the loop does not have — with them live
-                            // across the test the kernels spill inside the loop.
-                            uint off2 = toff; asm volatile("" : "+v"(off2));      // (an address the compiler cannot match with the loads above)
-                            const f32x4 rx = *reinterpret_cast<const f32x4*>(trisBase + off2), ry = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 16u)), rz = *reinterpret_cast<const f32x4*>(trisBase + (off2 + 32u));
-                            const uint prim = __float_as_uint(rx.w), flags = __float_as_uint(ry.w);
-                            bool c;
-                            if (ANYHIT) {
-                                c = t8_tri_box_accepts(rx, ry, rz, rz.w, o.x, o.y, o.z, ix, iy, iz, t);
-                                if (c && (flags & 1u)) { if (COUNT && !(flags & 2u)) alphaRan = true; c = !(flags & 2u) && alpha_test_slot(sc, slot0 + h + T8_LANES * r, u, v); }      // AlphaTestVisibilityRay (BridgeDonut:981-989)
-                            } else {
-                                c = ((t < bestT) || (t == bestT && prim < bestPrim)) && ((t < lt) || (t == lt && prim < lp));
-                                if (c) c = t8_tri_box_accepts(rx, ry, rz, rz.w, o.x, o.y, o.z, ix, iy, iz, t);
-                                if (c && (flags & 1u)) { if (COUNT) alphaRan = true; c = alpha_test_slot(sc, slot0 + h + T8_LANES * r, u, v); }
-                            }
-                            if (c) { lt = t; lp = prim; lu = u; lv = v; }
-                        }
-                    }
-                }
-            }
-            const bool cand = (lp != 0xFFFFFFFFu);
+            const T8LeafHit lh = t8_leaf_block<ANYHIT, COUNT>(sc, trisBase, pend, h, true, o.x, o.y, o.z, ix, iy, iz, Sx, Sy, axes, tmin, tmax, bestT, bestPrim, &ctr);
+            const bool cand = (lh.prim != 0xFFFFFFFFu);
             pend = pend1; pend1 = pend2; pend2 = BVH_EMPTY;
             uint candBits = pair_bits(t8_ballot(cand), pl);
 #ifndef T8_PROBE_INSTANCE_SWITCHES
-            T8_EVENT(4, alphaRan);
+            T8_EVENT(4, lh.alphaRan);
 #endif
             T8_EVENT(5, candBits != 0u);
             if (candBits) {
                 if (ANYHIT) {
-                    if (h == (uint)__ffs((int)candBits) - 1u) { HitInfo hh; hh.t = lt; hh.prim = lp; hh.u = hh.v = 0.f; commit(tag, hh); }
+                    if (h == (uint)__ffs((int)candBits) - 1u) { HitInfo hh; hh.t = lh.t; hh.prim = lh.prim; hh.u = hh.v = 0.f; commit(tag, hh); }
                     active = false;
                 } else {
-                    if (cand && !TASKS) { minePrim = lp; mineUV[threadIdx.x] = make_float2(lu, lv); }
-                    float tk = lt; uint pk = lp;      // lexicographic min of (t, prim) over the pair
-                    {   float ot = dpp_f<DPP_QP_XOR1>(tk); uint op = dpp_u<DPP_QP_XOR1>(pk);
-                        bool take = (ot < tk) || (ot == tk && op < pk); tk = take ? ot : tk; pk = take ? op : pk; }
+                    if (cand && !TASKS) { minePrim = lh.prim; mineUV[threadIdx.x] = make_float2(lh.u, lh.v); }
+                    float tk = lh.t; uint pk = lh.prim; t8_pair_min(tk, pk);
                     bestT = tk; bestPrim = pk;
                 }
             }
@@ -412,8 +316,7 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
                         else if (h == 0u && (bestPrim != taskPrim0 || bestT != taskT0)) { HitInfo hh; hh.t = bestT; hh.prim = bestPrim; hh.u = hh.v = 0.f; commit(tag, hh); }
                     }
                     else if (ANYHIT) { if (h == 0u) { HitInfo hh; hh.t = tmax; hh.prim = 0xFFFFFFFFu; hh.u = hh.v = 0.f; commit(tag, hh); } }
-                    else if (bestPrim == 0xFFFFFFFFu) { if (h == 0u) { HitInfo hh; hh.t = bestT; hh.prim = 0xFFFFFFFFu; hh.u = hh.v = 0.f; commit(tag, hh); } }
-                    else if (minePrim == bestPrim) { float2 uv = mineUV[threadIdx.x]; HitInfo hh; hh.t = bestT; hh.prim = bestPrim; hh.u = uv.x; hh.v = uv.y; commit(tag, hh); }
+                    else t8_report_closest(tag, h, bestT, bestPrim, minePrim, mineUV, commit);
                     active = false;
                 }
             }

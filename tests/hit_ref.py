@@ -1,4 +1,4 @@
-"""A float64 restatement of the hit test, exhaustive over the triangles, in plain numpy: what the traversal (device: pt_traverse8p.h's leaf block over the BVH8; oracle:
+"""A float64 restatement of the hit test, exhaustive over the triangles, in plain numpy: what the traversal (device: pt_traverse8.h's leaf block, t8_leaf_block, over the BVH8; oracle:
 oracle/ptref/scene.h) is held to. No BVH, no box half, no text shared with pt_scene.h.
 
 The definition. A ray is (o, tmin, d, tmax) in float32 AS THE QUERY RECEIVES IT, a triangle three world-space float32 vertices as the scene build bakes them (world_triangles

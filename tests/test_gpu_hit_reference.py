@@ -1,4 +1,4 @@
-"""The device's hit test (run with -m gpu) — the leaf block of pt_traverse8p.h under the device-built BVH8, default builder and host SAH, and after a refit — held to the
+"""The device's hit test (run with -m gpu) — the leaf block of pt_traverse8.h (t8_leaf_block) under the device-built BVH8, default builder and host SAH, and after a refit — held to the
 float64 restatement tests/hit_ref.py on the zoo of tests/hit_cases.py, and to the oracle bit for bit on the same rays. The CPU twin with the derivation of the bounds, the
 zoo and the far-origin contract: tests/test_hit_reference.py, tests/hit_ref.py, tests/hit_cases.py.
 
