@@ -190,6 +190,29 @@ int32_t pt_gltf_animation_positions(pt_gltf_animation* anim, uint32_t animation,
    normalize(SUM_k w_k inverse-transpose(J_k) n), its tangent normalize(SUM_k w_k J_k t.xyz) with the handedness kept; morph targets' NORMAL / TANGENT displacements are added first (renormalised); other vertices keep theirs.
    Returns the number of vertices (capacity 0: a query). -> pt_animate_normals */
 int32_t pt_gltf_animation_normals(pt_gltf_animation* anim, uint32_t animation, float timeSeconds, uint32_t* normalsSnorm8, uint32_t* tangentsSnorm8, uint32_t capacityVertices);
+/* The same pose split into what never changes and what a frame brings, for pt_set_skinning / pt_animate_skinned (below), which evaluate it on the device: the reference's skinned
+   instances are rewritten by Donut's SkinnedMeshInstance pass on the GPU every frame (Sample.cpp:1065, 1170-1198). Donut is not vendored and its skinning shader is not in the
+   reference tree, so the arithmetic is the glTF specification's as pt_gltf_animation_positions / _normals state it (UNPINNED); rtxpt_amd/csrc/pt_skin.h is its one text.
+   PtSkinningDesc is public: a host with its own skeleton (INTEGRATION.md's Donut host) fills it without glTF.
+   Per vertex of the WHOLE stream: joints (JOINTS_0, 4 x u16), weights (WEIGHTS_0, 4 x f32; all zero = unskinned), the bind-pose normals (3 x f32) and tangents (4 x f32, w the
+   handedness). The morph displacements of all deformed geometries, three arrays of numMorphDeltaFloats floats: target i of vertex v (counted from the range's firstVertex) of a
+   range is at firstMorphDelta + (i * numVertices + v) * 3. One PtSkinRange per deformed geometry: its vertices, its joint palette [firstMatrix, + numMatrices) (numMatrices 0: morph
+   only), its targets (numTargets 0: skin only) with their weights at firstWeight, and the geometry's PT_GEOM_HAS_* flags. Ranges do not overlap; geometries of one skinned mesh share a palette.
+   Limits: four joints a vertex (JOINTS_0 / WEIGHTS_0 only); normals by the inverse transpose of each joint matrix, as on the host; the palette is binary64. */
+typedef struct PtSkinRange { uint32_t firstVertex, numVertices, firstMatrix, numMatrices, firstMorphDelta, numTargets, firstWeight, geometryFlags; } PtSkinRange;
+typedef struct PtSkinningDesc {
+    uint32_t numVertices, numRanges, numMatrices, numMorphWeights;      /* numMatrices / numMorphWeights: what a frame's palette / weight array must hold */
+    const uint16_t* joints; const float* weights; const float* normals; const float* tangents;
+    const float* morphPositionDeltas; const float* morphNormalDeltas; const float* morphTangentDeltas; uint64_t numMorphDeltaFloats;
+    const PtSkinRange* ranges;
+} PtSkinningDesc;
+/* the file's description; its pointers stay valid until pt_gltf_animation_free. A mesh shared by several nodes appears once, with the last node's skin and weights. Host only. */
+int32_t pt_gltf_animation_skinning(pt_gltf_animation* anim, PtSkinningDesc* out);
+/* a frame's part: the joint matrices inverse(meshNodeWorld) * jointWorld_k * inverseBind_k, 16 doubles each, column major, at the ranges' firstMatrix, and the morph weights of every
+   range at its firstWeight. Returns 0 and writes both (capacities at least the description's counts), or the negative error; with both capacities 0 it is a query: *matrices /
+   *morphWeights untouched, the return value is numMatrices (the weights' count is the description's numMorphWeights). A mesh node whose world transform is singular at
+   that time has no palette: -PT_ERROR_UNSUPPORTED (the host pose leaves such a mesh unskinned). Host only. */
+int32_t pt_gltf_animation_palette(pt_gltf_animation* anim, uint32_t animation, float timeSeconds, double* matrices, uint32_t capacityMatrices, double* morphWeights, uint32_t capacityWeights);
 void    pt_gltf_animation_free(pt_gltf_animation* anim);
 /* raw-buffer path: the same data the bakers upload (GeometryData/InstanceData/PTMaterialData/SubInstanceData, Rtxpt/Sample.cpp:2319-2384) */
 int32_t pt_set_geometry(pt_context* ctx, const PtGeometryBuffers* buffers, const PtGeometryDesc* geometries, uint32_t numGeometries,
@@ -597,6 +620,25 @@ int32_t pt_set_previous_pose(pt_context* ctx, const PtInstanceDesc* instances, u
 /* deformed meshes' vertex normals / tangents (Donut's skinning rewrites them with the positions, Sample.cpp:1170-1198): replaces the packed streams of pt_set_geometry (either may be NULL)
    and rewrites the shading records; the BVH does not depend on them. Resets the accumulation like pt_animate. */
 int32_t pt_animate_normals(pt_context* ctx, const uint32_t* normalsSnorm8, const uint32_t* tangentsSnorm8, uint32_t numVertices);
+/* Skins and morph targets evaluated on the device (Donut's SkinnedMeshInstance pass followed by UpdateSkinnedBLASs, Sample.cpp:1065, 1170-1198; Donut is not vendored, the
+ * per-vertex arithmetic is PtSkinningDesc's, above — UNPINNED): a frame hands over a joint palette and morph weights (a few KB), not posed vertex streams.
+ * pt_set_skinning validates the description against the scene (PT_ERROR_INVALID_ARGUMENT with a message: the vertex count must be the scene's, ranges inside the stream and
+ * disjoint, matrix / weight / displacement offsets inside their arrays) and uploads it once; the positions the scene holds at that moment are kept on the device as the bind
+ * pose. NULL removes it; a later pt_set_geometry invalidates it.
+ * pt_animate_skinned is ONE scene refresh (pt_set_motion_history): every argument is validated first (numMatrices / numWeights must be the description's) — a rejected call
+ * changes nothing —, then the ranges' current pose becomes the previous one, `instances` (may be NULL) and the palette are uploaded, one kernel rewrites positions, normals
+ * and tangents of the ranges in place (bit for bit what pt_gltf_animation_positions / _normals give), the shading records of the touched geometries are rewritten, the BVH
+ * is refitted (or rebuilt), the lights re-baked and the accumulation reset, as by pt_animate. The host copies of the streams are brought back from the device only when
+ * something reads them (a re-upload after pt_set_materials, pt_animate_ranges, pt_animate_normals). */
+int32_t pt_set_skinning(pt_context* ctx, const PtSkinningDesc* desc);
+int32_t pt_animate_skinned(pt_context* ctx, const PtInstanceDesc* instances, uint32_t numInstances, const double* matrices, uint32_t numMatrices,
+                           const double* morphWeights, uint32_t numWeights, int32_t rebuild);
+/* device time of the skinning kernel of the last pt_animate_skinned call [ms] */
+int32_t pt_get_skinning_time(pt_context* ctx, double* kernelMilliseconds);
+/* the current vertex streams read back from the device (what a host uses to get posed vertices back): positions / prevPositions xyz per vertex, normals / tangents SNORM8
+ * words; any pointer may be NULL; prevPositions only with the motion history on (else PT_ERROR_INVALID_ARGUMENT). Returns the vertex count (capacity 0, or below it: a query,
+ * nothing written) or the negative error. */
+int32_t pt_get_vertex_streams(pt_context* ctx, float* positions, float* prevPositions, uint32_t* normalsSnorm8, uint32_t* tangentsSnorm8, uint32_t capacityVertices);
 /* BackBufferResizing / RenderTargets::Init (Rtxpt/SampleCommon/RenderTargets.cpp:35-240) */
 int32_t pt_resize(pt_context* ctx, uint32_t width, uint32_t height);
 /* Render -> SampleRenderCode -> PathTrace -> AccumulationPass for samples [first, first+count) (Rtxpt/Sample.cpp:1891-2313, 2438-2559, 2770-2778).

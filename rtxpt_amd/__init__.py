@@ -27,7 +27,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERROR_INVALID_ARGUMENT", 2: "PT_ERROR_NO_DEVICE", 3
 
 # every symbol include/mi355pt.h declares
 EXPORTS = [
-    "pt_create", "pt_destroy", "pt_get_last_error", "pt_load_scene_gltf", "pt_gltf_animation_load", "pt_gltf_animation_instances", "pt_gltf_animation_positions", "pt_gltf_animation_normals", "pt_animate_normals", "pt_gltf_animation_free", "pt_set_geometry", "pt_set_instances", "pt_set_materials",
+    "pt_create", "pt_destroy", "pt_get_last_error", "pt_load_scene_gltf", "pt_gltf_animation_load", "pt_gltf_animation_instances", "pt_gltf_animation_positions", "pt_gltf_animation_normals", "pt_gltf_animation_skinning", "pt_gltf_animation_palette", "pt_set_skinning", "pt_animate_skinned", "pt_get_skinning_time", "pt_get_vertex_streams", "pt_animate_normals", "pt_gltf_animation_free", "pt_set_geometry", "pt_set_instances", "pt_set_materials",
     "pt_set_environment", "pt_set_environment_cube", "pt_image_read_dds_cube", "pt_set_environment_bake", "pt_set_environment_compression", "pt_set_procedural_sky", "pt_procedural_sky_default_params", "pt_procedural_sky_update", "pt_env_bake_lights", "pt_set_lights", "pt_set_light_importance_boost", "pt_set_local_light_sampling", "pt_get_light_feedback", "pt_set_neeat", "pt_set_view_projection", "pt_neeat_reset", "pt_get_neeat_tables", "pt_neeat_pack_feedback", "pt_neeat_unpack_feedback", "pt_bridge_camera", "pt_set_camera", "pt_default_settings", "pt_set_settings", "pt_animate",
     "pt_resize", "pt_render", "pt_reset_accumulation", "pt_map_radiance", "pt_unmap_radiance", "pt_shard_info", "pt_pack_shard",
     "pt_unpack_shard", "pt_device_radiance", "pt_trace_closest", "pt_trace_visibility", "pt_get_lights", "pt_get_env_cube", "pt_get_subinstances",
@@ -409,6 +409,42 @@ class PtAnalyticLightDesc(ctypes.Structure):
                 ("radius", ctypes.c_float), ("innerAngle", ctypes.c_float), ("outerAngle", ctypes.c_float)]
 
 
+class PtSkinRange(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("firstVertex", "numVertices", "firstMatrix", "numMatrices", "firstMorphDelta", "numTargets", "firstWeight", "geometryFlags")]
+
+
+class PtSkinningDesc(ctypes.Structure):
+    _fields_ = [("numVertices", ctypes.c_uint32), ("numRanges", ctypes.c_uint32), ("numMatrices", ctypes.c_uint32), ("numMorphWeights", ctypes.c_uint32),
+                ("joints", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("normals", ctypes.c_void_p), ("tangents", ctypes.c_void_p),
+                ("morphPositionDeltas", ctypes.c_void_p), ("morphNormalDeltas", ctypes.c_void_p), ("morphTangentDeltas", ctypes.c_void_p), ("numMorphDeltaFloats", ctypes.c_uint64),
+                ("ranges", ctypes.c_void_p)]
+
+
+SKIN_RANGE_DTYPE = np.dtype([(k, np.uint32) for k in ("firstVertex", "numVertices", "firstMatrix", "numMatrices", "firstMorphDelta", "numTargets", "firstWeight", "geometryFlags")])
+
+
+class SkinningDesc:
+    """PtSkinningDesc as numpy arrays (PathTracer.set_skinning's argument): joints uint16 [V, 4], weights float32 [V, 4], normals float32 [V, 3], tangents float32 [V, 4]
+    (bind pose, per vertex of the whole stream), morph_position / _normal / _tangent_deltas float32 [D], ranges SKIN_RANGE_DTYPE [R], num_matrices, num_morph_weights."""
+    def __init__(self, joints, weights, normals, tangents, ranges, num_matrices, num_morph_weights=0, morph_position_deltas=None, morph_normal_deltas=None, morph_tangent_deltas=None):
+        z = np.zeros(0, np.float32)
+        self.joints = np.ascontiguousarray(joints, np.uint16).reshape(-1, 4); self.weights = np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+        self.normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3); self.tangents = np.ascontiguousarray(tangents, np.float32).reshape(-1, 4)
+        self.morph_position_deltas = np.ascontiguousarray(z if morph_position_deltas is None else morph_position_deltas, np.float32).reshape(-1)
+        self.morph_normal_deltas = np.ascontiguousarray(np.zeros_like(self.morph_position_deltas) if morph_normal_deltas is None else morph_normal_deltas, np.float32).reshape(-1)
+        self.morph_tangent_deltas = np.ascontiguousarray(np.zeros_like(self.morph_position_deltas) if morph_tangent_deltas is None else morph_tangent_deltas, np.float32).reshape(-1)
+        self.ranges = np.ascontiguousarray(ranges, SKIN_RANGE_DTYPE).reshape(-1); self.num_matrices = int(num_matrices); self.num_morph_weights = int(num_morph_weights)
+
+    def struct(self):
+        """the ctypes PtSkinningDesc over these arrays (which must outlive it)"""
+        assert len(self.weights) == len(self.joints) == len(self.normals) == len(self.tangents) and len(self.morph_normal_deltas) == len(self.morph_tangent_deltas) == len(self.morph_position_deltas)
+        d = PtSkinningDesc(len(self.joints), len(self.ranges), self.num_matrices, self.num_morph_weights)
+        d.joints, d.weights, d.normals, d.tangents = (a.ctypes.data for a in (self.joints, self.weights, self.normals, self.tangents))
+        d.morphPositionDeltas, d.morphNormalDeltas, d.morphTangentDeltas = (a.ctypes.data for a in (self.morph_position_deltas, self.morph_normal_deltas, self.morph_tangent_deltas))
+        d.numMorphDeltaFloats = len(self.morph_position_deltas); d.ranges = self.ranges.ctypes.data
+        return d
+
+
 class GltfAnimation:
     """pt_gltf_animation_*: the animations of a .gltf / .glb file, evaluated on the host into the instance transforms pt_animate takes."""
     def __init__(self, path):
@@ -446,6 +482,29 @@ class GltfAnimation:
         nrm, tan = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         if n: assert f(self.h, animation, float(t), _p(nrm), _p(tan), n) == n
         return nrm, tan
+
+    def skinning(self):
+        """pt_gltf_animation_skinning: the file's static skinning data as a SkinningDesc (copies; PathTracer.set_skinning's argument)"""
+        f = self.L.pt_gltf_animation_skinning; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(PtSkinningDesc)]; f.restype = ctypes.c_int32
+        d = PtSkinningDesc(); r = f(self.h, ctypes.byref(d))
+        if r != PT_OK: raise PtError(r, "pt_gltf_animation_skinning")
+        def arr(ptr, dtype, count): return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dtype))), (count,)).copy() if ptr and count else np.zeros(0, dtype)
+        nv, nd = d.numVertices, d.numMorphDeltaFloats
+        ranges = np.frombuffer(ctypes.string_at(d.ranges, d.numRanges * SKIN_RANGE_DTYPE.itemsize), SKIN_RANGE_DTYPE).copy() if d.numRanges else np.zeros(0, SKIN_RANGE_DTYPE)
+        return SkinningDesc(arr(d.joints, np.uint16, 4 * nv), arr(d.weights, np.float32, 4 * nv), arr(d.normals, np.float32, 3 * nv), arr(d.tangents, np.float32, 4 * nv), ranges, d.numMatrices, d.numMorphWeights,
+                            arr(d.morphPositionDeltas, np.float32, nd), arr(d.morphNormalDeltas, np.float32, nd), arr(d.morphTangentDeltas, np.float32, nd))
+
+    def palette(self, t, animation=0):
+        """pt_gltf_animation_palette: (matrices float64 [M, 16] column major, morph weights float64 [W]) at time t [s] — pt_animate_skinned's per-frame arguments"""
+        f = self.L.pt_gltf_animation_palette; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        n = f(self.h, animation, float(t), None, 0, None, 0)
+        if n < 0: raise PtError(-n, "pt_gltf_animation_palette")
+        if not hasattr(self, "_numMorphWeights"): self._numMorphWeights = self.skinning().num_morph_weights
+        m = np.zeros((n, 16), np.float64); w = np.zeros(self._numMorphWeights, np.float64)
+        if n or len(w):
+            r = f(self.h, animation, float(t), _p(m), n, _p(w), len(w))
+            if r < 0: raise PtError(-r, "pt_gltf_animation_palette")
+        return m, w
 
     def close(self):
         if self.h: self.L.pt_gltf_animation_free(self.h); self.h = ctypes.c_void_p()
@@ -1252,6 +1311,42 @@ class PathTracer:
         n = len(normals) if normals is not None else len(tangents)
         a = None if normals is None else np.ascontiguousarray(normals, np.uint32); b = None if tangents is None else np.ascontiguousarray(tangents, np.uint32)
         self._chk(f(self.h, _p(a), _p(b), n), "pt_animate_normals")
+
+    def set_skinning(self, desc):
+        """pt_set_skinning: a SkinningDesc (GltfAnimation.skinning(), or a host's own) uploaded once; the scene's current positions become the bind pose. None removes it."""
+        f = self.L.pt_set_skinning; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        if desc is None: self._chk(f(self.h, None), "pt_set_skinning"); return
+        d = desc.struct()
+        self._chk(f(self.h, ctypes.byref(d)), "pt_set_skinning")
+
+    def animate_skinned(self, instances=None, matrices=None, morph_weights=None, rebuild=False):
+        """pt_animate_skinned: one scene refresh from a joint palette (float64 [M, 16], column major) and morph weights (float64 [W]), posed on the device"""
+        f = self.L.pt_animate_skinned; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32]; f.restype = ctypes.c_int32
+        i = None if instances is None else np.ascontiguousarray(instances)
+        m = None if matrices is None else np.ascontiguousarray(matrices, np.float64).reshape(-1, 16); w = None if morph_weights is None else np.ascontiguousarray(morph_weights, np.float64).reshape(-1)
+        self._chk(f(self.h, _p(i), 0 if i is None else len(i), _p(m), 0 if m is None else len(m), _p(w), 0 if w is None else len(w), 1 if rebuild else 0), "pt_animate_skinned")
+
+    def animate_gltf(self, anim, t, animation=0, rebuild=False):
+        """a GltfAnimation's frame at time t [s] on the device: its instances and palette through animate_skinned (set_skinning(anim.skinning()) first)"""
+        m, w = anim.palette(t, animation)
+        self.animate_skinned(anim.instances(t, animation), m, w, rebuild)
+
+    def skinning_time(self):
+        """pt_get_skinning_time: the skinning kernel's device time in the last animate_skinned call [ms]"""
+        f = self.L.pt_get_skinning_time; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]; f.restype = ctypes.c_int32
+        ms = ctypes.c_double(); self._chk(f(self.h, ctypes.byref(ms)), "pt_get_skinning_time"); return ms.value
+
+    def vertex_streams(self, previous=False):
+        """pt_get_vertex_streams: the device's current streams, (positions float32 [V, 3], normals uint32 [V], tangents uint32 [V]); previous=True: the previous pose's
+        positions as a fourth array (motion history on)"""
+        f = self.L.pt_get_vertex_streams; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        n = f(self.h, None, None, None, None, 0)
+        if n < 0: self._chk(-n, "pt_get_vertex_streams")
+        p = np.zeros((n, 3), np.float32); q = np.zeros((n, 3), np.float32) if previous else None; nr = np.zeros(n, np.uint32); tg = np.zeros(n, np.uint32)
+        if n:
+            r = f(self.h, _p(p), _p(q), _p(nr), _p(tg), n)
+            if r < 0: self._chk(-r, "pt_get_vertex_streams")
+        return (p, nr, tg, q) if previous else (p, nr, tg)
 
     # ---- per-frame state
     def set_camera(self, cam):

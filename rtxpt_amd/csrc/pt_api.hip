@@ -179,6 +179,27 @@ static int32_t motion_history_sync(pt_context* c) {
     c->prevAllStale = false; c->prevStaleRanges.clear();
     return PT_OK;
 }
+// (pt_set_skinning) the description leaves the device
+static void skin_drop(pt_context* c) {
+    if (c->skinSet) (void)hipSetDevice(c->device);
+    c->skinSet = false; c->skinRanges.clear(); c->skinStale.clear(); c->skinMatrices = c->skinWeights = 0u; memset(&c->skinView, 0, sizeof(c->skinView));
+    c->dSkinJoints.free(); c->dSkinWeights.free(); c->dSkinNormals.free(); c->dSkinTangents.free(); c->dSkinBind.free(); c->dSkinDeltaP.free(); c->dSkinDeltaN.free(); c->dSkinDeltaT.free();
+    c->dSkinRanges.free(); c->dSkinRangeStart.free(); c->dSkinMatrices.free(); c->dSkinMorphWeights.free();
+}
+// (pt_animate_skinned) the host copies of the vertex streams <- the device's, over the ranges a device pose rewrote: paid by whoever reads the copies, not by every frame
+static int32_t sync_mirrors(pt_context* c) {
+    if (!c->mirrorsStale) return PT_OK;
+    for (size_t r = 0; r + 1 < c->mirrorRanges.size(); r += 2) {
+        const size_t first = c->mirrorRanges[r], count = c->mirrorRanges[r + 1];
+        if (!count || first + count > c->normals.size()) continue;
+        PT_CHECK_HIP(c, hipMemcpyAsync(c->positions.data() + 3 * first, c->dPositions.p + 3 * first, 12 * count, hipMemcpyDeviceToHost, c->stream));
+        PT_CHECK_HIP(c, hipMemcpyAsync(c->normals.data() + first, c->dNormals.p + first, 4 * count, hipMemcpyDeviceToHost, c->stream));
+        PT_CHECK_HIP(c, hipMemcpyAsync(c->tangents.data() + first, c->dTangents.p + first, 4 * count, hipMemcpyDeviceToHost, c->stream));
+    }
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+    c->mirrorsStale = false; c->mirrorRanges.clear();
+    return PT_OK;
+}
 int finalize_geometry(pt_context* c) {
     c->subInstances.clear(); c->subInstToInstGeom.clear(); c->primInfo.clear(); c->subInstFirstPrim.clear();
     for (size_t i = 0; i < c->instances.size(); i++) {
@@ -451,7 +472,7 @@ int bake_env_cube(pt_context* c) {
 int prepare(pt_context* c) {
     if (c->texDirty) { int r = upload_textures(c); if (r != PT_OK) return r; refresh_scene_view(c); c->lightsDirty = true; c->envCubeDirty = true; }
     if (c->envEnabled && c->envCubeDirty) { int r = bake_env_cube(c); if (r != PT_OK) return r; }
-    if (c->geomDirty) { int r = finalize_geometry(c); if (r != PT_OK) return r; }
+    if (c->geomDirty) { int r = sync_mirrors(c); if (r != PT_OK) return r; r = finalize_geometry(c); if (r != PT_OK) return r; }      // (re-uploads the host copies of the streams)
     if (c->lightsDirty) { int r = bake_lights(c); if (r != PT_OK) return r; }
     // the camera moved under a frustum boost: weights and proxies only (the lights themselves do not depend on it)
     else if (c->weightsDirty && !c->lights.empty()) {
@@ -613,6 +634,7 @@ int32_t pt_destroy(pt_context* c) {
     c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
     c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
     relax_free(c); taa_free(c); bloom_free(c); taau_free(c);
+    skin_drop(c); for (int e = 0; e < 2; e++) if (c->skinEvents[e]) (void)hipEventDestroy(c->skinEvents[e]);
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
     c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
     if (c->bvhAllocated) bvh_free(c->bvh);
@@ -650,6 +672,7 @@ int32_t pt_set_geometry(pt_context* c, const PtGeometryBuffers* b, const PtGeome
     c->geometries.resize(nGeoms); memcpy(c->geometries.data(), geoms, sizeof(GeometryDesc) * nGeoms);
     c->meshes.resize(nMeshes); memcpy(c->meshes.data(), meshes, sizeof(MeshDesc) * nMeshes);
     c->geomDirty = true;
+    skin_drop(c); c->mirrorsStale = false; c->mirrorRanges.clear();      // a new scene: the skinning description was of another one, and the host copies above are the truth again
     relax_drop_history(c); taa_drop_history(c); taau_drop_history(c);      // a new scene: the denoiser's and the two resolves' histories are of another one
     return PT_OK;
 }
@@ -1015,6 +1038,7 @@ int32_t pt_animate_ranges(pt_context* c, const PtInstanceDesc* inst, uint32_t nI
     if (positions && (size_t)nVerts * 3 != c->positions.size()) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate: vertex count must not change");
     if (positions && vertexRanges) for (uint32_t r = 0; r < nRanges; r++) if ((unsigned long long)vertexRanges[2 * r] + vertexRanges[2 * r + 1] > nVerts) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_ranges: vertex range beyond the vertex count");
     if (inst) for (uint32_t i = 0; i < nInst; i++) if (inst[i].meshIndex != c->instances[i].meshIndex) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate: topology must not change");
+    if (positions) { int r = sync_mirrors(c); if (r != PT_OK) return r; }      // (after pt_animate_skinned the host copy written below lags the device)
     // (every argument is validated by now: a rejected call must not advance the motion history — the next build pass would report zero object motion for what
     // moved last frame)
     if (c->motionHistory) {      // one scene refresh: what is current becomes previous (before the uploads below overwrite it)
@@ -1082,6 +1106,7 @@ int32_t pt_animate_normals(pt_context* c, const uint32_t* normals, const uint32_
     (void)hipSetDevice(c->device);
     if (c->geomDirty || c->texDirty) { int r = prepare(c); if (r != PT_OK) return r; }
     if ((normals && nVerts != c->normals.size()) || (tangents && nVerts != c->tangents.size())) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_normals: vertex count must not change");
+    { int r = sync_mirrors(c); if (r != PT_OK) return r; }      // (after pt_animate_skinned the host copies written below lag the device)
     if (normals) { memcpy(c->normals.data(), normals, 4 * (size_t)nVerts); PT_CHECK_HIP(c, c->dNormals.upload(c->normals, c->stream)); }
     if (tangents) { memcpy(c->tangents.data(), tangents, 4 * (size_t)nVerts); PT_CHECK_HIP(c, c->dTangents.upload(c->tangents, c->stream)); }
     refresh_scene_view(c);
@@ -1090,6 +1115,112 @@ int32_t pt_animate_normals(pt_context* c, const uint32_t* normals, const uint32_
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     return PT_OK;
+}
+
+// ---- skins and morph targets on the device (pt_skin.h: the per-vertex text, shared with the host pose of pt_gltf.cpp; pt_skin.hip: k_skin)
+int32_t pt_set_skinning(pt_context* c, const PtSkinningDesc* d) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!d) { skin_drop(c); return PT_OK; }
+    if (c->geomDirty || c->texDirty) { int r = prepare(c); if (r != PT_OK) return r; }
+    const size_t nv = c->positions.size() / 3;
+    if (d->numVertices != nv) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: vertex count differs from the scene's");
+    if ((d->numRanges && !d->ranges) || (nv && (!d->joints || !d->weights || !d->normals || !d->tangents))) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: null array");
+    std::vector<std::pair<uint64_t, uint64_t>> spans; std::vector<uint32_t> start(1, 0u), stale; bool morphs = false;
+    for (uint32_t i = 0; i < d->numRanges; i++) {
+        const PtSkinRange& r = d->ranges[i];
+        if ((uint64_t)r.firstVertex + r.numVertices > nv) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: range beyond the vertex stream");
+        if ((uint64_t)r.firstMatrix + r.numMatrices > d->numMatrices) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: a range's matrices lie beyond numMatrices");
+        if (r.numTargets) {
+            if ((uint64_t)r.firstWeight + r.numTargets > d->numMorphWeights) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: a range's morph weights lie beyond numMorphWeights");
+            if ((uint64_t)r.firstMorphDelta + (uint64_t)r.numTargets * r.numVertices * 3ull > d->numMorphDeltaFloats) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: a range's morph displacements lie beyond numMorphDeltaFloats");
+            morphs = true;
+        }
+        if (r.numVertices) spans.push_back({r.firstVertex, (uint64_t)r.firstVertex + r.numVertices});
+        start.push_back(start.back() + r.numVertices); stale.push_back(r.firstVertex); stale.push_back(r.numVertices);      // (inside the stream and disjoint, checked below: the sum fits)
+    }
+    if (morphs && (!d->morphPositionDeltas || !d->morphNormalDeltas || !d->morphTangentDeltas)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: null morph displacement array");
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); i++) if (spans[i].first < spans[i - 1].second) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_set_skinning: ranges overlap");
+    skin_drop(c);
+    const size_t nd = morphs ? (size_t)d->numMorphDeltaFloats : 0; hipStream_t st = c->stream;
+    PT_CHECK_HIP(c, c->dSkinJoints.upload(d->joints, 4 * nv, st)); PT_CHECK_HIP(c, c->dSkinWeights.upload(d->weights, 4 * nv, st));
+    PT_CHECK_HIP(c, c->dSkinNormals.upload(d->normals, 3 * nv, st)); PT_CHECK_HIP(c, c->dSkinTangents.upload(d->tangents, 4 * nv, st));
+    PT_CHECK_HIP(c, c->dSkinDeltaP.upload(d->morphPositionDeltas, nd, st)); PT_CHECK_HIP(c, c->dSkinDeltaN.upload(d->morphNormalDeltas, nd, st)); PT_CHECK_HIP(c, c->dSkinDeltaT.upload(d->morphTangentDeltas, nd, st));
+    PT_CHECK_HIP(c, c->dSkinRanges.upload(d->ranges, d->numRanges, st)); PT_CHECK_HIP(c, c->dSkinRangeStart.upload(start, st));
+    PT_CHECK_HIP(c, c->dSkinMatrices.resize(16 * (size_t)d->numMatrices)); PT_CHECK_HIP(c, c->dSkinMorphWeights.resize(d->numMorphWeights));
+    // the bind pose: dPositions is overwritten by every pose
+    PT_CHECK_HIP(c, c->dSkinBind.resize(3 * nv)); if (nv) PT_CHECK_HIP(c, hipMemcpyAsync(c->dSkinBind.p, c->dPositions.p, 12 * nv, hipMemcpyDeviceToDevice, st));
+    PT_CHECK_HIP(c, hipStreamSynchronize(st));      // (the uploads read the caller's arrays)
+    SkinView& v = c->skinView;
+    v.joints = c->dSkinJoints.p; v.weights = c->dSkinWeights.p; v.normals = c->dSkinNormals.p; v.tangents = c->dSkinTangents.p; v.bindPositions = c->dSkinBind.p;
+    v.deltasP = c->dSkinDeltaP.p; v.deltasN = c->dSkinDeltaN.p; v.deltasT = c->dSkinDeltaT.p; v.ranges = c->dSkinRanges.p; v.rangeStart = c->dSkinRangeStart.p;
+    v.numRanges = d->numRanges; v.total = start.back();
+    c->skinRanges.assign(d->ranges, d->ranges + d->numRanges); c->skinStale = stale; c->skinMatrices = d->numMatrices; c->skinWeights = d->numMorphWeights; c->skinSet = true;
+    return PT_OK;
+}
+int32_t pt_animate_skinned(pt_context* c, const PtInstanceDesc* inst, uint32_t nInst, const double* matrices, uint32_t numMatrices, const double* morphWeights, uint32_t numWeights, int32_t rebuild) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (c->geomDirty || c->texDirty) { int r = prepare(c); if (r != PT_OK) return r; }
+    if (!c->skinSet) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_skinned: pt_set_skinning first");
+    if (inst && nInst != c->instances.size()) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_skinned: instance count must not change");
+    if (inst) for (uint32_t i = 0; i < nInst; i++) if (inst[i].meshIndex != c->instances[i].meshIndex) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_skinned: topology must not change");
+    if (numMatrices != c->skinMatrices || (numMatrices && !matrices)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_skinned: the palette must hold the description's numMatrices matrices");
+    if (numWeights != c->skinWeights || (numWeights && !morphWeights)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_animate_skinned: the morph weights must be the description's numMorphWeights");
+    // (every argument is validated by now: a rejected call must not advance the motion history, pt_animate_ranges)
+    if (c->motionHistory) {      // one scene refresh: what is current becomes previous, before k_skin overwrites it; the ranges are what differs afterwards
+        int r = motion_history_sync(c); if (r != PT_OK) return r;
+        c->prevStaleRanges = c->skinStale;
+    }
+    if (inst) { memcpy(c->instances.data(), inst, sizeof(InstanceDesc) * nInst); PT_CHECK_HIP(c, c->dInstances.upload(c->instances, c->stream)); }
+    if (numMatrices) PT_CHECK_HIP(c, hipMemcpyAsync(c->dSkinMatrices.p, matrices, 128 * (size_t)numMatrices, hipMemcpyHostToDevice, c->stream));
+    if (numWeights) PT_CHECK_HIP(c, hipMemcpyAsync(c->dSkinMorphWeights.p, morphWeights, 8 * (size_t)numWeights, hipMemcpyHostToDevice, c->stream));
+    for (int e = 0; e < 2; e++) if (!c->skinEvents[e]) PT_CHECK_HIP(c, hipEventCreate(&c->skinEvents[e]));
+    PT_CHECK_HIP(c, hipEventRecord(c->skinEvents[0], c->stream));
+    launch_skin(c->skinView, c->dSkinMatrices.p, c->dSkinMorphWeights.p, c->dPositions.p, c->dNormals.p, c->dTangents.p, c->stream);
+    PT_CHECK_HIP(c, hipEventRecord(c->skinEvents[1], c->stream));
+    c->mirrorsStale = true; c->mirrorRanges = c->skinStale;
+    refresh_scene_view(c);
+    for (size_t s = 0; s < c->subInstToInstGeom.size(); s++) {      // the shading records of the sub-instances (= primitive ranges) of the geometries that hold a posed vertex
+        const GeometryDesc& gd = c->geometries[c->subInstToInstGeom[s].y];
+        bool touched = false;
+        for (size_t r = 0; r < c->skinRanges.size() && !touched; r++) { const PtSkinRange& k = c->skinRanges[r]; touched = k.numVertices && k.firstVertex < gd.vertexOffset + gd.numVertices && gd.vertexOffset < k.firstVertex + k.numVertices; }
+        if (touched) launch_shade_tris(c->dsc, c->subInstFirstPrim[s], gd.numIndices / 3u, c->dShadeTris.p, c->stream);
+    }
+    hipEvent_t e0, e1; PT_CHECK_HIP(c, hipEventCreate(&e0)); PT_CHECK_HIP(c, hipEventCreate(&e1));
+    PT_CHECK_HIP(c, hipEventRecord(e0, c->stream));
+    if (rebuild) {                                     // (pt_animate_ranges: a rebuild between animated frames is PLOC on the device)
+        if (c->bvh.builder == BVH_BUILDER_SAH || c->bvh.builder == BVH_BUILDER_PLOC_OPT) c->bvh.builder = BVH_BUILDER_PLOC;
+        PT_CHECK_HIP(c, bvh_build(c->bvh, c->dsc, c->numTris, c->stream));
+    } else PT_CHECK_HIP(c, bvh_refit(c->bvh, c->dsc, c->numTris, c->stream));
+    c->dsc.nodes = c->bvh.bvh2Stale ? nullptr : c->bvh.nodes;
+    PT_CHECK_HIP(c, hipEventRecord(e1, c->stream));
+    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));      // the call's one wait (the palette and the instances are the caller's arrays)
+    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); if (rebuild) c->buildMs = ms; else c->refitMs = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    ms = 0; (void)hipEventElapsedTime(&ms, c->skinEvents[0], c->skinEvents[1]); c->skinMs = ms;
+    const bool lightsWereDirty = c->lightsDirty;
+    c->lightsDirty = true;                    // emissive triangle lights move with the geometry
+    c->accumCount = 0;
+    PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
+    return bake_lights(c, !lightsWereDirty);
+}
+int32_t pt_get_skinning_time(pt_context* c, double* ms) { if (!c || !ms) return PT_ERROR_INVALID_ARGUMENT; *ms = c->skinMs; return PT_OK; }
+int32_t pt_get_vertex_streams(pt_context* c, float* positions, float* prevPositions, uint32_t* normals, uint32_t* tangents, uint32_t capacityVertices) {
+    if (!c) return -PT_ERROR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (c->geomDirty || c->texDirty) { int r = prepare(c); if (r != PT_OK) return -r; }
+    const size_t nv = c->positions.size() / 3;
+    if (capacityVertices < nv || !nv) return (int32_t)nv;
+    if (prevPositions && !(c->motionHistory && c->dPrevPositions.p && c->dPrevPositions.n >= 3 * nv)) return -fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_vertex_streams: the previous positions exist only with the motion history on");
+    auto back = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
+    hipError_t e = back(positions, c->dPositions.p, 12 * nv);
+    if (e == hipSuccess) e = back(prevPositions, c->dPrevPositions.p, 12 * nv);
+    if (e == hipSuccess) e = back(normals, c->dNormals.p, 4 * nv);
+    if (e == hipSuccess) e = back(tangents, c->dTangents.p, 4 * nv);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return -fail(c, PT_ERROR_HIP, std::string("pt_get_vertex_streams: ") + hipGetErrorString(e));
+    return (int32_t)nv;
 }
 static_assert(sizeof(::PtStablePlanesParams) == sizeof(ptk::StablePlanesParams) && sizeof(::PtStablePlane) == sizeof(ptk::StablePlane), "stable-plane ABI");
 int32_t pt_stable_planes_plane_stride(uint32_t width, uint32_t height, uint32_t* stride) { if (!stride) return PT_ERROR_INVALID_ARGUMENT; *stride = ptk::GenericTSComputePlaneStride(width, height); return PT_OK; }

@@ -14,6 +14,12 @@
 
 using namespace ptk;
 
+// what k_skin reads (pt_skin.hip): the device copies of a PtSkinningDesc's arrays, the bind-pose positions, the ranges and their prefix table (rangeStart[r]: the deformed
+// vertices before range r; numRanges + 1 entries, the last one `total`)
+struct SkinView {
+    const uint16_t* joints; const float* weights; const float* normals; const float* tangents; const float* bindPositions;
+    const float* deltasP; const float* deltasN; const float* deltasT; const PtSkinRange* ranges; const uint32_t* rangeStart; uint32_t numRanges, total;
+};
 template <typename T> struct DevBuf {
     T* p = nullptr; size_t n = 0;
     hipError_t resize(size_t count) {
@@ -139,6 +145,12 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // pt_set_motion_history: the previous frame's pose; the (first, count) vertex ranges in which it differs from the current one
     DevBuf<float> dPrevPositions; DevBuf<InstanceDesc> dPrevInstances; bool motionHistory = false, prevAllStale = false;
     std::vector<uint32_t> prevStaleRanges;
+    // pt_set_skinning: the description on the device (skinRanges: the host's copy of its ranges; skinStale: the (first, count) pairs of the ranges, what a device pose makes
+    // stale in the previous pose and in the host copies above). mirrorsStale: a device pose has rewritten dPositions / dNormals / dTangents since `positions` / `normals` /
+    // `tangents` were last equal to them (sync_mirrors brings mirrorRanges back before anything reads the host copies). skinMs: k_skin's device time in the last pt_animate_skinned
+    bool skinSet = false, mirrorsStale = false; std::vector<PtSkinRange> skinRanges; std::vector<uint32_t> skinStale, mirrorRanges; uint32_t skinMatrices = 0, skinWeights = 0; double skinMs = 0;
+    DevBuf<uint16_t> dSkinJoints; DevBuf<float> dSkinWeights, dSkinNormals, dSkinTangents, dSkinBind, dSkinDeltaP, dSkinDeltaN, dSkinDeltaT; DevBuf<PtSkinRange> dSkinRanges;
+    DevBuf<uint32_t> dSkinRangeStart; DevBuf<double> dSkinMatrices, dSkinMorphWeights; SkinView skinView = {}; hipEvent_t skinEvents[2] = {nullptr, nullptr};
     DevBuf<float> dPositions; DevBuf<ptk::float2> dUvs; DevBuf<GeometryDesc> dGeometries; DevBuf<InstanceDesc> dInstances;
     DevBuf<SubInstanceData> dSubInstances;
     DevBuf<ptk::AlphaPlane> dAlphaPlanes; DevBuf<unsigned char> dAlphaPool; DevBuf<ptk::ShadeTri> dShadeTris;
@@ -263,6 +275,8 @@ inline ptk::DenoiserBuffers dn_buffers(pt_context* c) {
     D.Roughness = c->dDnRoughness.p; D.DisocclusionThresholdMix = c->dDnDisocclusion.p; D.CombinedHistoryClampRelax = c->dDnHistoryClamp.p;
     return D;
 }
+// ---- pt_skin.hip: the device skinning pass over the ranges of `s`, in place on the scene's streams
+void launch_skin(const SkinView& s, const double* matrices, const double* morphWeights, float* positions, uint* normals, uint* tangents, hipStream_t st);
 // ---- pt_relax_api.hip: the device denoiser's history is dropped (resize to another size, new scene) / its buffers freed
 void relax_drop_history(pt_context* c);
 void relax_free(pt_context* c);

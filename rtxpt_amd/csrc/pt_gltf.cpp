@@ -4,6 +4,7 @@
 // buffers, accessors (float / normalised integer), node hierarchy (matrix or TRS), PNG (all colour types, bit depths, Adam7) via zlib, JPEG and .dds textures.
 // Output goes through the same raw-buffer entry points the bakers use (pt_set_materials / pt_set_geometry / pt_set_instances).
 #include "../../include/mi355pt.h"
+#include "pt_skin.h"
 #include <zlib.h>
 #include <cctype>
 #include <cmath>
@@ -186,11 +187,7 @@ M4 m4_trs(const double t[3], const double q[4], const double s[3]) {
     return r;
 }
 
-uint32_t pack_snorm8(const float* v, int n) {   // Packing.hlsli:127-140
-    uint32_t out = 0;
-    for (int i = 0; i < n; i++) { float c = v[i] < -1.f ? -1.f : (v[i] > 1.f ? 1.f : v[i]); out |= ((uint32_t)((int)(c * 127.0f)) & 0xFFu) << (8 * i); }
-    return out;
-}
+using ptskin::pack_snorm8;   // Packing.hlsli:127-140 (pt_skin.h: the device's skinning pass packs with the same text)
 uint32_t pack_texture_word(uint32_t index, uint32_t w, uint32_t h) {   // MaterialsBaker.cpp:497-508
     uint32_t mips = 1; { uint32_t m = w > h ? w : h; while (m > 1) { m >>= 1; mips++; } }
     uint32_t baseLOD = (uint32_t)lround(log2((double)w * (double)h));
@@ -669,6 +666,10 @@ struct pt_gltf_animation {
     struct Channel { int sampler, node, path; };                                       // path 0 translation, 1 rotation, 2 scale, 3 weights (morph targets)
     struct Anim { std::vector<Sampler> samplers; std::vector<Channel> channels; double duration = 0; };
     std::vector<Anim> anims;
+    // pt_gltf_animation_skinning: one range per deformed geometry; per range the mesh node whose weights it takes (-1: none); per palette the (mesh node, skin) it is of
+    struct Palette { int node, skin; uint32_t firstMatrix, numMatrices; };
+    bool skinningBuilt = false; std::vector<PtSkinRange> ranges; std::vector<Loader::MeshNode> rangeMorphNode; std::vector<uint32_t> rangeMorphTargets; std::vector<Palette> palettes;
+    uint32_t numMatrices = 0, numMorphWeights = 0;
 };
 namespace {
 void quat_normalize(double q[4]) { double l = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); if (l > 0) for (int i = 0; i < 4; i++) q[i] /= l; }
@@ -762,6 +763,29 @@ extern "C" void pt_gltf_animation_free(pt_gltf_animation* a) { delete a; }
 // normalize(SUM_k w_k inverse-transpose(J_k) n), its tangent normalize(SUM_k w_k J_k t.xyz) with the handedness kept (glTF 2.0 3.7.3.3 leaves the normal transform to the
 // implementation; the inverse transpose is the one that keeps normals perpendicular under the non-uniform scales a mesh node may carry). Morph targets' NORMAL / TANGENT displacements are added
 // before the skin and the sums renormalised.
+// the weights of a mesh node's morph targets at time t: the animation's "weights" channel of the node, else the node's own `weights`, else the mesh's; nT of them
+static std::vector<double> gltf_morph_weights(pt_gltf_animation* a, uint32_t animation, float t, const Loader::MeshNode& mn, uint32_t nT) {
+    Loader& L = a->L; const JValue* nodes = L.root.get("nodes"); std::vector<double> w;
+    if (animation < a->anims.size()) for (auto& c : a->anims[animation].channels) if (c.path == 3 && c.node == mn.node) sample_weights(a->anims[animation].samplers[(size_t)c.sampler], nT, (double)t, w);
+    if (w.empty() && nodes && (size_t)mn.node < nodes->size()) if (const JValue* jw = nodes->arr[(size_t)mn.node].get("weights")) for (auto& x : jw->arr) w.push_back(x.num);
+    if (w.empty()) w = L.meshWeights[(size_t)mn.mesh];
+    w.resize(nT, 0.0);
+    return w;
+}
+// the joint matrices of skin `sk` for the mesh under `meshNode`, from the node worlds visit() recorded: inverse(meshNodeWorld) * jointWorld_k * inverseBind_k. False: a skin
+// without joints, or a singular mesh node (the mesh stays unskinned)
+static bool gltf_joint_palette(Loader& L, const JValue& sk, int meshNode, std::vector<M4>& jm) {
+    const JValue* jl = sk.get("joints"); if (!jl || !jl->size()) return false;
+    std::vector<double> ibm; int comps = 0; const bool haveIbm = sk.get("inverseBindMatrices") && L.accessor(sk.intOr("inverseBindMatrices", -1), ibm, comps) && comps == 16 && ibm.size() == 16 * jl->size();
+    M4 invMesh; if (!m4_inverse(L.nodeWorld[(size_t)meshNode], invMesh)) return false;
+    jm.resize(jl->size());
+    for (size_t k = 0; k < jl->size(); k++) {
+        const int jn = (int)jl->arr[k].num; M4 w = (jn >= 0 && (size_t)jn < L.nodeWorld.size()) ? L.nodeWorld[(size_t)jn] : m4_identity();
+        M4 b = m4_identity(); if (haveIbm) memcpy(b.m, &ibm[16 * k], sizeof(b.m));
+        jm[k] = m4_mul(invMesh, m4_mul(w, b));
+    }
+    return true;
+}
 static int32_t gltf_animation_pose(pt_gltf_animation* a, uint32_t animation, float t, float* out, uint32_t* outN, uint32_t* outT, uint32_t capacityVertices) {
     if (!a || (capacityVertices && !out && !outN && !outT)) return -PT_ERROR_INVALID_ARGUMENT;
     try {
@@ -781,77 +805,36 @@ static int32_t gltf_animation_pose(pt_gltf_animation* a, uint32_t animation, flo
         // morph targets first (the specification applies them before the skin): p = base + SUM_i w_i * target_i. Weights: the animation's "weights" channel of the node,
         // else the node's own `weights`, else the mesh's
         if (!L.morphDeltas.empty()) {
-            const JValue* nodes = L.root.get("nodes");
             for (const Loader::MeshNode& mn : L.meshNodes) {
                 if ((size_t)mn.mesh >= L.meshes.size()) continue;
                 const PtMeshDesc& md = L.meshes[(size_t)mn.mesh];
                 uint32_t nT = 0; for (uint32_t g = 0; g < md.numGeometries; g++) if (L.geomMorph[md.firstGeometry + g].count > nT) nT = L.geomMorph[md.firstGeometry + g].count;
                 if (!nT) continue;
-                std::vector<double> w;
-                if (animation < a->anims.size()) for (auto& c : a->anims[animation].channels) if (c.path == 3 && c.node == mn.node) sample_weights(a->anims[animation].samplers[(size_t)c.sampler], nT, (double)t, w);
-                if (w.empty() && nodes && (size_t)mn.node < nodes->size()) if (const JValue* jw = nodes->arr[(size_t)mn.node].get("weights")) for (auto& x : jw->arr) w.push_back(x.num);
-                if (w.empty()) w = L.meshWeights[(size_t)mn.mesh];
-                w.resize(nT, 0.0);
+                const std::vector<double> w = gltf_morph_weights(a, animation, t, mn, nT);
                 for (uint32_t g = 0; g < md.numGeometries; g++) {
                     const PtGeometryDesc& gd = L.geoms[md.firstGeometry + g]; const Loader::GeomMorph& gm = L.geomMorph[md.firstGeometry + g];
-                    for (uint32_t v = 0; v < gd.numVertices; v++) for (int rr = 0; rr < 3; rr++) {
-                        double p = L.positions[3 * (size_t)(gd.vertexOffset + v) + rr];
-                        for (uint32_t i = 0; i < gm.count; i++) p += w[i] * (double)L.morphDeltas[gm.first + ((size_t)i * gd.numVertices + v) * 3 + rr];
-                        out[3 * (size_t)(gd.vertexOffset + v) + rr] = (float)p;
-                    }
+                    for (uint32_t v = 0; v < gd.numVertices; v++) { const size_t gv = gd.vertexOffset + v;
+                        ptskin::morph_position(&L.positions[3 * gv], L.morphDeltas.data() + gm.first, gd.numVertices, v, w.data(), gm.count, &out[3 * gv]); }
                     if (wantNT) for (uint32_t v = 0; v < gd.numVertices; v++) {      // n = normalize(base + SUM_i w_i dn_i), likewise the tangent's xyz (glTF 2.0 3.7.2.2); repacked for the unskinned case
-                        const size_t gv = gd.vertexOffset + v; double dn[3] = {0, 0, 0}, dt[3] = {0, 0, 0}; bool anyN = false, anyT = false;
-                        for (uint32_t i = 0; i < gm.count; i++) for (int rr = 0; rr < 3; rr++) {
-                            const float a = L.morphNormalDeltas[gm.first + ((size_t)i * gd.numVertices + v) * 3 + rr], b = L.morphTangentDeltas[gm.first + ((size_t)i * gd.numVertices + v) * 3 + rr];
-                            dn[rr] += w[i] * (double)a; dt[rr] += w[i] * (double)b; anyN = anyN || (a != 0.f && w[i] != 0.0); anyT = anyT || (b != 0.f && w[i] != 0.0); }
-                        if (anyN && (gd.flags & PT_GEOM_HAS_NORMAL)) { double q[3], l = 0; for (int rr = 0; rr < 3; rr++) { q[rr] = L.normalsF[3 * gv + rr] + dn[rr]; l += q[rr] * q[rr]; } l = sqrt(l);
-                            if (l > 0) { for (int rr = 0; rr < 3; rr++) nF[3 * gv + rr] = (float)(q[rr] / l); if (outN) outN[gv] = pack_snorm8(&nF[3 * gv], 3); } }
-                        if (anyT && (gd.flags & PT_GEOM_HAS_TANGENT)) { double q[3], l = 0; for (int rr = 0; rr < 3; rr++) { q[rr] = L.tangentsF[4 * gv + rr] + dt[rr]; l += q[rr] * q[rr]; } l = sqrt(l);
-                            if (l > 0) { for (int rr = 0; rr < 3; rr++) tF[4 * gv + rr] = (float)(q[rr] / l); if (outT) outT[gv] = pack_snorm8(&tF[4 * gv], 4); } }
+                        const size_t gv = gd.vertexOffset + v;
+                        ptskin::morph_frame(&L.normalsF[3 * gv], &L.tangentsF[4 * gv], L.morphNormalDeltas.data() + gm.first, L.morphTangentDeltas.data() + gm.first, gd.numVertices, v, w.data(), gm.count,
+                                            gd.flags, &nF[3 * gv], &tF[4 * gv], outN ? &outN[gv] : nullptr, outT ? &outT[gv] : nullptr);
                     }
                 }
             }
         }
         if (haveSkins) for (const Loader::SkinnedInstance& si : L.skinned) {
             if ((size_t)si.skin >= skins->size() || (size_t)si.mesh >= L.meshes.size()) continue;
-            const JValue& sk = skins->arr[(size_t)si.skin]; const JValue* jl = sk.get("joints"); if (!jl || !jl->size()) continue;
-            std::vector<double> ibm; int comps = 0; const bool haveIbm = sk.get("inverseBindMatrices") && L.accessor(sk.intOr("inverseBindMatrices", -1), ibm, comps) && comps == 16 && ibm.size() == 16 * jl->size();
-            M4 invMesh; if (!m4_inverse(L.nodeWorld[(size_t)si.node], invMesh)) continue;
-            std::vector<M4> jm(jl->size());
-            for (size_t k = 0; k < jl->size(); k++) {
-                const int jn = (int)jl->arr[k].num; M4 w = (jn >= 0 && (size_t)jn < L.nodeWorld.size()) ? L.nodeWorld[(size_t)jn] : m4_identity();
-                M4 b = m4_identity(); if (haveIbm) memcpy(b.m, &ibm[16 * k], sizeof(b.m));
-                jm[k] = m4_mul(invMesh, m4_mul(w, b));
-            }
+            std::vector<M4> jm; if (!gltf_joint_palette(L, skins->arr[(size_t)si.skin], si.node, jm)) continue;
             const PtMeshDesc& md = L.meshes[(size_t)si.mesh];
             for (uint32_t g = 0; g < md.numGeometries; g++) {
                 const PtGeometryDesc& gd = L.geoms[md.firstGeometry + g];
                 for (uint32_t v = gd.vertexOffset; v < gd.vertexOffset + gd.numVertices; v++) {
                     const float* wgt = &L.weights[4 * (size_t)v]; const uint16_t* jnt = &L.joints[4 * (size_t)v];
-                    if (!(wgt[0] + wgt[1] + wgt[2] + wgt[3] > 0.f)) continue;                 // an unskinned primitive of the mesh keeps its bind pose
-                    const double p[3] = {out[3 * (size_t)v], out[3 * (size_t)v + 1], out[3 * (size_t)v + 2]}; double q[3] = {0, 0, 0};      // (the morphed position)
-                    for (int k = 0; k < 4; k++) { if (wgt[k] == 0.f || jnt[k] >= jm.size()) continue; const double* m = jm[jnt[k]].m;
-                        for (int rr = 0; rr < 3; rr++) q[rr] += (double)wgt[k] * (m[rr] * p[0] + m[4 + rr] * p[1] + m[8 + rr] * p[2] + m[12 + rr]); }
-                    for (int rr = 0; rr < 3; rr++) out[3 * (size_t)v + rr] = (float)q[rr];
-                    if ((outN && (gd.flags & PT_GEOM_HAS_NORMAL)) || (outT && (gd.flags & PT_GEOM_HAS_TANGENT))) {
-                        double nrm[3] = {0, 0, 0}, tan[3] = {0, 0, 0}; const float* n0 = &nF[3 * (size_t)v]; const float* t0 = &tF[4 * (size_t)v];      // (morphed first)
-                        for (int k = 0; k < 4; k++) { if (wgt[k] == 0.f || jnt[k] >= jm.size()) continue; const double* m = jm[jnt[k]].m;      // column major: m[4 c + r]
-                            // cofactors of the upper 3 x 3 = det * inverse-transpose
-                            const double c00 = m[5] * m[10] - m[9] * m[6], c01 = m[9] * m[2] - m[1] * m[10], c02 = m[1] * m[6] - m[5] * m[2];      // (rows of the cofactor matrix, indexed [row][col] of M)
-                            const double det = m[0] * c00 + m[4] * c01 + m[8] * c02;
-                            if (det != 0.0) {
-                                const double C[3][3] = {{c00, c01, c02},
-                                                        {m[8] * m[6] - m[4] * m[10], m[0] * m[10] - m[8] * m[2], m[4] * m[2] - m[0] * m[6]},
-                                                        {m[4] * m[9] - m[8] * m[5], m[8] * m[1] - m[0] * m[9], m[0] * m[5] - m[4] * m[1]}};      // C[r][c]: cofactor of M(r, c), M(r, c) = m[4 c + r]; inverse-transpose = C / det
-                                for (int rr = 0; rr < 3; rr++) nrm[rr] += (double)wgt[k] * (C[rr][0] * n0[0] + C[rr][1] * n0[1] + C[rr][2] * n0[2]) / det;
-                            }
-                            for (int rr = 0; rr < 3; rr++) tan[rr] += (double)wgt[k] * (m[rr] * t0[0] + m[4 + rr] * t0[1] + m[8 + rr] * t0[2]);
-                        }
-                        if (outN && (gd.flags & PT_GEOM_HAS_NORMAL)) { const double l = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
-                            if (l > 0) { float nn[3] = {(float)(nrm[0] / l), (float)(nrm[1] / l), (float)(nrm[2] / l)}; outN[v] = pack_snorm8(nn, 3); } }
-                        if (outT && (gd.flags & PT_GEOM_HAS_TANGENT)) { const double l = sqrt(tan[0] * tan[0] + tan[1] * tan[1] + tan[2] * tan[2]);
-                            if (l > 0) { float tt[4] = {(float)(tan[0] / l), (float)(tan[1] / l), (float)(tan[2] / l), t0[3]}; outT[v] = pack_snorm8(tt, 4); } }
-                    }
+                    if (!ptskin::skinned(wgt)) continue;                                      // an unskinned primitive of the mesh keeps its bind pose
+                    ptskin::skin_position(&out[3 * (size_t)v], wgt, jnt, jm[0].m, (uint32_t)jm.size(), &out[3 * (size_t)v]);      // (reads the morphed position)
+                    const bool wantN = outN && (gd.flags & PT_GEOM_HAS_NORMAL), wantT = outT && (gd.flags & PT_GEOM_HAS_TANGENT);
+                    if (wantN || wantT) ptskin::skin_frame(&nF[3 * (size_t)v], &tF[4 * (size_t)v], wgt, jnt, jm[0].m, (uint32_t)jm.size(), wantN ? &outN[v] : nullptr, wantT ? &outT[v] : nullptr);      // (morphed first)
                 }
             }
         }
@@ -865,6 +848,75 @@ extern "C" int32_t pt_gltf_animation_positions(pt_gltf_animation* a, uint32_t an
 extern "C" int32_t pt_gltf_animation_normals(pt_gltf_animation* a, uint32_t animation, float t, uint32_t* normals, uint32_t* tangents, uint32_t capacityVertices) {
     if (capacityVertices && !normals && !tangents) return -PT_ERROR_INVALID_ARGUMENT;
     return gltf_animation_pose(a, animation, t, nullptr, normals, tangents, capacityVertices);
+}
+// The pose above split into its static and its per-frame part (include/mi355pt.h: PtSkinningDesc). The node walk decides which node poses a mesh: with several, the last one
+// met — for the morph weights as in the pose above; for the skin the pose above applies the nodes' skins one after another, the description holds the last one only.
+static int32_t gltf_skinning_build(pt_gltf_animation* a) {
+    if (a->skinningBuilt) return PT_OK;
+    Loader& L = a->L; const JValue* skins = L.root.get("skins");
+    L.recordWorlds = true; L.skinned.clear(); L.nodeWorld.clear(); L.meshNodes.clear();
+    std::vector<PtInstanceDesc> scratch(1); int32_t r = pt_gltf_animation_instances(a, 0xFFFFFFFFu, 0.f, scratch.data(), 0);      // (no animation: the walk alone)
+    L.recordWorlds = false; if (r < 0) return -r;
+    const size_t ng = L.geoms.size(); std::vector<int> morphOf(ng, -1), skinOf(ng, -1);      // per geometry: index into meshNodes / skinned of the node that poses it
+    if (!L.morphDeltas.empty()) for (size_t i = 0; i < L.meshNodes.size(); i++) { const Loader::MeshNode& mn = L.meshNodes[i]; if ((size_t)mn.mesh >= L.meshes.size()) continue;
+        const PtMeshDesc& md = L.meshes[(size_t)mn.mesh]; for (uint32_t g = 0; g < md.numGeometries; g++) if (L.geomMorph[md.firstGeometry + g].count) morphOf[md.firstGeometry + g] = (int)i; }
+    if (skins) for (size_t i = 0; i < L.skinned.size(); i++) { const Loader::SkinnedInstance& si = L.skinned[i]; if ((size_t)si.skin >= skins->size() || (size_t)si.mesh >= L.meshes.size()) continue;
+        const JValue* jl = skins->arr[(size_t)si.skin].get("joints"); if (!jl || !jl->size()) continue;
+        const PtMeshDesc& md = L.meshes[(size_t)si.mesh]; for (uint32_t g = 0; g < md.numGeometries; g++) skinOf[md.firstGeometry + g] = (int)i; }
+    a->ranges.clear(); a->rangeMorphNode.clear(); a->rangeMorphTargets.clear(); a->palettes.clear(); a->numMatrices = a->numMorphWeights = 0;
+    for (size_t g = 0; g < ng; g++) {
+        if (morphOf[g] < 0 && skinOf[g] < 0) continue;
+        const PtGeometryDesc& gd = L.geoms[g]; if (!gd.numVertices) continue;
+        PtSkinRange rg; memset(&rg, 0, sizeof(rg)); rg.firstVertex = gd.vertexOffset; rg.numVertices = gd.numVertices; rg.geometryFlags = gd.flags;
+        Loader::MeshNode mn{-1, -1}; uint32_t nT = 0;
+        if (morphOf[g] >= 0) {
+            const Loader::GeomMorph& gm = L.geomMorph[g]; if (gm.first > 0xFFFFFFFFull) return PT_ERROR_UNSUPPORTED;
+            mn = L.meshNodes[(size_t)morphOf[g]]; const PtMeshDesc& md = L.meshes[(size_t)mn.mesh];
+            for (uint32_t k = 0; k < md.numGeometries; k++) if (L.geomMorph[md.firstGeometry + k].count > nT) nT = L.geomMorph[md.firstGeometry + k].count;      // (a weights channel has one scalar per target of the mesh)
+            rg.firstMorphDelta = (uint32_t)gm.first; rg.numTargets = gm.count; rg.firstWeight = a->numMorphWeights; a->numMorphWeights += gm.count;
+        }
+        if (skinOf[g] >= 0) {
+            const Loader::SkinnedInstance& si = L.skinned[(size_t)skinOf[g]]; const pt_gltf_animation::Palette* found = nullptr;
+            for (auto& p : a->palettes) if (p.node == si.node && p.skin == si.skin) found = &p;
+            if (!found) { a->palettes.push_back({si.node, si.skin, a->numMatrices, (uint32_t)skins->arr[(size_t)si.skin].get("joints")->size()}); found = &a->palettes.back(); a->numMatrices += found->numMatrices; }
+            rg.firstMatrix = found->firstMatrix; rg.numMatrices = found->numMatrices;
+        }
+        a->ranges.push_back(rg); a->rangeMorphNode.push_back(mn); a->rangeMorphTargets.push_back(nT);
+    }
+    a->skinningBuilt = true;
+    return PT_OK;
+}
+extern "C" int32_t pt_gltf_animation_skinning(pt_gltf_animation* a, PtSkinningDesc* out) {
+    if (!a || !out) return PT_ERROR_INVALID_ARGUMENT;
+    try {
+        int32_t r = gltf_skinning_build(a); if (r != PT_OK) return r;
+        Loader& L = a->L; memset(out, 0, sizeof(*out));
+        out->numVertices = (uint32_t)(L.positions.size() / 3); out->numRanges = (uint32_t)a->ranges.size(); out->numMatrices = a->numMatrices; out->numMorphWeights = a->numMorphWeights;
+        out->joints = L.joints.data(); out->weights = L.weights.data(); out->normals = L.normalsF.data(); out->tangents = L.tangentsF.data();
+        out->morphPositionDeltas = L.morphDeltas.data(); out->morphNormalDeltas = L.morphNormalDeltas.data(); out->morphTangentDeltas = L.morphTangentDeltas.data(); out->numMorphDeltaFloats = L.morphDeltas.size();
+        out->ranges = a->ranges.data();
+        return PT_OK;
+    } catch (...) { a->L.recordWorlds = false; a->L.nodeOverride = nullptr; return PT_ERROR_IO; }
+}
+extern "C" int32_t pt_gltf_animation_palette(pt_gltf_animation* a, uint32_t animation, float t, double* matrices, uint32_t capacityMatrices, double* morphWeights, uint32_t capacityWeights) {
+    if (!a || (capacityMatrices && !matrices) || (capacityWeights && !morphWeights)) return -PT_ERROR_INVALID_ARGUMENT;
+    try {
+        int32_t r = gltf_skinning_build(a); if (r != PT_OK) return -r;
+        if (!capacityMatrices && !capacityWeights) return (int32_t)a->numMatrices;      // (query)
+        if (capacityMatrices < a->numMatrices || capacityWeights < a->numMorphWeights) return -PT_ERROR_INVALID_ARGUMENT;
+        Loader& L = a->L; const JValue* skins = L.root.get("skins");
+        L.recordWorlds = true; L.skinned.clear(); L.nodeWorld.clear(); L.meshNodes.clear();
+        std::vector<PtInstanceDesc> scratch(1); r = pt_gltf_animation_instances(a, animation, t, scratch.data(), 0);      // evaluates the channels and walks the nodes
+        L.recordWorlds = false; if (r < 0) return r;
+        for (auto& p : a->palettes) {
+            std::vector<M4> jm; if (!gltf_joint_palette(L, skins->arr[(size_t)p.skin], p.node, jm) || jm.size() != p.numMatrices) return -PT_ERROR_UNSUPPORTED;
+            memcpy(matrices + 16 * (size_t)p.firstMatrix, jm[0].m, sizeof(M4) * jm.size());
+        }
+        for (size_t i = 0; i < a->ranges.size(); i++) { const PtSkinRange& rg = a->ranges[i]; if (!rg.numTargets) continue;
+            const std::vector<double> w = gltf_morph_weights(a, animation, t, a->rangeMorphNode[i], a->rangeMorphTargets[i]);
+            memcpy(morphWeights + rg.firstWeight, w.data(), sizeof(double) * rg.numTargets); }
+        return 0;
+    } catch (...) { a->L.recordWorlds = false; a->L.nodeOverride = nullptr; return -PT_ERROR_IO; }
 }
 extern "C" int32_t pt_gltf_animation_instances(pt_gltf_animation* a, uint32_t animation, float t, PtInstanceDesc* out, uint32_t capacity) {
     if (!a || (capacity && !out)) return -PT_ERROR_INVALID_ARGUMENT;
