@@ -243,7 +243,7 @@ int finalize_geometry(pt_context* c) {
     if (c->motionHistory) { c->prevAllStale = true; c->prevStaleRanges.clear(); int r = motion_history_sync(c); if (r != PT_OK) return r; }
     if (c->bvhAllocated && c->bvh.capacity < c->numTris) { bvh_free(c->bvh); c->bvhAllocated = false; }
     if (!c->bvhAllocated) { PT_CHECK_HIP(c, bvh_alloc(c->bvh, c->numTris)); c->bvhAllocated = true; }
-    c->bvh.builder = c->bvhBuilder;
+    c->bvh.builder = c->bvhBuilder; c->bvh.occlusionSlotOrder = c->occlusionSlotOrder ? 1u : 0u;
     // BVH_BUILDER_PLOC_OPT: parallel re-insertion passes (MI355X, C3: 8 passes = 1463 Mrays/s in 63 ms, 12 = 1477 in 81 ms, 16 = 1476 in 98 ms; host SAH +
     // re-insertion 1479 in 1824 ms — profiles/r03k_device_reinsertion_sweep.txt)
     { const char* e = getenv("MI355PT_REINSERT_PASSES"); c->bvh.riPasses = e ? (uint)atoi(e) : 12u; }
@@ -617,6 +617,7 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
     { const char* e = getenv("MI355PT_PACKET_STEP_CAP"); if (e) c->packetStepCap = (uint)strtoul(e, nullptr, 10); }
     { const char* e = getenv("MI355PT_PACKET_STACK"); if (e) c->packetStack = (uint)strtoul(e, nullptr, 10); }
     { const char* e = getenv("MI355PT_FUSED_TRAVERSAL"); if (e) c->fusedTraversal = (uint)strtoul(e, nullptr, 10); }
+    { const char* e = getenv("MI355PT_OCCLUSION_SLOT_ORDER"); if (e) c->occlusionSlotOrder = atoi(e) != 0; }      // developer A/B / test switch (0: child slots in collapse order, as before)
     { const char* e = getenv("MI355PT_DROP_INERT_TERMINAL"); if (e) c->dropInertTerminal = atoi(e) != 0; }      // developer A/B / test switch (0: every terminal hit is shaded, as before)
     // test switch: iterations after which the tail kernel hands a ray back (0: T8_TAIL_DEFER); a small value sends most rays through the hand-back path
     { const char* e = getenv("MI355PT_TAIL_DEFER"); if (e) c->tailDefer = (uint)strtoul(e, nullptr, 10); }

@@ -19,7 +19,9 @@
 //                   for scenes above PT_RANGE_TABLE_MAX_TRIS) took 20.9 ms of a 25 ms refit; min/max are exact, so the tree is bit-identical
 //   k_emit          collapse sub-trees of <= 4 triangles into leaves and write BVH2 nodes (both child boxes per node)
 //   k_alpha_records per leaf-order triangle: texture coordinates + alpha texture + cutoff for the traversal's alpha test
-//   k_collapse8     level by level: greedily open the largest-area inner child until 8 children -> quantised 128 B BVH8 nodes
+//   k_collapse8     level by level: greedily open the largest-area inner child until 8 children -> quantised 128 B BVH8 nodes; the children take the first n slots by
+//                   descending box area per triangle below them (pt_build_wide.h wide_occlusion_slots: the order an any-hit query walks them in, and the one that
+//                   breaks a closest-hit query's ties in entry distance). A refit keeps the slots of the build: its bytes are a fresh collapse's up to that order
 // Refit (animated instances / deformed vertices, same topology), round 4: k_refit_world (leaf-order triangles straight from a flat source record: instance, three global
 //   vertex indices — one hop instead of five; scene bounds reduced per 1024-thread block before the six atomics) and k_refit8_level, bottom-up over the levels of the WIDE
 //   tree: a wide node's children keep their slots, their boxes are the padded unions of what lies below — triangles of a leaf child, the stored un-padded box of an inner
@@ -68,6 +70,7 @@ struct BvhBuildBuffers {
     uint wideFlagsValid;        // BVH_BUILDER_PLOC_OPT: absorb[] holds the programme's flags (0: the collapse opens the largest child)
     uint wideLevels;            // depth of the binary tree above the wide tree's leaves (levels of the last device-side wide-node programme)
     uint optimiserPasses;       // re-insertion passes the last build ran (host: pt_build_sah.cpp; device: BVH_BUILDER_PLOC_OPT)
+    uint occlusionSlotOrder;    // 1: the collapse orders a wide node's child slots for occlusion rays (pt_build_wide.h wide_occlusion_slots); 0: collapse order. A refit keeps the slots it finds
     uint capacity;
 };
 

@@ -420,7 +420,8 @@ __device__ __forceinline__ void bvh8_pack(Bvh8Node& out, const float3* cmn, cons
     for (uint k = 0; k < n; k++) bvh8_child_codes(cmn[k], cmx[k], mn, sx, sy, sz, out.c[slotOf[k]].q0, out.c[slotOf[k]].q1);
 }
 __global__ void __launch_bounds__(128) k_collapse8(const BvhNode* __restrict__ nodes2, const uint* __restrict__ levelIn, uint nIn, uint* __restrict__ levelOut,
-                                                   uint* __restrict__ counter, Bvh8Node* __restrict__ nodes8, uint costDriven) {
+                                                   uint* __restrict__ counter, Bvh8Node* __restrict__ nodes8, uint costDriven, const uint* __restrict__ rangeFirst,
+                                                   const uint* __restrict__ rangeLast, uint occlusionOrder) {
     uint i = blockIdx.x * 128u + threadIdx.x;
     if (i >= nIn) return;
     uint wide = levelIn[2 * i], r = levelIn[2 * i + 1];
@@ -446,6 +447,12 @@ __global__ void __launch_bounds__(128) k_collapse8(const BvhNode* __restrict__ n
     if (nInner) { wbase = atomicAdd(&counter[0], nInner); obase = atomicAdd(&counter[1], nInner); }
     uint slotOf[8]; for (uint k = 0; k < n; k++) slotOf[k] = k;      // children in collapse order (slots by octant — Ylitie et al. 2017 — were measured in round 4 and lost: +25 % on k_extend, profiles/r04u_octant_order_ab.txt)
     Bvh8Node out; bvh8_pack(out, cmn, cmx, n, slotOf);
+    if (occlusionOrder) {                                   // the first n slots again, likeliest blocker per unit of work first (pt_build_wide.h wide_occlusion_slots): what an any-hit query walks in
+        uint q0[8], q1[8], nt[8];
+        for (uint k = 0; k < n; k++) { q0[k] = out.c[k].q0; q1[k] = out.c[k].q1; nt[k] = (cref[k] & BVH_LEAF_BIT) ? (cref[k] & 7u) + 1u : rangeLast[cref[k]] - rangeFirst[cref[k]] + 1u; }
+        wide_occlusion_slots(n, q0, q1, out.exps, nt, slotOf);
+        for (uint k = 0; k < n; k++) { out.c[slotOf[k]].q0 = q0[k]; out.c[slotOf[k]].q1 = q1[k]; }
+    }
     uint inner = 0;
     for (uint k = 0; k < n; k++) {
         if (cref[k] & BVH_LEAF_BIT) out.c[slotOf[k]].ref = cref[k];
@@ -697,7 +704,7 @@ static hipError_t bvh_bounds_and_emit(BvhBuildBuffers& b, const DeviceScene& sc,
     uint nIn = 1, levels = 0; uint* in = b.levelA; uint* out = b.levelB;
     b.wideLevelStart[0] = 0u; b.wideLevelStart[1] = 1u;
     while (nIn) {
-        hipLaunchKernelGGL(k_collapse8, dim3((nIn + 127u) / 128u), dim3(128), 0, st, b.nodes, in, nIn, out, b.wideCounter, b.nodes8, costDriven ? 1u : 0u);
+        hipLaunchKernelGGL(k_collapse8, dim3((nIn + 127u) / 128u), dim3(128), 0, st, b.nodes, in, nIn, out, b.wideCounter, b.nodes8, costDriven ? 1u : 0u, b.rangeFirst, b.rangeLast, b.occlusionSlotOrder);
         uint host[2];
         PT_HIP_TRY(hipMemcpyAsync(host, b.wideCounter, 8, hipMemcpyDeviceToHost, st));
         PT_HIP_TRY(hipStreamSynchronize(st));

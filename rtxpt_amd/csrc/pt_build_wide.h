@@ -69,4 +69,24 @@ PT_WIDE_HD inline void wide_mark_node(uint id, uint state, uint childL, uint chi
     if (!(childR & WIDE_LEAF_BIT)) stateOut[childR] = wide_state(i - a, false);
 }
 
+// ---- the child slots of a wide node: a static priority for occlusion rays. An any-hit query walks a node's hit children in slot order (pt_traverse8.h T8_ANYHIT_UNORDERED) and
+// stops at the first accepted triangle, so the child most likely to end the walk for the least work goes first: by descending (surface area of the child's box) / (triangles
+// below the child), ties in collapse order. A closest-hit query ranks by entry distance and takes the slot only to break ties — but all the boxes that
+// hold the ray's origin tie at tmin, so the same order also finds a bounce ray its first hit sooner (profiles/r19a_occlusion_order_ab.txt). The area is taken from the child's quantised box
+// as the node stores it (q0 / q1 of bvh8_pack, the three scale exponents of `exps` taken relative to the largest: extents of at most 255, no overflow whatever the scene's size),
+// so the order can be restated from a read-back of the nodes alone: every product below is exact in float, the two sums and the division round once each.
+//   q0[k], q1[k]: child k's codes (lo x | lo y << 8 | lo z << 16 | hi x << 24, hi y | hi z << 8); tris[k] >= 1: triangles below child k; slotOf[k]: the slot child k goes to,
+//   a permutation of 0 .. n - 1
+PT_WIDE_HD inline float wide_pow2_rel(uint e, uint emax) { const uint d = emax - e; const uint b = (d < 40u) ? ((127u - d) << 23) : 0u;      /* an axis 2^40 times finer than the coarsest counts as flat: no product leaves the normal range */ float f; __builtin_memcpy(&f, &b, 4); return f; }
+PT_WIDE_HD inline void wide_occlusion_slots(uint n, const uint* q0, const uint* q1, uint exps, const uint* tris, uint* slotOf) {
+    const uint ex = exps & 0xFFu, ey = (exps >> 8) & 0xFFu, ez = (exps >> 16) & 0xFFu, emax = ex > ey ? (ex > ez ? ex : ez) : (ey > ez ? ey : ez);
+    const float sx = wide_pow2_rel(ex, emax), sy = wide_pow2_rel(ey, emax), sz = wide_pow2_rel(ez, emax);
+    float key[8];
+    for (uint k = 0; k < n; k++) {
+        const float dx = (float)((q0[k] >> 24) - (q0[k] & 0xFFu)) * sx, dy = (float)((q1[k] & 0xFFu) - ((q0[k] >> 8) & 0xFFu)) * sy, dz = (float)(((q1[k] >> 8) & 0xFFu) - ((q0[k] >> 16) & 0xFFu)) * sz;
+        key[k] = ((dx * dy + dy * dz) + dz * dx) / (float)tris[k];
+    }
+    for (uint k = 0; k < n; k++) { uint r = 0; for (uint j = 0; j < n; j++) r += (key[j] > key[k] || (key[j] == key[k] && j < k)) ? 1u : 0u; slotOf[k] = r; }
+}
+
 } // namespace ptk

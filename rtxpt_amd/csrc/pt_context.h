@@ -119,7 +119,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     int device = 0; hipStream_t stream = nullptr; uint shardRank = 0, shardCount = 1;
     // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
     hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
-    uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
+    uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool occlusionSlotOrder = true, compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
     // vertex 0 as packets (ptk::FirstPackets): the switch, the step cap and stack bound of a packet (0: T8_PACKET_STEP_CAP / T8_PACKET_STACK), the leftover list (one word per path)
     bool firstVertexPackets = PT_FIRST_VERTEX_PACKETS != 0; uint packetStepCap = 0, packetStack = 0; DevBuf<uint> dFirstLeftover;
     // pt_render's classified passes drop the terminal hits that can add nothing (k_classify, pt_wavefront.hip); droppedTerminal: how many the last pt_render call dropped

@@ -2,6 +2,8 @@
 // Builds the scene's BVH with several builders (Morton LBVH as pt_build.hip does, PLOC, binned top-down SAH), collapses each to BVH8 with the
 // product's greedy rule or a cost-driven rule, and counts node visits / leaf visits / triangle tests per ray of a nearest-first traversal with the
 // product's pruning rules over a set of path-like rays (camera rays + cosine-distributed bounces). Input: tools/bvh_lab/dump_tris.py.
+// LAB_ANYHIT=1: instead, visibility rays from the paths' bounce vertices through an any-hit walk in static child-slot order, one table row per ordering rule
+// (profiles/r19a_occlusion_order_lab.txt).
 //   g++ -O3 -march=native -fopenmp -std=c++17 tools/bvh_lab/bvh_lab.cpp rtxpt_amd/csrc/pt_build_sah.cpp -lpthread -o /tmp/bvh_lab && /tmp/bvh_lab /tmp/bvh_lab_tris.bin
 #include <algorithm>
 #include <array>
@@ -384,6 +386,12 @@ static Bvh8 collapse(const Bvh2& b, int maxLeaf, int mode) {
                     if (kind[id][i] == 0) { roots.push_back(id); return; }
                     int a = dk[id][i]; place(b.nodes[id].l, a); place(b.nodes[id].r, i - a);
                 };
+                if (mode == 1 && getenv("LAB_ANYHIT")) {     // the same roots in the order k_collapse8 leaves them in: the lowest child that is to be opened is replaced by its left child, the right one is appended
+                    struct S { int id, i; }; S sl[8]; int m = 0; { int a = dk[j.id][8]; sl[m++] = {b.nodes[j.id].l, a}; sl[m++] = {b.nodes[j.id].r, 8 - a}; }
+                    for (;;) { int k = 0; for (; k < m; k++) { while (kind[sl[k].id][sl[k].i] == 2) sl[k].i--; if (kind[sl[k].id][sl[k].i] == 1) break; }
+                        if (k == m) break; const S o = sl[k]; const int a = dk[o.id][o.i]; sl[k] = {b.nodes[o.id].l, a}; sl[m++] = {b.nodes[o.id].r, o.i - a}; }
+                    for (int k = 0; k < m; k++) roots.push_back(sl[k].id);
+                } else
                 { int a = dk[j.id][8]; place(b.nodes[j.id].l, a); place(b.nodes[j.id].r, 8 - a); }
                 Wide wn; wn.n = 0;
                 for (int id : roots) {
@@ -513,6 +521,90 @@ static void packet_table(const Bvh8& w, int packets) {
     }
 }
 
+// LAB_ANYHIT: occlusion rays. The product's any-hit loop (T8_ANYHIT_UNORDERED) numbers a node's hit children by child slot: the lowest hit slot is entered next, the others go on
+// the stack with the lower slot on top — a depth-first walk in static slot order that ends at the first accepted triangle. What it costs an occluded ray depends on the slot
+// order alone, so the lab permutes the slots of a collapsed tree by a static rule and counts node and leaf visits of visibility rays, split by outcome.
+struct VisRay { V3 o, d; float tmax; };
+struct AnyCtr { uint64_t nodes[2] = {0, 0}, leaves[2] = {0, 0}, rays[2] = {0, 0}; };      // [0]: visible rays, [1]: occluded rays
+// nearest: rank the hit children by entry distance instead (dynamic: for reference only)
+static bool occluded8(const Bvh8& w, const VisRay& r, bool nearest, uint64_t& nNodes, uint64_t& nLeaves) {
+    V3 id{1.f / r.d.x, 1.f / r.d.y, 1.f / r.d.z};
+    int stack[512]; int sp = 0; stack[sp++] = 0;
+    while (sp) {
+        int cur = stack[--sp];
+        if (cur >= 0) {
+            const Wide& n = w.nodes[cur]; nNodes++;
+            struct E { int ref; float t; }; E hits[8]; int nh = 0;
+            for (int k = 0; k < n.n; k++) {
+                const Box& b = n.cb[k];
+                float tx1 = (b.mn.x - r.o.x) * id.x, tx2 = (b.mx.x - r.o.x) * id.x, ty1 = (b.mn.y - r.o.y) * id.y, ty2 = (b.mx.y - r.o.y) * id.y, tz1 = (b.mn.z - r.o.z) * id.z, tz2 = (b.mx.z - r.o.z) * id.z;
+                float tn = std::max(std::max(std::min(tx1, tx2), std::min(ty1, ty2)), std::max(std::min(tz1, tz2), 0.f));
+                float tf = std::min(std::min(std::max(tx1, tx2), std::max(ty1, ty2)), std::min(std::max(tz1, tz2), r.tmax));
+                if (tn <= tf) hits[nh++] = {n.ref[k], tn};
+            }
+            if (nearest) std::stable_sort(hits, hits + nh, [](const E& a, const E& b) { return a.t < b.t; });
+            for (int k = nh - 1; k >= 0; k--) stack[sp++] = hits[k].ref;
+        } else {
+            int code = ~cur, first = code >> 4, cnt = (code & 15) + 1; nLeaves++;
+            for (int k = 0; k < cnt; k++) { float tt; if (isect(tris[w.order[first + k]], r.o, r.d, r.tmax, tt)) return true; }
+        }
+    }
+    return false;
+}
+// static slot orders. key: children are sorted by ascending key, ties keep collapse order
+enum { ORD_COLLAPSE = 0, ORD_LEAVES_THEN_AREA, ORD_INNER_AREA_THEN_LEAVES, ORD_AREA_ALL, ORD_AREA_PER_TRI, ORD_LEAVES_AREA_THEN_INNER_AREA, ORD_INNER_AREA_IN_PLACE, ORD_FEWEST_TRIS, ORD_AREA_PER_SQRT_TRI, ORD_AREA_ASC, ORD_COUNT };
+static const char* const ORD_NAME[ORD_COUNT] = {"collapse order (today)", "leaves, then inner by area desc", "inner by area desc, then leaves", "all children by area desc", "all by area / triangles desc",
+                                                "leaves by area desc, inner by area desc", "inner by area desc, leaves keep slots", "fewest triangles first", "all by area / sqrt(triangles) desc", "all children by area asc"};
+static Bvh8 reorder_slots(const Bvh8& src, int rule) {
+    Bvh8 w = src; const int N = (int)w.nodes.size();
+    std::vector<int> ntri(N, 0);                             // triangles below a wide node (children have larger indices than their parent)
+    for (int i = N - 1; i >= 0; i--) { const Wide& n = w.nodes[i]; int c = 0; for (int k = 0; k < n.n; k++) c += n.ref[k] < 0 ? ((~n.ref[k]) & 15) + 1 : ntri[n.ref[k]]; ntri[i] = c; }
+    if (rule == ORD_COLLAPSE) return w;
+    for (int i = 0; i < N; i++) {
+        Wide& n = w.nodes[i]; const Wide o = n; int perm[8]; for (int k = 0; k < n.n; k++) perm[k] = k;
+        auto leaf = [&](int k) { return o.ref[k] < 0; }; auto area = [&](int k) { return o.cb[k].area(); };
+        auto cnt = [&](int k) { return (float)(leaf(k) ? ((~o.ref[k]) & 15) + 1 : ntri[o.ref[k]]); };
+        if (rule == ORD_INNER_AREA_IN_PLACE) {               // the inner children's slots are handed out again among the inner children, largest first
+            int slots[8], ids[8], m = 0; for (int k = 0; k < n.n; k++) if (!leaf(k)) { slots[m] = k; ids[m] = k; m++; }
+            std::stable_sort(ids, ids + m, [&](int a, int b) { return area(a) > area(b); });
+            for (int j = 0; j < m; j++) perm[slots[j]] = ids[j];
+        } else {
+            auto before = [&](int a, int b) {
+                switch (rule) {
+                case ORD_LEAVES_THEN_AREA: if (leaf(a) != leaf(b)) return leaf(a); return !leaf(a) && area(a) > area(b);
+                case ORD_INNER_AREA_THEN_LEAVES: if (leaf(a) != leaf(b)) return leaf(b); return !leaf(a) && area(a) > area(b);
+                case ORD_AREA_ALL: return area(a) > area(b);
+                case ORD_AREA_PER_TRI: return area(a) / cnt(a) > area(b) / cnt(b);
+                case ORD_FEWEST_TRIS: return cnt(a) < cnt(b);
+                case ORD_AREA_PER_SQRT_TRI: return area(a) / std::sqrt(cnt(a)) > area(b) / std::sqrt(cnt(b));
+                case ORD_AREA_ASC: return area(a) < area(b);
+                default: if (leaf(a) != leaf(b)) return leaf(a); return area(a) > area(b); }
+            };
+            std::stable_sort(perm, perm + n.n, before);
+        }
+        for (int k = 0; k < n.n; k++) { n.cb[k] = o.cb[perm[k]]; n.ref[k] = o.ref[perm[k]]; }
+    }
+    return w;
+}
+static void anyhit_table(const Bvh8& base, const std::vector<VisRay>& vr) {
+    printf("%-42s %9s | %-23s | %-23s | %-31s | %s\n", "child slot order", "occluded", "occluded: nodes leaves", "visible: nodes leaves", "all: nodes leaves nodes+leaves", "against collapse order");
+    double ref = 0;
+    for (int rule = 0; rule <= ORD_COUNT; rule++) {
+        const bool nearest = rule == ORD_COUNT; const Bvh8 w = reorder_slots(base, nearest ? ORD_COLLAPSE : rule); AnyCtr tot;
+        #pragma omp parallel
+        { AnyCtr c;
+          #pragma omp for schedule(dynamic, 1024)
+          for (size_t i = 0; i < vr.size(); i++) { uint64_t nn = 0, nl = 0; const int o = occluded8(w, vr[i], nearest, nn, nl) ? 1 : 0; c.nodes[o] += nn; c.leaves[o] += nl; c.rays[o]++; }
+          #pragma omp critical
+          for (int o = 0; o < 2; o++) { tot.nodes[o] += c.nodes[o]; tot.leaves[o] += c.leaves[o]; tot.rays[o] += c.rays[o]; } }
+        const double R = (double)(tot.rays[0] + tot.rays[1]), all = (double)(tot.nodes[0] + tot.nodes[1] + tot.leaves[0] + tot.leaves[1]) / R;
+        if (rule == 0) ref = all;
+        printf("%-42s %8.2f%% | %11.2f %11.2f | %11.2f %11.2f | %9.2f %9.2f %11.2f | %+6.2f %%\n", nearest ? "nearest first (dynamic, reference only)" : ORD_NAME[rule], 100.0 * tot.rays[1] / R,
+               (double)tot.nodes[1] / std::max<uint64_t>(tot.rays[1], 1), (double)tot.leaves[1] / std::max<uint64_t>(tot.rays[1], 1), (double)tot.nodes[0] / std::max<uint64_t>(tot.rays[0], 1),
+               (double)tot.leaves[0] / std::max<uint64_t>(tot.rays[0], 1), (double)(tot.nodes[0] + tot.nodes[1]) / R, (double)(tot.leaves[0] + tot.leaves[1]) / R, all, 100.0 * (all / ref - 1.0));
+        fflush(stdout);
+    }
+}
 
 int main(int argc, char** argv) {
     const char* path = argc > 1 ? argv[1] : "/tmp/bvh_lab_tris.bin";
@@ -526,7 +618,7 @@ int main(int argc, char** argv) {
 
     // rays: camera rays + cosine bounces over the baseline tree
     Bvh2 lb = build_lbvh(); Bvh8 base = collapse(lb, 4, 0);
-    std::vector<Ray> rays;
+    std::vector<Ray> rays; struct Vert { V3 p, n; }; std::vector<Vert> verts;      // verts: the bounce vertices (offset along the normal), where visibility rays start
     { V3 pos{4.0f, 1.7f, 20.0f}, dir = normalize(V3{1.0f, 0.12f, 0.05f}), up{0, 1, 0}; V3 U = normalize(cross(dir, up)), Vv = normalize(cross(U, dir)); float th = std::tan(0.5f * 1.0471975512f), asp = 16.f / 9.f;
       uint32_t s = 777u; Ctr dummy;
       for (int p = 0; p < nPaths; p++) {
@@ -538,6 +630,7 @@ int main(int argc, char** argv) {
               if (bounce >= 2 && frand(s) > 0.75f) break;
               const Tri& tr = tris[h.prim]; V3 ng = normalize(cross(tr.e1, tr.e2)); if (dot(ng, r.d) > 0) ng = ng * -1.f;
               V3 hp = r.o + r.d * h.t + ng * 1e-4f;
+              verts.push_back({hp, ng});
               float u1 = frand(s), u2 = frand(s), rr = std::sqrt(u1), ph = 6.2831853f * u2; V3 t1 = normalize(std::fabs(ng.x) > 0.5f ? cross(ng, V3{0, 1, 0}) : cross(ng, V3{1, 0, 0})), t2 = cross(ng, t1);
               r = {hp, normalize(t1 * (rr * std::cos(ph)) + t2 * (rr * std::sin(ph)) + ng * std::sqrt(std::max(0.f, 1 - u1)))};
           }
@@ -557,6 +650,25 @@ int main(int argc, char** argv) {
                (double)N / rays.size(), (double)L / rays.size(), (double)T / rays.size(), (double)(N + L) / rays.size());
         fflush(stdout);
     };
+    // LAB_ANYHIT=1: the table of static child-slot orders for occlusion rays, over the tree the device builds (PLOC + 12 parallel re-insertion passes, cost-driven collapse, leaves
+    // of at most two triangles). Two visibility rays per bounce vertex: one into the sky hemisphere (unbounded), one towards a random point of a random triangle (ends just in front
+    // of it); a ray that would leave through the back of its surface is not traced, as in the product.
+    if (getenv("LAB_ANYHIT")) {
+        std::vector<VisRay> vr; uint32_t s = 31337u;
+        for (const Vert& v : verts) {
+            { float u1 = frand(s), u2 = frand(s), sy = u1, sr = std::sqrt(std::max(0.f, 1 - sy * sy)), ph = 6.2831853f * u2; V3 d{sr * std::cos(ph), sy, sr * std::sin(ph)};
+              if (dot(d, v.n) > 0.f && sy > 1e-3f) vr.push_back({v.p, d, 1e30f}); }
+            { const Tri& tr = tris[std::min((uint32_t)(frand(s) * n), n - 1)]; float a = frand(s), b = frand(s); if (a + b > 1.f) { a = 1 - a; b = 1 - b; }
+              V3 q = tr.v0 + tr.e1 * a + tr.e2 * b, d = q - v.p; float len = std::sqrt(dot(d, d));
+              if (len > 1e-3f && dot(d, v.n) > 0.f) vr.push_back({v.p, d * (1.f / len), len * 0.999f}); }
+        }
+        fprintf(stderr, "%zu visibility rays from %zu bounce vertices\n", vr.size(), verts.size());
+        Bvh2 t = build_ploc(32); optimize_parallel_reinsert(t, 12, 1.0f);
+        Bvh8 w8 = collapse(t, 2, 1);
+        printf("%u triangles, %zu wide nodes, %zu visibility rays (sky hemisphere + random triangle at finite tmax) from %zu bounce vertices of %d paths; visits per ray\n", n, w8.nodes.size(), vr.size(), verts.size(), nPaths);
+        anyhit_table(w8, vr);
+        return 0;
+    }
     if (!getenv("LAB_SKIP_BASE")) {
     eval("lbvh greedy leaf4 (product)", lb, 4, 0);
     eval("lbvh cost-driven leaf4", lb, 4, 1);
