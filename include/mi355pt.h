@@ -129,6 +129,10 @@ typedef struct PtDeviceDesc {
                                                refits keep the topology they find. The image does not depend on the tree. */
 #define PT_DEVICE_HOST_SAH_BUILDER 4u       /* the fast-trace tree of round 2 instead: binned-SAH topology + insertion-based optimisation on the host's cores
                                                (1.8 s at 2.8 M triangles, the same trace speed within 0.2 %); bounds, collapse and refit on the device as always */
+#define PT_DEVICE_TEXTURES_ON_DEVICE 8u     /* pt_set_materials (and what ends in it: pt_scene_import_apply, pt_load_scene_gltf) converts the textures, builds their mip
+                                               chains and their alpha planes on the device: the source pixels stream through a fixed pinned staging buffer, the host
+                                               converts no texel and keeps none. The same bits in the same tables as the host path. Environment
+                                               MI355PT_DEVICE_TEXTURES=0|1 overrides the flag. */
 
 /* pt_render fills every field; pt_build_stable_planes / pt_fill_stable_planes fill the same fields from the same counters (no tail launches, no per-launch times). */
 typedef struct PtFrameStats {
@@ -219,6 +223,13 @@ int32_t pt_set_geometry(pt_context* ctx, const PtGeometryBuffers* buffers, const
                         const PtMeshDesc* meshes, uint32_t numMeshes);
 int32_t pt_set_instances(pt_context* ctx, const PtInstanceDesc* instances, uint32_t numInstances);
 int32_t pt_set_materials(pt_context* ctx, const PTMaterialData* materials, uint32_t numMaterials, const PtTextureDesc* textures, uint32_t numTextures);
+/* Replace the pixels of texture `texture` of the last pt_set_materials: same width, height and format (anything else, or an index out of range, is
+ * PT_ERROR_INVALID_ARGUMENT). desc->pixels must stay valid until the call returns. With PT_DEVICE_TEXTURES_ON_DEVICE only that texture is staged, and its level 0, its
+ * chain and its alpha plane are rewritten in place: the lights are baked again (an emissive texture may have changed), the BVH is not built again. One exception: a
+ * PT_TEX_RGBA32F texture whose alpha plane holds bytes (every opacity was k / 255) and which receives other opacities gets a float plane — the alpha pool is laid out and
+ * filled again on the device and the geometry is finalised again, as after pt_set_materials. A float plane that receives byte-exact opacities stays a float plane.
+ * Without the flag the texture is converted on the host and everything is uploaded and finalised again. */
+int32_t pt_update_texture(pt_context* ctx, uint32_t texture, const PtTextureDesc* desc);
 /* EnvMapBaker source + EnvMapSceneParams (Rtxpt/Sample.cpp:1364-1388,1939): lat-long float RGB image, row 0 at +Y. width==0 disables.
  * params->ColorMultiplier is the reference's own: tint * intensity / c_envMapRadianceScale (Sample.cpp:1939-1940; the baked cube holds radiance x 1/4, so a
  * multiplier of 4 renders the image's radiance as supplied). params == NULL means identity orientation and exactly that: ColorMultiplier = 1 / c_envMapRadianceScale. */
@@ -875,6 +886,20 @@ int32_t pt_get_lights(pt_context* ctx, uint32_t* numLights, uint32_t* numProxies
  * EnvMapBaker.cpp:298-343, 593-633): 8 bytes per RGBA16F texel, mips one after the
  * other (dim, dim/2 .. 8), face-major (+X -X +Y -Y +Z -Z) within a mip. texels8B may be NULL to query the sizes. */
 int32_t pt_get_env_cube(pt_context* ctx, uint32_t* texelCount, uint32_t* dim, uint32_t* mipLevels, void* texels8B, uint32_t capacityTexels);
+/* Texture read-backs, from the device buffers the kernels sample (with or without PT_DEVICE_TEXTURES_ON_DEVICE). pt_get_texture_level: the RGBA32F texels of one mip level
+ * of a material texture, row-major; w / h receive the level's sides; rgba may be NULL to query them. pt_get_alpha_plane: the texture's alpha plane, the opacities of its
+ * level 0 — fmt 0: one byte per texel (every opacity is k / 255), fmt 1: one float per texel; `bytes` receives the plane's size; out may be NULL to query. */
+int32_t pt_get_texture_level(pt_context* ctx, uint32_t texture, uint32_t mip, uint32_t* w, uint32_t* h, float* rgba, uint32_t capacityTexels);
+int32_t pt_get_alpha_plane(pt_context* ctx, uint32_t texture, uint32_t* fmt, void* out, uint32_t capacityBytes, uint32_t* bytes);
+/* What the last texture ingest (pt_set_materials, or its upload on the host path) or pt_update_texture did. onDevice: 1 with PT_DEVICE_TEXTURES_ON_DEVICE; launches: the
+ * kernels it launched — a function of the level count and the staging chunks, never of the number of textures; stagingChunks: the pieces the source pixels were streamed
+ * in; sourceBytes: the pixels handed in; level0Texels / poolTexels: texels of the sources / of the pool, chains and the room for the environment image included;
+ * hostBytesHeld: what the context still holds on the host for textures after the call (host path: the converted texels of every level). uploadMs, level0Ms, mipMs,
+ * alphaMs: HIP-event times of the copies and of the three kernel groups (host path: uploadMs is the host time of pooling and uploading, the others 0); totalMs: a host
+ * clock around the whole ingest, ending in a stream synchronise. */
+typedef struct PtTextureIngestStats { uint32_t onDevice, launches, stagingChunks, _pad; uint64_t sourceBytes, level0Texels, poolTexels, hostBytesHeld;
+                                      double uploadMs, level0Ms, mipMs, alphaMs, totalMs; } PtTextureIngestStats;
+int32_t pt_get_texture_ingest_stats(pt_context* ctx, PtTextureIngestStats* out);
 int32_t pt_get_subinstances(pt_context* ctx, uint32_t* count, void* out32B);
 int32_t pt_get_scene_info(pt_context* ctx, uint32_t* numTriangles, uint32_t* numBvhNodes, uint32_t* numInstances, uint32_t* numMaterials);
 /* BVH build/refit timing of the last geometry update, milliseconds */

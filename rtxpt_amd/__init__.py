@@ -32,6 +32,7 @@ EXPORTS = [
     "pt_resize", "pt_render", "pt_reset_accumulation", "pt_map_radiance", "pt_unmap_radiance", "pt_shard_info", "pt_pack_shard",
     "pt_unpack_shard", "pt_device_radiance", "pt_trace_closest", "pt_trace_visibility", "pt_get_lights", "pt_get_env_cube", "pt_get_subinstances",
     "pt_get_scene_info", "pt_get_build_stats", "pt_get_bvh_info", "pt_set_counters",
+    "pt_update_texture", "pt_get_texture_level", "pt_get_alpha_plane", "pt_get_texture_ingest_stats",
     "pt_default_tonemap", "pt_tonemap", "pt_image_read_float", "pt_image_free", "pt_image_read_dds", "pt_image_read_dds_memory", "pt_image_read_jpeg", "pt_scene_import_texture", "pt_write_png", "pt_write_bmp", "pt_set_fused_traversal", "pt_set_serial_kernels", "pt_set_tail_paths", "pt_animate_ranges", "pt_set_motion_history", "pt_set_previous_pose", "pt_realtime_frame", "pt_exchange_planes_host", "pt_neeat_update_begin", "pt_neeat_update_end", "pt_pack_stable_plane_guides", "pt_unpack_stable_plane_guides", "pt_stable_planes_shard_bytes", "pt_pack_stable_planes", "pt_unpack_stable_planes", "pt_gather_stable_planes", "pt_material_from_json", "pt_convert_light",
     "pt_tonemap_color_transform", "pt_scene_json_import", "pt_scene_import_free", "pt_scene_import_cameras", "pt_scene_import_lights",
     "pt_scene_import_directional_lights", "pt_scene_import_instances", "pt_scene_import_geometries", "pt_scene_import_materials", "pt_scene_import_vertices", "pt_set_scene_directional_lights", "pt_scene_import_apply", "pt_scene_import_settings", "pt_average_luminance",
@@ -122,6 +123,12 @@ def procedural_sky_update(state, scene_time, preset="==PROCEDURAL_SKY==", params
 
 class PtDeviceDesc(ctypes.Structure):
     _fields_ = [("deviceOrdinal", ctypes.c_int32), ("shardRank", ctypes.c_uint32), ("shardCount", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class PtTextureIngestStats(ctypes.Structure):      # pt_get_texture_ingest_stats
+    _fields_ = [("onDevice", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("stagingChunks", ctypes.c_uint32), ("_pad", ctypes.c_uint32),
+                ("sourceBytes", ctypes.c_uint64), ("level0Texels", ctypes.c_uint64), ("poolTexels", ctypes.c_uint64), ("hostBytesHeld", ctypes.c_uint64),
+                ("uploadMs", ctypes.c_double), ("level0Ms", ctypes.c_double), ("mipMs", ctypes.c_double), ("alphaMs", ctypes.c_double), ("totalMs", ctypes.c_double)]
 
 
 class PtFrameStats(ctypes.Structure):
@@ -836,15 +843,16 @@ def bloom_kernel(radius, lib=None, capacity=BLOOM_MAX_TAPS + 1):
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
-    def __init__(self, device=0, shard_rank=0, shard_count=1, serial_kernels=False, prefer_fast_build=False, host_sah_builder=False, test_hooks=False):
+    def __init__(self, device=0, shard_rank=0, shard_count=1, serial_kernels=False, prefer_fast_build=False, host_sah_builder=False, test_hooks=False, device_textures=False):
         """serial_kernels: PT_DEVICE_SERIAL_KERNELS — pt_render runs one batch on one stream (clean per-kernel timings) instead of two pipelined half-frame batches.
         prefer_fast_build: PT_DEVICE_PREFER_FAST_BUILD — scene builds use the plain device-side PLOC builder instead of the default fast-trace tree (PLOC + parallel
         re-insertion + cost-driven wide nodes, on the device); host_sah_builder: PT_DEVICE_HOST_SAH_BUILDER — round 2's binned SAH + re-insertion on the host's cores.
+        device_textures: PT_DEVICE_TEXTURES_ON_DEVICE — textures are converted, mip-mapped and given their alpha planes on the device (the same bits as the host path's).
         test_hooks: run on libmi355pt_testhooks.so, the tests' build of the same sources that also exports pt_probe (include/mi355pt_testhooks.h)."""
         self.L = load_library(test_hooks)
         self.test_hooks = test_hooks
         self.h = ctypes.c_void_p()
-        desc = PtDeviceDesc(device, shard_rank, shard_count, (1 if serial_kernels else 0) | (2 if prefer_fast_build else 0) | (4 if host_sah_builder else 0))
+        desc = PtDeviceDesc(device, shard_rank, shard_count, (1 if serial_kernels else 0) | (2 if prefer_fast_build else 0) | (4 if host_sah_builder else 0) | (8 if device_textures else 0))
         r = self.L.pt_create(ctypes.byref(desc), ctypes.byref(self.h))
         if r != PT_OK:
             raise PtError(r, "pt_create failed (no HIP device? this library has no CPU path)")
@@ -909,6 +917,14 @@ class PathTracer:
         if sc.get("lights") is not None:
             base, ex = sc["lights"]
             self._chk(self.L.pt_set_lights(self.h, _p(base), _p(ex), len(base)), "pt_set_lights")
+
+    def set_environment(self, env):
+        """pt_set_environment alone: env = (lat-long float32 [h, w, 3], transform [12], colour multiplier [3]) as a scene's "env" entry, or None (off). The bake settings stay."""
+        if env is None: self._chk(self.L.pt_set_environment(self.h, None, 0, 0, None), "pt_set_environment"); return
+        rgb, tw, cm = env; rgb = np.ascontiguousarray(rgb, np.float32)
+        cm4 = (np.asarray(cm, np.float32) * np.float32(4.0)).astype(np.float32)
+        p = PtEnvMapSceneParams((ctypes.c_float * 12)(*np.asarray(tw, np.float32).tolist()), (ctypes.c_float * 3)(*cm4.tolist()), 1.0)
+        self._chk(self.L.pt_set_environment(self.h, _p(rgb), rgb.shape[1], rgb.shape[0], ctypes.byref(p)), "pt_set_environment")
 
     def set_procedural_sky(self, consts, textures=None):
         """consts: PtProceduralSkyConstants / 40 float32 values / None (off); textures: four float32 arrays (transmittance, scattering, irradiance, clouds) or None (keep)"""
@@ -1472,6 +1488,47 @@ class PathTracer:
         out = np.zeros((n.value, 2), np.uint32)
         if n.value: self._chk(self.L.pt_get_env_cube(self.h, None, None, None, _p(out), n.value), "pt_get_env_cube")
         return out, dim.value, lv.value
+
+    def update_texture(self, index, pixels):
+        """pt_update_texture: new pixels for texture `index` of the scene — uint8 [h, w, 4] for the two 8-bit formats, float32 [h, w, 4] for PT_TEX_RGBA32F; the size and the
+        format (sRGB or not: the texture's own) stay. With device_textures only that texture is converted again and the BVH stays."""
+        sc = self._keep[0] if self._keep and isinstance(self._keep[0], dict) else {}
+        if np.asarray(pixels).dtype == np.float32: fmt = PT_TEX_RGBA32F
+        elif index < len(sc.get("textures", ())): fmt = sc["textures"][index][2]          # the format set_scene handed in
+        else: fmt = PT_TEX_RGBA8_UNORM
+        self.update_texture_desc(index, pixels, fmt)
+
+    def update_texture_desc(self, index, pixels, fmt):
+        """pt_update_texture with an explicit PtTextureDesc format."""
+        px = np.ascontiguousarray(pixels); assert px.ndim == 3 and px.shape[2] == 4 and px.dtype in (np.uint8, np.float32)
+        d = PtTextureDesc(px.shape[1], px.shape[0], int(fmt), px.ctypes.data)
+        self.L.pt_update_texture.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; self.L.pt_update_texture.restype = ctypes.c_int32
+        self._chk(self.L.pt_update_texture(self.h, int(index), ctypes.byref(d)), "pt_update_texture")
+
+    def texture_level(self, index, mip):
+        """pt_get_texture_level: the texels of one mip level as the kernels sample them, float32 [h, w, 4]."""
+        f = self.L.pt_get_texture_level; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        w, h = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(f(self.h, int(index), int(mip), ctypes.byref(w), ctypes.byref(h), None, 0), "pt_get_texture_level")
+        out = np.zeros((h.value, w.value, 4), np.float32)
+        self._chk(f(self.h, int(index), int(mip), None, None, _p(out), w.value * h.value), "pt_get_texture_level")
+        return out
+
+    def alpha_plane(self, index):
+        """pt_get_alpha_plane: (fmt, plane) — fmt 0: uint8 [texels], every opacity of level 0 is k / 255; fmt 1: float32 [texels]."""
+        f = self.L.pt_get_alpha_plane; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        fmt, n = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(f(self.h, int(index), ctypes.byref(fmt), None, 0, ctypes.byref(n)), "pt_get_alpha_plane")
+        out = np.zeros(n.value, np.uint8)
+        self._chk(f(self.h, int(index), None, _p(out), n.value, None), "pt_get_alpha_plane")
+        return fmt.value, (out if fmt.value == 0 else out.view(np.float32))
+
+    def texture_ingest_stats(self):
+        """pt_get_texture_ingest_stats: what the last texture ingest or update did (PtTextureIngestStats as a dict)."""
+        s = PtTextureIngestStats()
+        self.L.pt_get_texture_ingest_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; self.L.pt_get_texture_ingest_stats.restype = ctypes.c_int32
+        self._chk(self.L.pt_get_texture_ingest_stats(self.h, ctypes.byref(s)), "pt_get_texture_ingest_stats")
+        return {n: getattr(s, n) for n, _ in PtTextureIngestStats._fields_ if not n.startswith("_")}
 
     def subinstances(self):
         n = ctypes.c_uint32()

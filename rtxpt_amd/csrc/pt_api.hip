@@ -26,22 +26,26 @@ static_assert(sizeof(::PolymorphicLightInfo) == sizeof(ptk::PolymorphicLightInfo
 
 namespace {
 
+// the host path's chain and level 0: pt_texture_ingest.h's texel arithmetic, one texel at a time
 void build_mips(HostTexture& t) {
-    uint lv = 1; { uint m = std::max(t.w, t.h); while (m > 1) { m >>= 1; lv++; } }
+    const uint lv = texi_level_count(t.w, t.h);
     t.mipLevels = lv; t.mips.resize(lv);
     for (uint l = 1; l < lv; l++) {
-        uint pw = std::max(1u, t.w >> (l - 1)), ph = std::max(1u, t.h >> (l - 1));
-        uint mw = std::max(1u, t.w >> l), mh = std::max(1u, t.h >> l);
+        const uint pw = texi_side(t.w, l - 1), ph = texi_side(t.h, l - 1), mw = texi_side(t.w, l), mh = texi_side(t.h, l);
         t.mips[l].resize((size_t)mw * mh);
-        const std::vector<ptk::float4>& p = t.mips[l - 1];
-        for (uint y = 0; y < mh; y++) for (uint x = 0; x < mw; x++) {
-            uint x0 = std::min(2 * x, pw - 1), x1 = std::min(2 * x + 1, pw - 1), y0 = std::min(2 * y, ph - 1), y1 = std::min(2 * y + 1, ph - 1);
-            ptk::float4 s = (p[(size_t)y0 * pw + x0] + p[(size_t)y0 * pw + x1]) + (p[(size_t)y1 * pw + x0] + p[(size_t)y1 * pw + x1]);
-            t.mips[l][(size_t)y * mw + x] = s * 0.25f;
-        }
+        const ptk::float4* p = t.mips[l - 1].data();
+        for (uint y = 0; y < mh; y++) for (uint x = 0; x < mw; x++) t.mips[l][(size_t)y * mw + x] = texi_mip_texel(p, pw, ph, x, y);
     }
 }
-float srgb_to_linear(float c) { return (c <= 0.04045f) ? c / 12.92f : dm_pow((c + 0.055f) / 1.055f, 2.4f); }
+void host_convert_texture(const PtTextureDesc& d, HostTexture& t) {
+    t.w = d.width; t.h = d.height; t.mips.clear(); t.mips.resize(1); t.mips[0].resize((size_t)d.width * d.height);
+    for (size_t k = 0; k < (size_t)d.width * d.height; k++) {
+        if (d.format == PT_TEX_RGBA32F) { const float* p = (const float*)d.pixels + 4 * k; t.mips[0][k] = ptk::make_float4(p[0], p[1], p[2], p[3]); }
+        else { const uint8_t* p = (const uint8_t*)d.pixels + 4 * k; t.mips[0][k] = texi_level0_rgba8((uint)p[0] | ((uint)p[1] << 8) | ((uint)p[2] << 16) | ((uint)p[3] << 24), d.format); }
+    }
+    build_mips(t);
+}
+size_t host_texture_bytes(const HostTexture& t) { size_t n = 0; for (auto& m : t.mips) n += m.size() * sizeof(ptk::float4); return n; }
 
 uint morton2(uint x, uint y) {
     auto part = [](uint v) { v &= 0xFFFF; v = (v | (v << 8)) & 0x00FF00FF; v = (v | (v << 4)) & 0x0F0F0F0F; v = (v | (v << 2)) & 0x33333333; v = (v | (v << 1)) & 0x55555555; return v; };
@@ -107,37 +111,51 @@ struct RcclApi {
 RcclApi g_rccl;
 #define PT_CHECK_NCCL(c, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); } while (0)
 
+// the host path: the texels the setters converted (HostTexture::mips) pooled and uploaded, with the tables pt_texture_ingest.h lays out. With PT_DEVICE_TEXTURES_ON_DEVICE the
+// material textures are on the device already (pt_texture_ingest.hip) and only the environment image is placed.
 int upload_textures(pt_context* c) {
+    if (c->deviceTextures) return tex_place_environment(c);
+    const auto t0 = std::chrono::steady_clock::now();
     std::vector<ptk::float4> pool; c->texInfos.clear();
     auto add = [&](const HostTexture& t) {
-        TexInfo ti; memset(&ti, 0, sizeof(ti)); ti.w = t.w; ti.h = t.h; ti.mipLevels = t.mipLevels; ti.base = pool.size();
-        size_t off = 0;
-        for (uint l = 0; l < t.mipLevels && l < 16; l++) { ti.mipOffset[l] = (uint)off; off += t.mips[l].size(); pool.insert(pool.end(), t.mips[l].begin(), t.mips[l].end()); }
+        TexInfo ti; memset(&ti, 0, sizeof(ti)); ti.w = t.w; ti.h = t.h; ti.base = pool.size();
+        if (t.mips.size() == 1) { ti.mipLevels = 1; pool.insert(pool.end(), t.mips[0].begin(), t.mips[0].end()); return ti; }      // (the environment image: level 0 only)
+        texi_layout(t.w, t.h, &ti.mipLevels, ti.mipOffset);
+        for (uint l = 0; l < t.mipLevels && l < 16; l++) pool.insert(pool.end(), t.mips[l].begin(), t.mips[l].end());
         return ti;
     };
     for (auto& t : c->textures) c->texInfos.push_back(add(t));
+    c->matTexels = pool.size();
     memset(&c->envTexInfo, 0, sizeof(TexInfo));
     if (c->envEnabled && c->envTex.w) c->envTexInfo = add(c->envTex);      // (a procedural sky alone has no image)
     // alpha planes (pt_scene.h AlphaPlane): the opacity channel of every texture's mip 0 on its own, a byte per texel where every value is k / 255
-    std::vector<ptk::AlphaPlane> planes(std::max<size_t>(1, c->textures.size())); std::vector<unsigned char> apool;
-    memset(planes.data(), 0, sizeof(ptk::AlphaPlane) * planes.size());
+    std::vector<uint> fmts(c->textures.size()); size_t poolBytes = 0;
     for (size_t ti = 0; ti < c->textures.size(); ti++) {
-        const HostTexture& t = c->textures[ti]; const std::vector<ptk::float4>& m0 = t.mips[0];
+        const std::vector<ptk::float4>& m0 = c->textures[ti].mips[0];
         bool bytes = true;
-        for (size_t k = 0; k < m0.size() && bytes; k++) { const float a = m0[k].w; const int q = (a >= 0.f && a <= 1.f) ? (int)(a * 255.0f + 0.5f) : -1; bytes = q >= 0 && (float)q / 255.0f == a; }
-        while (apool.size() % 16u) apool.push_back(0);
-        if (apool.size() + m0.size() * (bytes ? 1u : 4u) > 0xFFFFFFF0ull) return fail(c, PT_ERROR_UNSUPPORTED, "alpha planes above 4 GB are not supported");
-        if (t.w > 0xFFFFu || t.h > 0xFFFFu) return fail(c, PT_ERROR_UNSUPPORTED, "textures larger than 65535 texels on a side are not supported (the traversal's alpha test packs the size into 16 + 16 bits)");
-        ptk::AlphaPlane& ap = planes[ti]; ap.wh = (t.w & 0xFFFFu) | (t.h << 16); ap.offset = (uint)apool.size(); ap.fmt = bytes ? 0u : 1u;
-        if (bytes) for (size_t k = 0; k < m0.size(); k++) apool.push_back((unsigned char)(int)(m0[k].w * 255.0f + 0.5f));
-        else { const size_t at = apool.size(); apool.resize(at + 4u * m0.size()); for (size_t k = 0; k < m0.size(); k++) memcpy(&apool[at + 4u * k], &m0[k].w, 4); }
+        for (size_t k = 0; k < m0.size() && bytes; k++) bytes = texi_alpha_is_byte(m0[k].w);
+        fmts[ti] = bytes ? 0u : 1u;
     }
-    while (apool.size() % 16u || apool.empty()) apool.push_back(0);
-    PT_CHECK_HIP(c, c->dAlphaPlanes.upload(planes, c->stream)); PT_CHECK_HIP(c, c->dAlphaPool.upload(apool, c->stream));
+    { int r = tex_plan_alpha_planes(c, fmts, &poolBytes); if (r != PT_OK) return r; }
+    std::vector<unsigned char> apool(poolBytes, 0);
+    for (size_t ti = 0; ti < c->textures.size(); ti++) {
+        const std::vector<ptk::float4>& m0 = c->textures[ti].mips[0]; const size_t at = c->alphaPlanes[ti].offset;
+        if (!fmts[ti]) for (size_t k = 0; k < m0.size(); k++) apool[at + k] = (unsigned char)texi_alpha_byte(m0[k].w);
+        else for (size_t k = 0; k < m0.size(); k++) memcpy(&apool[at + 4u * k], &m0[k].w, 4);
+    }
+    PT_CHECK_HIP(c, c->dAlphaPlanes.upload(c->alphaPlanes, c->stream)); PT_CHECK_HIP(c, c->dAlphaPool.upload(apool, c->stream));
     PT_CHECK_HIP(c, c->dTexels.upload(pool, c->stream));
     PT_CHECK_HIP(c, c->dTexInfos.upload(c->texInfos, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     c->texDirty = false;
+    // (pt_get_texture_ingest_stats) what this path did and what it keeps: the converted texels of every level stay on the host for the next upload
+    PtTextureIngestStats& s = c->texStats; const double hostMs = c->texHostMs; memset(&s, 0, sizeof(s));
+    for (size_t ti = 0; ti < c->textures.size(); ti++) {
+        const HostTexture& t = c->textures[ti];
+        s.level0Texels += (uint64_t)t.w * t.h; s.sourceBytes += (uint64_t)t.w * t.h * (c->texFormats[ti] == PT_TEX_RGBA32F ? 16u : 4u); s.hostBytesHeld += host_texture_bytes(t);
+    }
+    s.hostBytesHeld += host_texture_bytes(c->envTex); s.poolTexels = pool.size();
+    s.uploadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); s.totalMs = hostMs + s.uploadMs;
     return PT_OK;
 }
 
@@ -621,6 +639,11 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
     { const char* e = getenv("MI355PT_DROP_INERT_TERMINAL"); if (e) c->dropInertTerminal = atoi(e) != 0; }      // developer A/B / test switch (0: every terminal hit is shaded, as before)
     // test switch: iterations after which the tail kernel hands a ray back (0: T8_TAIL_DEFER); a small value sends most rays through the hand-back path
     { const char* e = getenv("MI355PT_TAIL_DEFER"); if (e) c->tailDefer = (uint)strtoul(e, nullptr, 10); }
+    // PT_DEVICE_TEXTURES_ON_DEVICE: pt_set_materials converts the textures and builds their chains on the device (pt_texture_ingest.hip); the environment overrides the flag
+    c->deviceTextures = desc && (desc->flags & PT_DEVICE_TEXTURES_ON_DEVICE);
+    { const char* e = getenv("MI355PT_DEVICE_TEXTURES"); if (e) c->deviceTextures = atoi(e) != 0; }
+    // test switch: the bytes of the pinned staging buffer (both halves together), so that chunk boundaries fall inside small textures
+    { const char* e = getenv("MI355PT_TEXTURE_STAGING_BYTES"); if (e) c->texStagingBytes = std::max<size_t>(64u, (size_t)strtoull(e, nullptr, 10)); }
     memset(&c->dsc, 0, sizeof(c->dsc)); memset(&c->cam, 0, sizeof(c->cam)); memset(&c->bvh, 0, sizeof(c->bvh));
     pt_default_settings(reinterpret_cast<::PtSettings*>(&c->S));
     const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; memcpy(c->envToWorld.m, I, 48); memcpy(c->envToLocal.m, I, 48); c->envColorMul = ptk::make_float3(1.0f / ptk::kEnvMapRadianceScale);      // no params = tint 1, intensity 1: the cube holds radiance x 1/4
@@ -686,24 +709,17 @@ int32_t pt_set_instances(pt_context* c, const PtInstanceDesc* inst, uint32_t n) 
 int32_t pt_set_materials(pt_context* c, const ::PTMaterialData* mats, uint32_t nMats, const PtTextureDesc* tex, uint32_t nTex) {
     if (!c || (!mats && nMats) || (!tex && nTex)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "null argument");
     c->materials.resize(nMats); if (nMats) memcpy(c->materials.data(), mats, 128 * (size_t)nMats);
-    c->textures.clear();
+    (void)hipSetDevice(c->device);
+    const auto t0 = std::chrono::steady_clock::now();
+    c->textures.clear(); c->texFormats.clear();
     for (uint32_t i = 0; i < nTex; i++) {
         const PtTextureDesc& d = tex[i];
         if (!d.pixels || !d.width || !d.height || d.format > 2) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad texture descriptor");
         if (d.width > 32768u || d.height > 32768u) return fail(c, PT_ERROR_UNSUPPORTED, "textures above 32768 texels per side are not supported (16 mip levels)");
-        HostTexture t; t.w = d.width; t.h = d.height; t.mips.resize(1); t.mips[0].resize((size_t)d.width * d.height);
-        for (size_t k = 0; k < (size_t)d.width * d.height; k++) {
-            ptk::float4 v;
-            if (d.format == PT_TEX_RGBA32F) { const float* p = (const float*)d.pixels + 4 * k; v = ptk::make_float4(p[0], p[1], p[2], p[3]); }
-            else {
-                const uint8_t* p = (const uint8_t*)d.pixels + 4 * k;
-                v = ptk::make_float4((float)p[0] / 255.0f, (float)p[1] / 255.0f, (float)p[2] / 255.0f, (float)p[3] / 255.0f);
-                if (d.format == PT_TEX_RGBA8_SRGB) { v.x = srgb_to_linear(v.x); v.y = srgb_to_linear(v.y); v.z = srgb_to_linear(v.z); }
-            }
-            t.mips[0][k] = v;
-        }
-        build_mips(t);
-        c->textures.push_back(std::move(t));
+        HostTexture t;
+        if (c->deviceTextures) { t.w = d.width; t.h = d.height; t.mipLevels = texi_level_count(t.w, t.h); }      // sizes only: the texels are made on the device, below
+        else host_convert_texture(d, t);
+        c->textures.push_back(std::move(t)); c->texFormats.push_back(d.format);
     }
     for (uint32_t m = 0; m < nMats; m++) {
         const ptk::PTMaterialData& mm = c->materials[m];
@@ -713,7 +729,29 @@ int32_t pt_set_materials(pt_context* c, const ::PTMaterialData* mats, uint32_t n
             !chk(PTMaterialFlags_UseTransmissionTexture, mm.TransmissionTextureIndex))
             return fail(c, PT_ERROR_INVALID_ARGUMENT, "material references a missing texture");
     }
+    // the device path ingests here, while the caller's pixels are valid: no copy of them is kept (texDirty stays raised for the environment image's place in the new pool)
+    if (c->deviceTextures) { int r = tex_ingest_all(c, tex, nTex); if (r != PT_OK) return r; }
+    c->texHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->texDirty = true; c->geomDirty = true;
+    return PT_OK;
+}
+int32_t pt_update_texture(pt_context* c, uint32_t texture, const PtTextureDesc* d) {
+    if (!c || !d) return fail(c, PT_ERROR_INVALID_ARGUMENT, "null argument");
+    if (texture >= c->textures.size()) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_update_texture: no such texture in the last pt_set_materials");
+    if (!d->pixels || d->width != c->textures[texture].w || d->height != c->textures[texture].h || d->format != c->texFormats[texture])
+        return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_update_texture: the new pixels must have the texture's width, height and format");
+    if (c->deviceTextures) {
+        int r = tex_update_one(c, texture, d); if (r != PT_OK) return r;
+        refresh_scene_view(c);                       // (the alpha pool may have been allocated again)
+    } else {
+        // correctness only: the one texture converted on the host, then everything pooled, uploaded and finalised again (a plane may change its format and move the others)
+        (void)hipSetDevice(c->device);
+        const auto t0 = std::chrono::steady_clock::now();
+        host_convert_texture(*d, c->textures[texture]);
+        c->texHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        c->texDirty = true; c->geomDirty = true;
+    }
+    c->lightsDirty = true;                           // the emissive bake may read the texture
     return PT_OK;
 }
 // orientation and colour multiplier of the environment (EnvMapSceneParams), shared by the two image setters
@@ -1649,6 +1687,44 @@ int32_t pt_get_env_cube(pt_context* c, uint32_t* texelCount, uint32_t* dim, uint
         PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
         PT_CHECK_HIP(c, hipMemcpy(texels8B, c->dEnvCube.p, 8 * n, hipMemcpyDeviceToHost));
     }
+    return PT_OK;
+}
+// (the texture read-backs) prepare()'s texture step alone: they need no geometry
+static int32_t sync_textures(pt_context* c) {
+    (void)hipSetDevice(c->device);
+    if (c->texDirty) { int r = upload_textures(c); if (r != PT_OK) return r; refresh_scene_view(c); c->lightsDirty = true; c->envCubeDirty = true; }
+    return PT_OK;
+}
+int32_t pt_get_texture_level(pt_context* c, uint32_t texture, uint32_t mip, uint32_t* w, uint32_t* h, float* rgba, uint32_t capacityTexels) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    int r = sync_textures(c); if (r != PT_OK) return r;
+    if (texture >= c->texInfos.size() || mip >= c->texInfos[texture].mipLevels) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_texture_level: texture or mip out of range");
+    const TexInfo& ti = c->texInfos[texture]; const uint mw = texi_side(ti.w, mip), mh = texi_side(ti.h, mip);
+    if (w) *w = mw; if (h) *h = mh;
+    if (rgba) {
+        if (capacityTexels < (size_t)mw * mh) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_texture_level: buffer too small");
+        PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+        PT_CHECK_HIP(c, hipMemcpy(rgba, c->dTexels.p + ti.base + ti.mipOffset[mip], sizeof(ptk::float4) * (size_t)mw * mh, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+int32_t pt_get_alpha_plane(pt_context* c, uint32_t texture, uint32_t* fmt, void* out, uint32_t capacityBytes, uint32_t* bytes) {
+    if (!c) return PT_ERROR_INVALID_ARGUMENT;
+    int r = sync_textures(c); if (r != PT_OK) return r;
+    if (texture >= c->textures.size() || texture >= c->alphaPlanes.size()) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_alpha_plane: texture out of range");
+    const ptk::AlphaPlane& ap = c->alphaPlanes[texture]; const size_t n = texi_alpha_plane_bytes(c->textures[texture].w, c->textures[texture].h, ap.fmt == 0u);
+    if (fmt) *fmt = ap.fmt; if (bytes) *bytes = (uint32_t)n;
+    if (out) {
+        if (capacityBytes < n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_alpha_plane: buffer too small");
+        PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+        PT_CHECK_HIP(c, hipMemcpy(out, c->dAlphaPool.p + ap.offset, n, hipMemcpyDeviceToHost));
+    }
+    return PT_OK;
+}
+int32_t pt_get_texture_ingest_stats(pt_context* c, PtTextureIngestStats* out) {
+    if (!c || !out) return PT_ERROR_INVALID_ARGUMENT;
+    int r = sync_textures(c); if (r != PT_OK) return r;      // (the host path ingests at its upload)
+    *out = c->texStats;
     return PT_OK;
 }
 int32_t pt_get_subinstances(pt_context* c, uint32_t* count, void* out) {

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/mi355pt.h"
 #include "pt_wavefront.h"
+#include "pt_texture_ingest.h"
 #include "pt_stableplanes_launch.h"
 #include "pt_denoiser.h"
 #include "pt_build.h"
@@ -108,6 +109,10 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 // pt_render: once every live batch holds fewer paths than this, the batches stop advancing in lockstep (0: lockstep to the end)
 #define PT_FREE_RUN_BELOW (1u << 22)
 #endif
+#ifndef PT_TEXTURE_STAGING_BYTES
+// the pinned staging buffer a device texture ingest streams the source pixels through, both halves together (pt_texture_ingest.hip; MI355PT_TEXTURE_STAGING_BYTES: tests)
+#define PT_TEXTURE_STAGING_BYTES (64u << 20)
+#endif
 #ifndef PT_PIPELINE_BATCHES
 // independent sub-frame batches pt_render keeps in flight on separate streams (A/B on C3 in DESIGN.md)
 #define PT_PIPELINE_BATCHES 4
@@ -201,6 +206,11 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // ...Sh: the visibility rays' own straggler state in a frame of fused traversal launches
     DevBuf<ptk::TravTask> dTaskQSh; DevBuf<uint> dResolveListSh; DevBuf<unsigned long long> dBestKeySh;
     std::vector<TexInfo> texInfos; TexInfo envTexInfo;
+    // textures (pt_texture_ingest.hip). deviceTextures: PT_DEVICE_TEXTURES_ON_DEVICE — `textures` then holds sizes only. texFormats: the source format of every texture;
+    // alphaPlanes: the host's copy of the plane table; matTexels: the texels of the material textures in the pool, where the environment image starts; texStagingBytes: the
+    // pinned staging buffer of an ingest, both halves; texStats: of the last ingest or update; texHostMs: the host time of the last pt_set_materials
+    bool deviceTextures = false; std::vector<uint> texFormats; std::vector<ptk::AlphaPlane> alphaPlanes; size_t matTexels = 0, texStagingBytes = PT_TEXTURE_STAGING_BYTES;
+    PtTextureIngestStats texStats = {}; double texHostMs = 0;
     BvhBuildBuffers bvh; bool bvhAllocated = false; uint numTris = 0; uint bvhBuilder = BVH_BUILDER_SAH;
     DeviceScene dsc;
     // frame state
@@ -277,6 +287,13 @@ inline ptk::DenoiserBuffers dn_buffers(pt_context* c) {
 }
 // ---- pt_skin.hip: the device skinning pass over the ranges of `s`, in place on the scene's streams
 void launch_skin(const SkinView& s, const double* matrices, const double* morphWeights, float* positions, uint* normals, uint* tangents, hipStream_t st);
+// ---- pt_texture_ingest.hip: the texture pool made on the device (PT_DEVICE_TEXTURES_ON_DEVICE). tex_plan_alpha_planes: the plane table of `textures` for the given plane
+// formats (0 = bytes, 1 = floats) into c->alphaPlanes, and the bytes of the alpha pool — both paths' layout; tex_ingest_all: pt_set_materials' textures, from the caller's
+// pixels to the pool, the chains and the planes; tex_update_one: pt_update_texture's fast path; tex_place_environment: the lat-long image behind the material textures
+int tex_plan_alpha_planes(pt_context* c, const std::vector<uint>& fmts, size_t* poolBytes);
+int tex_ingest_all(pt_context* c, const PtTextureDesc* tex, uint32_t n);
+int tex_update_one(pt_context* c, uint32_t index, const PtTextureDesc* desc);
+int tex_place_environment(pt_context* c);
 // ---- pt_relax_api.hip: the device denoiser's history is dropped (resize to another size, new scene) / its buffers freed
 void relax_drop_history(pt_context* c);
 void relax_free(pt_context* c);
