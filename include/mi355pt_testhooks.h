@@ -35,6 +35,28 @@ int32_t pt_get_inert_terminal(pt_context* ctx, uint32_t* numPrims, uint32_t* wor
  * read: after a refit (pt_animate without rebuild) the binary tree, the primitive-order triangles and the range tables of the last full build hold an older pose and stay out. */
 int32_t pt_get_bvh8(pt_context* ctx, uint32_t* numNodes, void* nodes, uint32_t capacityNodes, uint32_t* numTris, void* tris, uint32_t capacityTris, float* bounds,
                     uint32_t* collapseLevels, uint32_t* wideLevelStart, uint32_t capacityLevels);
+/* A caller's rays through the traversal launches a FRAME runs, for tests/test_gpu_traversal_routes.py: pt_trace_closest / pt_trace_visibility run a probe kernel whose
+ * instantiation of the traverser (no fixed interval, no sub-tree tasks, no splitting) no frame uses. rays: n x 8 floats, origin | tmin | direction | tmax, as pt_trace_closest
+ * takes them. Everything the launches write is owned by the call: the context's pool, queues and counters are untouched.
+ *   PT_ROUTE_EXTEND         the rays stand in a path pool as k_generate stores them (origin | id, direction | length), behind an identity queue; launch_extend: k_extend, the
+ *                           sub-tree task rounds of that count, k_resolve_extend. The interval is [0, kMaxRayTravel] whatever a ray says, so rays that say anything else
+ *                           (tmin != 0, tmax != 1e15f) are refused. out: n x 4 words, t | primitive | u | v — the pool's hit records.
+ *   PT_ROUTE_EXTEND_RANGED  the same with launch_extend(..., ranged): every ray's (tmin, tmax) waits in the first two words of its hit record (the stable-plane fill pass's first launch).
+ *   PT_ROUTE_SHADOW         the rays stand in a shadow queue of the grouped layout, one entry per group (origin | tmax, direction | entry, radiance zero); tmin must be 0.
+ *                           launch_shadow: k_shadow, its task rounds, the marking resolve pass (and the fold of the marks into a path pool of the call's own). out: n words,
+ *                           1 = visible (the entry's mark), 0 = occluded.
+ *   PT_ROUTE_PACKETS        32 rays per wave on one stack (traverse8_packets), read from the same pool; the packets over the step cap or the stack bound leave their rays on a
+ *                           list that launch_extend then traces one by one, task rounds included — what launch_extend_first does for camera rays. Fixed interval, as EXTEND.
+ * options (may be null; a zero field is the product's value): taskCap = entries of a task queue (TASK_QUEUE_CAPACITY); maxBlocks = TravAux::maxBlocks, the grid bound of the
+ * traversal launches; stepCap / stackBound = FirstPackets' (T8_PACKET_STEP_CAP, T8_PACKET_STACK).
+ * stats (may be null), written whenever the launches ran: splitRays = the resolve list's length (rays cut into sub-trees); taskCounts[r] = sub-trees fed to task round r;
+ * packetRays = rays the packets committed themselves, leftoverRays = rays they left over (both 0 on the other routes); overflow = WaveCounters::overflow after the launches
+ * (1: a stack tail, 2: a task queue or the leftover list ran out of room). A set overflow word is PT_ERROR_HIP, as at the end of pt_render — `out` is then not the answer.
+ * A ray whose tmin is negative, -0 or NaN is refused before anything reaches the device (pt_trace_closest's rule), an unknown route too. */
+enum { PT_ROUTE_EXTEND = 0, PT_ROUTE_EXTEND_RANGED = 1, PT_ROUTE_SHADOW = 2, PT_ROUTE_PACKETS = 3 };
+typedef struct PtRouteOptions { uint32_t taskCap, maxBlocks, stepCap, stackBound; } PtRouteOptions;
+typedef struct PtRouteStats { uint32_t splitRays, taskCounts[4], packetRays, leftoverRays, overflow; } PtRouteStats;
+int32_t pt_trace_route(pt_context* ctx, int32_t route, const float* rays, uint32_t n, const PtRouteOptions* options, void* out, PtRouteStats* stats);
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,7 @@ EXPORTS = [
     "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
-TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal", "pt_get_bvh8"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
+TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal", "pt_get_bvh8", "pt_trace_route"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
 
 
 class PtError(RuntimeError):
@@ -1578,6 +1578,28 @@ class PathTracer:
         if n.value: self._chk(self.L.pt_get_inert_terminal(self.h, None, _p(words), words.size, None), "pt_get_inert_terminal")
         prim = np.arange(n.value, dtype=np.uint32)
         return ((words[prim // 16] >> (2 * (prim % 16))) & 3).astype(np.uint32), int(dropped.value)
+
+    ROUTES = {"extend": 0, "extend_ranged": 1, "shadow": 2, "packets": 3}
+
+    def trace_route(self, route, rays, task_cap=0, max_blocks=0, step_cap=0, stack_bound=0):
+        """pt_trace_route (include/mi355pt_testhooks.h): rays [n, 8] (origin | tmin | direction | tmax) through the traversal launches a frame runs. route: "extend",
+        "extend_ranged", "packets" (-> hit records [n, 4] float32: t | primitive bits | u | v) or "shadow" (-> [n] uint32, 1 = visible), or the route's number. The options: 0
+        is the product's value. Returns (out, stats): stats = dict of split (rays cut into sub-trees), tasks (sub-trees fed to each of the four task rounds), packet_rays,
+        leftover_rays, overflow. An error of the call is raised as PtError with the stats of the launches, where they ran, in its .stats. Only on a PathTracer(test_hooks=True)."""
+        if not self.test_hooks: raise RuntimeError("pt_trace_route is not part of the shipped library: PathTracer(test_hooks=True)")
+        route = self.ROUTES.get(route, route)
+        rays = np.ascontiguousarray(rays, np.float32); n = rays.shape[0]
+        out = np.zeros(n, np.uint32) if route == 2 else np.zeros((n, 4), np.float32)
+        opt = np.array([task_cap, max_blocks, step_cap, stack_bound], np.uint32); st = np.full(8, 0xFFFFFFFF, np.uint32)
+        f = self.L.pt_trace_route; f.restype = ctypes.c_int32
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        r = f(self.h, int(route), _p(rays), n, _p(opt), _p(out), _p(st))
+        stats = None if (st == 0xFFFFFFFF).all() else dict(split=int(st[0]), tasks=[int(x) for x in st[1:5]], packet_rays=int(st[5]), leftover_rays=int(st[6]), overflow=int(st[7]))
+        try:
+            self._chk(r, "pt_trace_route")
+        except PtError as e:
+            e.stats = stats; raise
+        return out, stats
 
     def get_bvh8(self, short_by=0):
         """pt_get_bvh8 (include/mi355pt_testhooks.h): the wide tree as the traversal reads it — dict of nodes [numNodes8, 32] uint32 (the 128-byte Bvh8Node records), tris

@@ -108,5 +108,7 @@ void launch_tonemap(const float4* accum, uint num, const ToneMapParams& p, uint*
 // scratch: 2 * pow2floor(W) * pow2floor(H) floats; *result points at the 1x1 mip inside scratch once the stream has drained
 void launch_average_log_luminance(const float4* accum, uint W, uint H, float* scratch, float** result, hipStream_t st);
 void launch_probe(const PathKernelContext& k, int kind, const void* dIn, void* dOut, uint n, hipStream_t st);
+// (test hooks: pt_trace_route's packet route) the `count` rays stored in pool.s0 / s1 as packets, hits to pool.hit; *committed counts the rays the packets reported themselves
+void launch_route_packets(const DeviceScene& sc, PathPool pool, const uint* countPtr, uint count, WaveCounters* wc, FirstPackets pk, uint* committed, uint maxBlocks, hipStream_t st);
 
 } // namespace ptk

@@ -144,8 +144,11 @@ __device__ __forceinline__ uint t8_tasks_per_chunk(uint count) { return (!T8_TAS
 template <int STAGE, bool FINAL>
 __device__ __forceinline__ void t8_extend_tasks_body(const DeviceScene& sc, const PathPool& pool, WaveCounters* wc, const TravAux& aux, uint2* stack, uint* rayBuf, const uint vBlock, const uint vGrid) {
     constexpr int IN = STAGE & 1;
-    uint count = aux.counts[STAGE]; if (count > aux.taskCap) count = aux.taskCap;
-    if (count == 0u) return;
+    // A count above the capacity: the producer ran out of room (it has set the overflow word, and the frame fails at its end). Such a queue is not read at all: a ray's
+    // reservation that straddles the end is not written (pt_traverse8p.h: all of a ray's sub-trees or none), so the entries from there to the capacity hold whatever the
+    // memory held — stale tasks of an earlier launch, or nothing ever written — and a tag or a node reference taken from there indexes the pool and the tree out of bounds.
+    const uint count = aux.counts[STAGE];
+    if (count == 0u || count > aux.taskCap) return;
     const TravTask* tasks = aux.taskQ[IN];
     const uint real = t8_tasks_per_chunk(count), per = (count + real - 1u) / real;
     Traverse8Counters ctr; t8_counters_init(ctr);
@@ -437,8 +440,8 @@ __global__ void __launch_bounds__(T8_BLOCK, COUNT ? 1 : T8_SHADOW_MIN_WAVES) k_s
 template <int STAGE, bool FINAL>
 __device__ __forceinline__ void t8_shadow_tasks_body(const DeviceScene& sc, const ShadowQueue& sq, WaveCounters* wc, const TravAux& aux, uint2* stack, uint* rayBuf, const uint vBlock, const uint vGrid) {
     constexpr int IN = STAGE & 1;
-    uint count = aux.counts[STAGE]; if (count > aux.taskCap) count = aux.taskCap;
-    if (count == 0u) return;
+    const uint count = aux.counts[STAGE];
+    if (count == 0u || count > aux.taskCap) return;      // (an overflowed queue is not read: t8_extend_tasks_body)
     const TravTask* tasks = aux.taskQ[IN];
     const uint real = t8_tasks_per_chunk(count), per = (count + real - 1u) / real;
     Traverse8Counters ctr; t8_counters_init(ctr);
@@ -1208,6 +1211,23 @@ void launch_bake_emissive(const DeviceScene& sc, const uint* subInstList, const 
 #ifdef MI355PT_TEST_HOOKS
 void launch_probe(const PathKernelContext& k, int kind, const void* dIn, void* dOut, uint n, hipStream_t st) {
     hipLaunchKernelGGL(k_probe, dim3((n + 63) / 64), dim3(64), 0, st, k, kind, (const float*)dIn, (float*)dOut, n);
+}
+// pt_trace_route's packet route: k_extend_first_packets for rays that are STORED (pool.s0 / s1, as k_generate writes them) instead of formed from a camera — the same
+// traverse8_packets, the same commit, the same leftover list; *committed counts the calls of commit. The rays the packets leave over are the caller's to trace (launch_extend
+// with the list as its queue: what k_extend_first_listed is to k_extend_first).
+__global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_route_packets(DeviceScene sc, PathPool pool, const uint* __restrict__ countPtr, WaveCounters* wc, FirstPackets pk, uint* committed) {
+    __shared__ uint2 stack[(T8_BLOCK / 64u) * T8_PACKET_STACK];
+    __shared__ float2 mineUV[T8_BLOCK];
+    auto form = [&](uint i, float3& o, float3& d) {
+        const uint4 a = pool.s0[i], b = pool.s1[i];
+        o = make_float3(asfloat(a.x), asfloat(a.y), asfloat(a.z)); d = make_float3(asfloat(b.x), asfloat(b.y), asfloat(b.z));
+    };
+    auto commit = [&](uint p, const HitInfo& h) { pool.hit[p] = make_uint4(asuint(h.t), h.prim, asuint(h.u), asuint(h.v)); atomicAdd(committed, 1u); };
+    traverse8_packets(sc, *countPtr, stack, mineUV, form, commit, pk, &wc->overflow);
+}
+void launch_route_packets(const DeviceScene& sc, PathPool pool, const uint* countPtr, uint count, WaveCounters* wc, FirstPackets pk, uint* committed, uint maxBlocks, hipStream_t st) {
+    const uint gp = grid_for(count, (T8_BLOCK / 64u) * T8_PACKET_RAYS, (maxBlocks && maxBlocks < T8_MAX_BLOCKS) ? maxBlocks : T8_MAX_BLOCKS);      // (launch_extend_first's packet grid)
+    hipLaunchKernelGGL(k_route_packets, dim3(gp), dim3(T8_BLOCK), 0, st, sc, pool, countPtr, wc, pk, committed);
 }
 #endif
 

@@ -1,5 +1,5 @@
-"""The zoo of the hit-test reference tests (tests/test_hit_reference.py on the oracle, tests/test_gpu_hit_reference.py on the device): small scenes (<= ~1 000 triangles) and
-ray sets (<= 20 000 rays) at the places where a float32 hit test goes wrong — geometry whose flat axis sits at a large coordinate, the offset given in the vertices or in the
+"""The zoo of the hit-test reference tests (tests/test_hit_reference.py on the oracle, tests/test_gpu_hit_reference.py on the device; tests/test_gpu_traversal_routes.py takes
+some of it through the traversal launches of a frame): small scenes (<= ~1 000 triangles; the two tube cases: 4 096) and ray sets (<= 20 000 rays) at the places where a float32 hit test goes wrong — geometry whose flat axis sits at a large coordinate, the offset given in the vertices or in the
 instance transform, very small and very large scenes, ray origins very near and very far, axis-parallel / grazing / tied directions, and an instance moved after the build.
 
 A case is a dict: name, sc (scene dict), V (world-space float32 vertices as float64 [T, 3, 3], tests/hit_ref.py world_triangles), rays [n, 8] float32, and — for the refit
@@ -65,7 +65,18 @@ def _tiny_in_large():
     return np.concatenate([t] + far), np.arange(9, dtype=np.uint32)
 
 
-GEOMETRY = {"quadx": lambda: _quad(0), "quady": lambda: _quad(1), "quadz": lambda: _quad(2), "box": _box, "ico": _icosphere, "fan": _fan, "grid": _grid, "tiny": _tiny_in_large}
+def _tube(n=4096, length=64.0, half=0.5, jitter=0.02):
+    """n small triangles scattered through a long thin box, [0, length] x [-half, half]^2: each vertex is its triangle's centre plus uniform(-jitter, jitter)^3. A ray
+    down the tube's axis that hits nothing walks the whole tree: the rays of a traversal launch that outlive their wave's other rays and are cut into sub-tree tasks
+    (tests/test_gpu_traversal_routes.py)"""
+    rng = np.random.default_rng(0x70BE)
+    c = np.stack([rng.uniform(0.0, length, n), rng.uniform(-half, half, n), rng.uniform(-half, half, n)], 1)
+    p = c[:, None, :] + rng.uniform(-jitter, jitter, (n, 3, 3))
+    return p.reshape(-1, 3), np.arange(3 * n, dtype=np.uint32)
+
+
+TUBE = dict(length=64.0, half=0.5)
+GEOMETRY = {"quadx": lambda: _quad(0), "quady": lambda: _quad(1), "quadz": lambda: _quad(2), "box": _box, "ico": _icosphere, "fan": _fan, "grid": _grid, "tiny": _tiny_in_large, "tube": _tube}
 ROTATED = {"ico": (0.731, (1.7, 0.9, 1.3)), "fan": (0.4, (1.0, 0.8, 1.1))}      # rot_y, non-uniform scale of the instance
 
 
@@ -119,14 +130,28 @@ def make_rays(V, dist, kind, n, rng, aim=None, variants=True):
     d = np.concatenate([d, _unit(rng.normal(size=(n - n_on, 3)))]); tgt = np.concatenate([tgt, off_tgt])
     o = tgt - d * (dist * diag)
     rays = np.concatenate([o, np.zeros((n, 1)), d, np.full((n, 1), 1e30)], 1).astype(np.float32)
-    if not variants: return rays
-    m = n // 5
+    return _with_variants(V, rays, dist * diag) if variants else rays
+
+
+def _with_variants(V, rays, length):
+    """the n rays, then four interval variants of the first n // 5 (module docstring); length: the t a ray without a clear hit gets its variants around"""
+    m = len(rays) // 5
     base = hit_ref.Reference(V, rays[:m])
-    t1 = np.where(base.any_hit, base.first, dist * diag); mg = 4.0 * np.where(base.any_hit, base.first_Bt, 1e-5 * dist * diag)
+    t1 = np.where(base.any_hit, base.first, length); mg = 4.0 * np.where(base.any_hit, base.first_Bt, 1e-5 * length)
     out = [rays]
     for col, val in ((7, t1 - mg), (7, t1 + mg), (3, t1 - mg), (3, t1 + mg)):
         r = rays[:m].copy(); r[:, col] = np.maximum(val, 0.0).astype(np.float32); out.append(r)          # (tmin >= +0: DXR's rule, and pt_trace_closest's)
     return np.concatenate(out)
+
+
+def make_tube_rays(n, rng, offset, V):
+    """[n + 4 * (n // 5), 8]: n rays down the tube, from a point of the square on the plane x = -1 to a point of the square on the plane x = length + 1 (both uniform),
+    and their interval variants"""
+    L, h = TUBE["length"], TUBE["half"]
+    a = np.concatenate([np.full((n, 1), -1.0), rng.uniform(-h, h, (n, 2))], 1) + np.asarray(offset, np.float64)
+    b = np.concatenate([np.full((n, 1), L + 1.0), rng.uniform(-h, h, (n, 2))], 1) + np.asarray(offset, np.float64)
+    rays = np.concatenate([a, np.zeros((n, 1)), _unit(b - a), np.full((n, 1), 1e30)], 1).astype(np.float32)
+    return _with_variants(V, rays, L + 2.0)
 
 
 def _specs():
@@ -165,6 +190,8 @@ def _specs():
     add("grid-dist8", "grid", large, dist=float(MAX_ORIGIN_DIAGONALS)); add("grid-refit-to-1e3", "grid", large, refit=(1e3, 1e3, 1e3))
     add("tiny-in-1e3-scene", "tiny", small, dist=1e-5, aim=(0,))          # origins 0.01 units = 10 triangle sizes away
     add("tiny-in-1e3-scene-axis", "tiny", small, dist=1e-5, aim=(0,), kind="axis")
+    # the deep cases (appended: a case's seed is its index): thousands of triangles, and rays that walk all of them
+    add("tube-4096", "tube", 2048, kind="tube"); add("tube-4096-1e3-all", "tube", 2048, offset=(1e3, 1e3, 1e3), kind="tube")
     return S
 
 
@@ -183,7 +210,7 @@ def case(name):
         moved["transform"][0][[3, 7, 11]] += np.asarray(s["refit"], np.float32)
     V = hit_ref.world_triangles(sc, moved)
     rng = np.random.default_rng(0x417C0DE + NAMES.index(name))
-    rays = make_rays(V, s["dist"], s["kind"], s["n"], rng, aim=s["aim"])
+    rays = make_tube_rays(s["n"], rng, s["offset"], V) if s["kind"] == "tube" else make_rays(V, s["dist"], s["kind"], s["n"], rng, aim=s["aim"])
     return dict(name=name, sc=sc, V=V, rays=rays, moved=moved)
 
 

@@ -49,10 +49,12 @@ def test_the_two_routes_of_the_reference_agree():
 @pytest.mark.parametrize("name", hit_cases.NAMES)
 def test_oracle_hit_test_against_the_float64_reference(name):
     c = hit_cases.case(name); ref = hit_cases.reference(name)
-    assert len(c["V"]) <= 1100 and len(c["rays"]) <= 20000
+    deep = hit_cases.SPECS[name]["geom"] == "tube"      # the two deep cases: thousands of small triangles, and most rays thread the whole tube without a hit
+    assert len(c["V"]) <= (20000 if deep else 1100) and len(c["rays"]) <= 20000
     print("%s: %d triangles, %d rays, skipped share %.4f" % (name, len(c["V"]), len(c["rays"]), ref.skipped_share()))
     assert ref.skipped_share() <= MAX_SKIPPED, "%s: the reference skips %.2f %% of the rays" % (name, 100 * ref.skipped_share())
-    assert ref.any_hit.mean() > 0.4 and ref.all_miss.any()
+    assert ref.any_hit.mean() > (0.3 if deep else 0.4) and ref.all_miss.any()
+    if deep: assert ref.all_miss.mean() > 0.3      # (rays that walk the whole tree: what these cases are for)
     o = _oracle(c)
     try:
         hit_ref.check_closest(ref, o.trace_closest(c["rays"]), name + " (BVH)")
