@@ -96,9 +96,9 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 #define PT_FIRST_VERTEX_IN_PLACE 1
 #endif
 #ifndef PT_FIRST_VERTEX_PACKETS
-// ... and that first pass traces its camera rays as 32-ray packets on one shared stack per wave (pt_traverse8k.h; environment MI355PT_FIRST_VERTEX_PACKETS overrides,
-// 0: k_extend_first, one ray per lane pair)
-#define PT_FIRST_VERTEX_PACKETS 1
+// ... and that first pass traces its camera rays as packets on one shared stack per wave (pt_traverse8k.h; environment MI355PT_FIRST_VERTEX_PACKETS overrides):
+// 0: k_extend_first, one ray per lane pair; 1: 32-ray packets in the lane-pair layout; 2: 64-ray packets, one lane per ray
+#define PT_FIRST_VERTEX_PACKETS 2
 #endif
 #ifndef PT_DROP_INERT_TERMINAL
 // pt_render: k_classify leaves out the hits of terminating paths (PF_terminateAtNextBounce) on primitives that can neither emit nor stand in for an analytic light — their
@@ -125,8 +125,8 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
     hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
     uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool occlusionSlotOrder = true, compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
-    // vertex 0 as packets (ptk::FirstPackets): the switch, the step cap and stack bound of a packet (0: T8_PACKET_STEP_CAP / T8_PACKET_STACK), the leftover list (one word per path)
-    bool firstVertexPackets = PT_FIRST_VERTEX_PACKETS != 0; uint packetStepCap = 0, packetStack = 0; DevBuf<uint> dFirstLeftover;
+    // vertex 0 as packets (ptk::FirstPackets): the switch (0 / 1 / 2, as above), the step cap and stack bound of a packet (0: T8_PACKET_STEP_CAP or T8_PACKET64_STEP_CAP / T8_PACKET_STACK), the leftover list (one word per path)
+    uint firstVertexPackets = PT_FIRST_VERTEX_PACKETS; uint packetStepCap = 0, packetStack = 0; DevBuf<uint> dFirstLeftover;
     // pt_render's classified passes drop the terminal hits that can add nothing (k_classify, pt_wavefront.hip); droppedTerminal: how many the last pt_render call dropped
     bool dropInertTerminal = PT_DROP_INERT_TERMINAL != 0; unsigned long long droppedTerminal = 0;
     std::string lastError;

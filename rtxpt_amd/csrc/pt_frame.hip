@@ -161,7 +161,7 @@ struct RenderBatch : Batch {
     uint pendingShadow = 0; TravAux auxSh;                          // fused traversal launches (enable_fused)
     PathPool poolSet[2]; uint set = 0; bool compact = false;        // the compacted pool (enable_compact_pool)
     bool firstInPlace = false;                                      // no k_generate: the first pass forms the vertex-0 state itself (enable_first_vertex_in_place)
-    FirstPackets packets = {nullptr, nullptr, 0u, 0u, 0u};          // ... and traces its camera rays as packets (leftover == nullptr: one by one)
+    FirstPackets packets = {nullptr, nullptr, 0u, 0u, 0u, 0u};          // ... and traces its camera rays as packets (leftover == nullptr: one by one)
     bool timed = false; Events marks; size_t t0 = 0, t1 = 0;
     struct Span { size_t a, b; int kind; uint items; }; std::vector<Span> spans;      // kind: 0 extend, 1 shade, 2 shadow, 3 tail
     size_t mark() { return timed ? marks.mark(st) : 0; }
@@ -273,12 +273,14 @@ struct RenderFrame {
     // 4 spp — walk almost the same nodes, and one ray per lane pair repeats the per-ray bookkeeping 32 times over. k_extend_first_packets walks them on one stack per wave;
     // the packets over the step cap leave their rays on the batch's slice of dFirstLeftover (count: word PASS_LEFTOVER of the pass's counter block, zeroed with it), and
     // k_extend_first's loop traces those behind it, straggler machinery included. Same hits at the same positions: nothing else of the pass knows.
+    // c->firstVertexPackets == 2 (the default): 64-ray packets, one lane per ray — two rows of the block — through k_extend_first_packets64 (traverse8_packets64), step cap
+    // T8_PACKET64_STEP_CAP; 1: the 32-ray packets above.
     int32_t enable_first_vertex_packets() {
         PT_CHECK_HIP(c, c->dFirstLeftover.resize(c->poolCapacity));
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b]; if (!t.firstInPlace) continue;
             t.packets = FirstPackets{c->dFirstLeftover.p + t.base, t.aux.counts + PASS_LEFTOVER, t.total,
-                                     c->packetStepCap ? c->packetStepCap : (uint)T8_PACKET_STEP_CAP, c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK};
+                                     c->packetStepCap ? c->packetStepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u};
         }
         return PT_OK;
     }

@@ -15,6 +15,9 @@
 //
 // A packet that needs more than `stepCap` steps, or a deeper stack than `stackBound`, commits nothing: its rays go to a leftover list (one atomic per packet) that the
 // per-ray kernel traces from scratch behind this launch (pt_wavefront.hip launch_extend_first).
+//
+// Two traversers: traverse8_packets (32 rays, the lane-pair layout described above) and, further down, traverse8_packets64 (64 rays, one lane per ray, the uniform part
+// of a step in scalar registers), which the frame uses by default (MI355PT_FIRST_VERTEX_PACKETS, pt_context.h).
 #pragma once
 #include "pt_traverse8p.h"
 #include "pt_wavefront.h"
@@ -148,6 +151,167 @@ __device__ __forceinline__ void traverse8_packets(const DeviceScene& sc, const u
             else if (lane == 0u) atomicOr(overflowFlag, 2u);
         } else if (valid) {
             t8_report_closest(i, h, bestT, bestPrim, minePrim, mineUV, commit);
+        }
+    }
+}
+
+// ---- 64-ray packets, ONE LANE PER RAY: lane L of a wave holds ray 64 p + L of packet p (at 4 spp: two rows of an 8 x 8 block of the owned-pixel list), forms it once, tests
+// all eight children of the node in hand and both triangles of a leaf for it, and reports its own hit — no pair, no hand-off of barycentrics through LDS. What is wave-uniform
+// lives in scalar registers: the node's 128 bytes (scalar loads; T8_PACKET64_VECTOR_NODE: vector loads at a uniform address, the A/B partner), the per-child minimum of the
+// entry-distance keys (reduced over the wave only for a child whose ballot of "some ray enters" is non-zero), the order of the entered children (a sorting network of scalar
+// min / max on the unique keys distance | child), the stack pointer, the step count, the packet's largest best t.
+//
+// The three invariants above hold as they do for traverse8_packets, and the result is bit for bit the single-ray kernel's for the same reason:
+//  - a child is visited if ANY ray's own slab test enters it: its bit of the hit mask is the ballot of T8_HIT over the lanes, each on its own t8_slab interval;
+//  - a stack entry carries a value no larger than any entering ray's entry distance: the wave minimum of the entering lanes' keys with the three index bits cleared;
+//  - an entry is dropped unvisited only when that value exceeds the largest best t over the packet's valid rays (maxBest, taken over the valid lanes after every leaf that
+//    produced a candidate).
+// The slab test, the ray frame, the selectors and the leaf block are pt_traverse8.h's functions on the same operands; the leaf block runs once as lane h = 0 and once as lane
+// h = 1 of a pair, and the second call's candidate has to beat the first's in the order (t, primitive): the pair's minimum.
+#ifndef T8_PACKET64_MIN_BLOCKS
+#define T8_PACKET64_MIN_BLOCKS 7   // waves per SIMD the register allocator leaves room for in the 64-ray packet kernels (72 VGPRs; at 8 / 64 VGPRs it spills eight registers, some inside the leaf step)
+#endif
+#ifndef T8_PACKET64_VECTOR_NODE
+#define T8_PACKET64_VECTOR_NODE 0
+#endif
+typedef uint u32x16 __attribute__((ext_vector_type(16)));
+#if T8_PACKET64_VECTOR_NODE
+typedef const u32x16* T8kNodeHalf;
+#else
+typedef const __attribute__((address_space(4))) u32x16* T8kNodeHalf;      // constant address space: s_load_dwordx16 (the tree is not written while a frame is traced)
+#endif
+// the minimum / maximum of v over the wave, as a scalar: four exchanges within a row of sixteen lanes (every lane then holds its row's value), lane 15 of rows 0 and 2 to
+// rows 1 and 3 (row_bcast:15), lane 31 to rows 2 and 3 (row_bcast:31) — lane 63 holds the wave's. The rows a broadcast does not write get the operation's identity.
+#define DPP_ROW_BCAST15 0x142
+#define DPP_ROW_BCAST31 0x143
+template <int CTRL, int ROWS> __device__ __forceinline__ uint t8k_dpp_rows(uint v, uint identity) { return (uint)__builtin_amdgcn_update_dpp((int)identity, (int)v, CTRL, ROWS, 0xF, false); }
+__device__ __forceinline__ uint t8k_wave_min(uint v) {
+    v = t8k_min(v, dpp_u<DPP_QP_XOR1>(v)); v = t8k_min(v, dpp_u<DPP_QP_XOR2>(v)); v = t8k_min(v, dpp_u<DPP_ROW_ROR(4)>(v)); v = t8k_min(v, dpp_u<DPP_ROW_ROR(8)>(v));
+    v = t8k_min(v, t8k_dpp_rows<DPP_ROW_BCAST15, 0xA>(v, 0xFFFFFFFFu)); v = t8k_min(v, t8k_dpp_rows<DPP_ROW_BCAST31, 0xC>(v, 0xFFFFFFFFu));
+    return (uint)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ uint t8k_wave_max(uint v) {
+    v = t8k_max(v, dpp_u<DPP_QP_XOR1>(v)); v = t8k_max(v, dpp_u<DPP_QP_XOR2>(v)); v = t8k_max(v, dpp_u<DPP_ROW_ROR(4)>(v)); v = t8k_max(v, dpp_u<DPP_ROW_ROR(8)>(v));
+    v = t8k_max(v, t8k_dpp_rows<DPP_ROW_BCAST15, 0xA>(v, 0u)); v = t8k_max(v, t8k_dpp_rows<DPP_ROW_BCAST31, 0xC>(v, 0u));
+    return (uint)__builtin_amdgcn_readlane((int)v, 63);
+}
+// eight wave-uniform keys into ascending order: the 19 compare-exchanges of the optimal 8-input network, each a scalar min and a scalar max
+__device__ __forceinline__ void t8k_sort8(uint (&s)[8]) {
+#define T8K_CE(a, b) { const uint lo_ = t8k_min(s[a], s[b]), hi_ = t8k_max(s[a], s[b]); s[a] = lo_; s[b] = hi_; }
+    T8K_CE(0, 2) T8K_CE(1, 3) T8K_CE(4, 6) T8K_CE(5, 7)
+    T8K_CE(0, 4) T8K_CE(1, 5) T8K_CE(2, 6) T8K_CE(3, 7)
+    T8K_CE(0, 1) T8K_CE(2, 3) T8K_CE(4, 5) T8K_CE(6, 7)
+    T8K_CE(2, 4) T8K_CE(3, 5)
+    T8K_CE(1, 4) T8K_CE(3, 6)
+    T8K_CE(1, 2) T8K_CE(3, 4) T8K_CE(5, 6)
+#undef T8K_CE
+}
+
+// Ray: void form(uint i, float3& o, float3& d) — ray i of the launch, formed once, by the lane that holds it. Dst: void commit(uint i, const HitInfo&), by the same lane.
+template <class Ray, class Dst>
+__device__ __forceinline__ void traverse8_packets64(const DeviceScene& sc, const uint count, uint2* stackBase, Ray form, Dst commit, const FirstPackets pk, uint* overflowFlag) {
+    const uint lane = threadIdx.x & 63u;
+    const uint wavesPerBlock = T8_BLOCK / 64u;
+    const uint waveId = t8k_uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), numWaves = t8k_uniform(gridDim.x * wavesPerBlock);
+    uint2* stack = stackBase + t8k_uniform(threadIdx.x >> 6) * T8_PACKET_STACK;
+    const char* nodesBase = reinterpret_cast<const char*>(sc.nodes8);
+    const char* trisBase = reinterpret_cast<const char*>(sc.tris);
+    const uint INF_BITS = 0x7F800000u;
+    const float tmin = 0.f, tmax = kMaxRayTravel;
+    // lane k < 8 fetches child k's reference (a child is twelve bytes from byte 16 of the node: reference, six plane bytes, two spare); v_readlane picks one by child index
+    const uint refOff = 16u + 12u * (lane & 7u);
+    const uint stepCap = t8k_uniform(pk.stepCap), stackBound = t8k_uniform(pk.stackBound < T8_PACKET_STACK ? pk.stackBound : T8_PACKET_STACK);
+    const uint numPackets = (count + T8_PACKET64_RAYS - 1u) / T8_PACKET64_RAYS;
+
+    for (uint p = waveId; p < numPackets; p += numWaves) {
+        const uint i0 = p * T8_PACKET64_RAYS, i = i0 + lane;
+        const bool valid = i < count;      // (the launch's last packet may be short: its idle lanes form the last ray and enter nothing)
+        float3 o; float Sx, Sy, ix, iy, iz; uint axes, selN, selF;
+        {   float3 rd; form(valid ? i : count - 1u, o, rd); t8_ray_frame(rd, ix, iy, iz, Sx, Sy, axes); t8_slab_selectors(ix, iy, iz, selN, selF); }
+        // (an idle lane's best t is negative: its slab intervals are empty, it enters nothing, and no triangle is tested for it)
+        float bestT = valid ? tmax : -1.0f, bestU = 0.f, bestV = 0.f; uint bestPrim = 0xFFFFFFFFu;
+        // wave-uniform: the node in hand, the stack pointer, the steps so far, the largest best t of the packet (as bits: t > 0)
+        uint cur = sc.rootIsValid ? 0u : BVH_EMPTY, sp = 0u, steps = 0u, maxBest = __float_as_uint(tmax);
+        bool handOff = false;
+
+        for (;;) {
+            if (cur == BVH_EMPTY) {
+                while (sp > 0u) {
+                    sp--;
+                    const uint2 e = stack[sp];
+                    const uint er = t8k_uniform(e.x), et = t8k_uniform(e.y);
+                    if (et <= maxBest && er != BVH_EMPTY) { cur = er; break; }      // (both are the bits of floats >= +0: they order like the values; an empty slot's reference is skipped)
+                }
+                if (cur == BVH_EMPTY) break;
+            }
+            if (++steps > stepCap) { handOff = true; break; }
+            cur = t8k_uniform(cur);      // (wave-uniform by construction; said once per step, so that the node's address and the leaf's slot are formed in scalar registers)
+
+            if (!(cur & BVH_LEAF_BIT)) {
+                // ---- inner node: every lane tests all eight children for its ray
+                const uint nodeOff = cur * 128u;
+                const uint vref = *reinterpret_cast<const uint*>(nodesBase + nodeOff + refOff);
+                const T8kNodeHalf np = (T8kNodeHalf)(unsigned long long)(nodesBase + nodeOff);
+                const u32x16 w0 = np[0], w1 = np[1];
+                // (the node's origin in vector registers, once: as scalars each of the eight slab tests copies the three pairs again)
+                float nx = __uint_as_float(w0[0]), ny = __uint_as_float(w0[1]), nz = __uint_as_float(w0[2]);
+                asm volatile("" : "+v"(nx), "+v"(ny), "+v"(nz));
+                const float sx = __uint_as_float(w1[12]), sy = __uint_as_float(w1[13]), sz = __uint_as_float(w1[14]);
+                // child k's plane bytes: words 5 + 3k and 6 + 3k of the node
+                const uint q0[8] = {w0[5], w0[8], w0[11], w0[14], w1[1], w1[4], w1[7], w1[10]};
+                const uint q1[8] = {w0[6], w0[9], w0[12], w0[15], w1[2], w1[5], w1[8], w1[11]};
+                const uint ref[8] = {w0[4], w0[7], w0[10], w0[13], w1[0], w1[3], w1[6], w1[9]};
+                // a child's key: the minimum over the rays that enter it of the entry distance (tn >= 0: the bits order like the value; the sign is cleared with the index
+                // bits, so a -0 is a 0), then the child index in the low bits (unique keys, ties to the lower child); +inf for a child that nothing enters
+                uint sk[8]; uint nhit = 0u;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    float tn, tf;
+                    t8_slab(q0[k], q1[k], selN, selF, nx, ny, nz, sx, sy, sz, o.x, o.y, o.z, ix, iy, iz, tmin, bestT, tn, tf);
+                    const bool hit = T8_HIT(ref[k], tn, tf);      // (an empty slot is an inverted box, which nothing enters: pt_traverse8.h T8_EMPTY_SLOT_CHECK)
+                    uint mk = INF_BITS;
+                    if (t8_ballot(hit) != 0ull) { mk = t8k_wave_min(hit ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS); nhit++; }
+                    sk[k] = mk | (uint)k;
+                }
+                uint next = BVH_EMPTY;
+                if (nhit == 1u) {
+                    const uint m = t8k_min(t8k_min(t8k_min(sk[0], sk[1]), t8k_min(sk[2], sk[3])), t8k_min(t8k_min(sk[4], sk[5]), t8k_min(sk[6], sk[7])));
+                    next = (uint)__builtin_amdgcn_readlane((int)vref, (int)(m & 7u));
+                } else if (nhit > 1u) {
+                    if (sp + nhit - 1u > stackBound) { handOff = true; break; }
+                    t8k_sort8(sk);
+                    next = (uint)__builtin_amdgcn_readlane((int)vref, (int)(sk[0] & 7u));
+                    // far to near: nearest on top. One lane writes; the entries are wave-uniform
+#pragma unroll
+                    for (int r = 1; r < 8; r++) {
+                        if ((uint)r < nhit) { const uint ref = (uint)__builtin_amdgcn_readlane((int)vref, (int)(sk[r] & 7u)); if (lane == 0u) stack[sp + (nhit - 1u - (uint)r)] = make_uint2(ref, sk[r] & ~7u); }
+                    }
+                    sp += nhit - 1u;
+                }
+                cur = next;      // (a reference of BVH_EMPTY — a node of zero extent "entering" an empty slot — pops; the pop loop skips such an entry)
+            } else {
+                // ---- leaf: every ray of the packet tests both triangles — the shared leaf block (pt_traverse8.h t8_leaf_block), once as each lane of a pair
+                bool cand = false;
+#pragma unroll 1
+                for (uint h = 0; h < 2u; h++) {
+                    const T8LeafHit lh = t8_leaf_block<false, false>(sc, trisBase, cur, h, valid, o.x, o.y, o.z, ix, iy, iz, Sx, Sy, axes, tmin, tmax, bestT, bestPrim, nullptr);
+                    if (lh.prim != 0xFFFFFFFFu) { bestT = lh.t; bestPrim = lh.prim; bestU = lh.u; bestV = lh.v; cand = true; }
+                }
+                if (t8_ballot(cand) != 0ull) maxBest = t8k_wave_max(valid ? __float_as_uint(bestT) : 0u);
+                cur = BVH_EMPTY;
+            }
+        }
+
+        if (handOff) {
+            // nothing is committed: the packet's rays are traced again, one by one
+            const uint n = (count - i0 < T8_PACKET64_RAYS) ? count - i0 : T8_PACKET64_RAYS;
+            uint base = 0u;
+            if (lane == 0u) base = atomicAdd(pk.leftoverCount, n);
+            base = t8k_uniform(base);
+            if (base + n <= pk.capacity) { if (valid) pk.leftover[base + lane] = i; }
+            else if (lane == 0u) atomicOr(overflowFlag, 2u);
+        } else if (valid) {
+            HitInfo hh; hh.t = bestT; hh.prim = bestPrim; hh.u = bestU; hh.v = bestV; commit(i, hh);
         }
     }
 }

@@ -57,7 +57,7 @@ void launch_generate(const PathKernelContext& k, PathPool pool, const uint* owne
 void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged = false);      // ranged: the rays' intervals wait in pool.hit[p].xy (k_extend)
 // launch_extend for the first pass of a batch whose paths were NOT generated: ray i is the camera ray of path i of `fv` (no queue, no read of pool.s0 / s1). The rays that are cut into
 // sub-trees get their origin | id and direction | length written to pool.s0 / s1 [i] by a launch over the resolve list (k_first_split_rays), for the task rounds and the resolve pass behind it. The camera: wc->firstCamera. Composed frames only (no counters).
-// pk.leftover != null: the rays are traced as 32-ray packets on one shared stack per wave (k_extend_first_packets, pt_traverse8k.h); the packets that exceed pk.stepCap steps or
+// pk.leftover != null: the rays are traced as packets on one shared stack per wave (pt_traverse8k.h: k_extend_first_packets64, 64 rays, or k_extend_first_packets, 32); the packets that exceed pk.stepCap steps or
 // pk.stackBound stack entries leave their rays on pk.leftover (count: *pk.leftoverCount, zero on entry; capacity >= count), which the per-ray kernel traces behind them. Same hits.
 #ifndef T8_PACKET_STACK
 #define T8_PACKET_STACK 64        // entries of a wave's stack in LDS (a node pushes at most seven)
@@ -65,8 +65,12 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
 #ifndef T8_PACKET_STEP_CAP
 #define T8_PACKET_STEP_CAP 128    // node + leaf steps after which a packet is handed to the per-ray kernel (environment MI355PT_PACKET_STEP_CAP overrides)
 #endif
-static const uint T8_PACKET_RAYS = 32;
-struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound; };
+#ifndef T8_PACKET64_STEP_CAP
+#define T8_PACKET64_STEP_CAP 192  // the same for the 64-ray packets, which take a few more steps: the first launch of a 4K step alone on the GPU 7.05 / 6.68 / 6.71 ms at 128 / 192 / 256 (profiles/r21a_packet64_ab.txt)
+#endif
+static const uint T8_PACKET_RAYS = 32, T8_PACKET64_RAYS = 64;
+// wide != 0: 64-ray packets, one lane per ray (k_extend_first_packets64, traverse8_packets64); 0: the 32-ray pair packets
+struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound, wide; };
 void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, FirstPackets pk, hipStream_t st);
 // classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (4 words, zero on entry: three classes and the dropped hits): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)
