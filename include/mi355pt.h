@@ -317,6 +317,21 @@ int32_t pt_get_light_feedback(pt_context* ctx, uint32_t sample, float* totalWeig
  * is built as for type 1). preFilter: LightsBaker.h:251 m_importanceBoost_PreFilter (default on). The frustum importance boost (LightsBaker.h:247-249) is not applied.
  * pt_get_light_feedback(0, ...) returns the run's reservoirs after the last frame; pt_get_neeat_tables the tile tables and jitter that frame was traced with. */
 int32_t pt_set_neeat(pt_context* ctx, int32_t enable, float globalTemporalFeedbackWeight, float localToGlobalSampleRatio, float screenSpaceVsWorldSpaceThreshold, int32_t preFilter);
+/* Stochastic texture filtering (RTXPT_STOCHASTIC_TEXTURE_FILTERING_ENABLE; STFFilterMode, STFMagnificationMethod, STFGaussianSigma of PathTracerConstants, PathTracerShared.h:88-90):
+ * while enabled, every material lookup of Bridge::loadSurface — pt_render's shading and tail kernels, the stable-plane build and fill passes and with them pt_realtime_frame —
+ * fetches ONE stored texel, chosen at random so that its expectation is the filtered value, instead of the eight texels of the trilinear filter. The random numbers are the
+ * reference's (PathTracerBridgeDonut.hlsli:648-650: keyed by pixel, path vertex and sample index; one draw per loadSurface call, shared by its lookups — equal-sized textures
+ * of one material read the same texel position); the sampler is the project's own (rtxpt_amd/csrc/pt_stf.h states it; the reference's library is not in its tree):
+ *   PT_STF_FILTER_POINT   the nearest level, the texel that holds the coordinate; no random numbers
+ *   PT_STF_FILTER_LINEAR  expectation = the trilinear value
+ *   PT_STF_FILTER_CUBIC   expectation = the cubic B-spline convolution of the two levels, blended by the level's fraction
+ * PT_STF_FILTER_GAUSSIAN and every magnification method but 0 (Default) are PT_ERROR_UNSUPPORTED; a null pointer, enable > 1, a filter above 3 or a magnification method above 3
+ * PT_ERROR_INVALID_ARGUMENT. The traversal's alpha test, the emissive-triangle bake, the environment cube and the sky stay deterministic. Off by default: frames are then what
+ * they were. Context state like pt_set_neeat; independent of pt_set_settings. A change resets the accumulation (pt_reset_accumulation). */
+enum { PT_STF_FILTER_POINT = 0, PT_STF_FILTER_LINEAR = 1, PT_STF_FILTER_CUBIC = 2, PT_STF_FILTER_GAUSSIAN = 3 };
+typedef struct PtTextureFiltering { uint32_t enable, filter, magnification; float gaussianSigma; } PtTextureFiltering;
+int32_t pt_texture_filtering_default_params(PtTextureFiltering* p);   /* enable 0, LINEAR, 0, 0.3f — SampleUI.h:185-187 */
+int32_t pt_set_texture_filtering(pt_context* ctx, const PtTextureFiltering* p);
 /* PlanarViewConstants::matWorldToClip of the frame (Donut; row vectors: clip = p * M, 16 floats row-major) — what Bridge::ExportSurface / ExportNonSurface project the path's last
  * vertex with when the reference-mode path tracer "dumps guide buffers" (PathTracer.hlsli:487, 684; PathTracerBridgeDonut.hlsli:1105-1140). Of those buffers this path keeps the depth,
  * because NEE-AT's Reproject (LightsBaker.hlsl:1348-1375; motion vectors are zero in reference mode) tests it: a pixel whose last two frames exported depths more than 1.5 x apart counts

@@ -11,13 +11,18 @@ extern "C" {
  * (tests/golden/refpin_hlsl_golden.npz) or of the oracle. kind (rtxpt_amd/csrc/pt_wavefront.hip k_probe): 0 deterministic math (fn, x, y); 1 binary16 round trip;
  * 2 sample streams (pixel, vertex, sample, seed, generator, count); 3 whole-BSDF eval / sample / pdf; 4 camera rays; 5 leaf functions pinned to the reference text
  * (Fresnel, microfacet, octahedral maps, disk / hemisphere sampling, ComputeRayOrigin, firefly filter ...); 6 polymorphic lights; 7 the half-typed operators of the lp16 build;
- * 8 Bridge::loadSurface (45 words per hit); 9 EnvMap::EvalLocal on the baked cube; 10 the traversal's alpha test; 11 the texture samplers. `n` rows in, `n` rows out; the row
+ * 8 Bridge::loadSurface (45 words per hit); 9 EnvMap::EvalLocal on the baked cube; 10 the traversal's alpha test; 11 the texture samplers; 12 stochastic texture filtering. `n` rows in, `n` rows out; the row
  * layouts are the probe's.
  * Kind 11, eight 32-bit words in, one float4 out: word 0 the mode, word 1 the texture, words 2-3 uv (floats), words 4-7 by mode —
  *   mode 0  PathKernelContext::sampleTexture: word 1 = the packed texture word of a material (baseLOD << 24 | mipLevels << 16 | index), word 4 = lambdaNoDims (float)
  *   mode 1  sample_bilinear at one level:     word 1 = the texture index, word 4 = the mip (integer, below the texture's mipLevels)
  *   mode 2  sample_grad_anisotropic:          word 1 = the texture index, words 4-5 = gx, words 6-7 = gy (floats)
- * pt_probe refuses rows whose mode, texture or mip the scene does not have. uv, lambda and the gradients must be finite: the samplers' data contract. */
+ * pt_probe refuses rows whose mode, texture or mip the scene does not have. uv, lambda and the gradients must be finite: the samplers' data contract.
+ * Kind 12, stochastic texture filtering (rtxpt_amd/csrc/pt_stf.h), twelve words in, eight words out: word 0 the mode, word 1 the packed texture word of a material, words 2-3 uv,
+ * word 4 lambdaNoDims, word 5 the filter (PT_STF_FILTER_POINT / LINEAR / CUBIC), words 6-9 by mode, words 10-11 unused —
+ *   mode 0  one lookup with the four random numbers of words 6-9 (floats in [0, 1)): words 0-3 out = the texel, words 4-6 = the level, x and y it was taken from, word 7 = 0
+ *   mode 1  words 6-8 = packed pixel (x << 16 | y), path vertex index, sample index: words 0-3 out = the four numbers Bridge::loadSurface draws for that call, words 4-7 = 0
+ * pt_probe refuses rows whose mode, texture (mode 0) or filter (mode 0) the scene or the library does not have. */
 int32_t pt_probe(pt_context* ctx, int32_t kind, const void* in, size_t inBytes, void* out, size_t outBytes, uint32_t n);
 /* The "inert when terminal" table of the prepared scene (rtxpt_amd/csrc/pt_scene.h inert_bits_of; built on the device by k_inert_bits) and what the last pt_render call did with
  * it. Two bits per global primitive, sixteen primitives a word, primitive p in bits 2 (p % 16) and 2 (p % 16) + 1 of word p / 16: bit 0 = the material can neither emit (all three

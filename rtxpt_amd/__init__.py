@@ -28,7 +28,7 @@ STATUS = {0: "PT_OK", 1: "PT_ERROR_INVALID_ARGUMENT", 2: "PT_ERROR_NO_DEVICE", 3
 # every symbol include/mi355pt.h declares
 EXPORTS = [
     "pt_create", "pt_destroy", "pt_get_last_error", "pt_load_scene_gltf", "pt_gltf_animation_load", "pt_gltf_animation_instances", "pt_gltf_animation_positions", "pt_gltf_animation_normals", "pt_gltf_animation_skinning", "pt_gltf_animation_palette", "pt_set_skinning", "pt_animate_skinned", "pt_get_skinning_time", "pt_get_vertex_streams", "pt_animate_normals", "pt_gltf_animation_free", "pt_set_geometry", "pt_set_instances", "pt_set_materials",
-    "pt_set_environment", "pt_set_environment_cube", "pt_image_read_dds_cube", "pt_set_environment_bake", "pt_set_environment_compression", "pt_set_procedural_sky", "pt_procedural_sky_default_params", "pt_procedural_sky_update", "pt_env_bake_lights", "pt_set_lights", "pt_set_light_importance_boost", "pt_set_local_light_sampling", "pt_get_light_feedback", "pt_set_neeat", "pt_set_view_projection", "pt_neeat_reset", "pt_get_neeat_tables", "pt_neeat_pack_feedback", "pt_neeat_unpack_feedback", "pt_bridge_camera", "pt_set_camera", "pt_default_settings", "pt_set_settings", "pt_animate",
+    "pt_set_environment", "pt_set_environment_cube", "pt_image_read_dds_cube", "pt_set_environment_bake", "pt_set_environment_compression", "pt_set_procedural_sky", "pt_procedural_sky_default_params", "pt_procedural_sky_update", "pt_env_bake_lights", "pt_set_lights", "pt_set_light_importance_boost", "pt_set_local_light_sampling", "pt_get_light_feedback", "pt_set_neeat", "pt_texture_filtering_default_params", "pt_set_texture_filtering", "pt_set_view_projection", "pt_neeat_reset", "pt_get_neeat_tables", "pt_neeat_pack_feedback", "pt_neeat_unpack_feedback", "pt_bridge_camera", "pt_set_camera", "pt_default_settings", "pt_set_settings", "pt_animate",
     "pt_resize", "pt_render", "pt_reset_accumulation", "pt_map_radiance", "pt_unmap_radiance", "pt_shard_info", "pt_pack_shard",
     "pt_unpack_shard", "pt_device_radiance", "pt_trace_closest", "pt_trace_visibility", "pt_get_lights", "pt_get_env_cube", "pt_get_subinstances",
     "pt_get_scene_info", "pt_get_build_stats", "pt_get_bvh_info", "pt_set_counters",
@@ -123,6 +123,22 @@ def procedural_sky_update(state, scene_time, preset="==PROCEDURAL_SKY==", params
 
 class PtDeviceDesc(ctypes.Structure):
     _fields_ = [("deviceOrdinal", ctypes.c_int32), ("shardRank", ctypes.c_uint32), ("shardCount", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+PT_STF_FILTER_POINT, PT_STF_FILTER_LINEAR, PT_STF_FILTER_CUBIC, PT_STF_FILTER_GAUSSIAN = 0, 1, 2, 3
+
+
+class PtTextureFiltering(ctypes.Structure):      # include/mi355pt.h
+    _fields_ = [("enable", ctypes.c_uint32), ("filter", ctypes.c_uint32), ("magnification", ctypes.c_uint32), ("gaussianSigma", ctypes.c_float)]
+
+
+def texture_filtering_default_params():
+    """pt_texture_filtering_default_params: (enable, filter, magnification, gaussianSigma) = (0, LINEAR, 0, 0.3)."""
+    p = PtTextureFiltering(); L = load_library()
+    f = L.pt_texture_filtering_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(ctypes.byref(p))
+    if r != PT_OK: raise PtError(r, "pt_texture_filtering_default_params")
+    return p.enable, p.filter, p.magnification, p.gaussianSigma
 
 
 class PtTextureIngestStats(ctypes.Structure):      # pt_get_texture_ingest_stats
@@ -1270,6 +1286,12 @@ class PathTracer:
         f = self.L.pt_denoise_pass_times; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
         self._chk(f(self.h, 1 if enable else 0, _p(ms), 16, ctypes.byref(n)), "pt_denoise_pass_times")
         return ms[:n.value].copy()
+
+    def set_texture_filtering(self, enable, filter=1, magnification=0, gaussian_sigma=0.3):
+        """pt_set_texture_filtering: stochastic texture filtering — one texel per material lookup (filter: PT_STF_FILTER_POINT / LINEAR / CUBIC). Off by default."""
+        p = PtTextureFiltering(1 if enable is True else int(enable), int(filter), int(magnification), float(gaussian_sigma))
+        f = self.L.pt_set_texture_filtering; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(p)), "pt_set_texture_filtering")
 
     def set_neeat(self, enable=True, global_feedback_weight=0.75, ratio=0.65, ssc_threshold=0.3, prefilter=True):
         """NEE-AT with the light baker in the loop (pt_set_neeat): every sample of render() becomes a frame — feedback passes, then the path tracer"""

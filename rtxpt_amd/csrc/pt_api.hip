@@ -1015,6 +1015,25 @@ int32_t pt_set_settings(pt_context* c, const ::PtSettings* s) {
     if (s->nestedDielectricsQuality > 2 || (s->diffuseBrdf != 0 && s->diffuseBrdf != 2) || s->bounceCount > 96 || s->useFp16Types > 1) return fail(c, PT_ERROR_INVALID_ARGUMENT, "setting out of range");
     if (c->S.NEEEnabled != s->NEEEnabled || c->S.NEEType != s->NEEType) c->lightsDirty = true;
     memcpy(&c->S, s, sizeof(c->S));
+    ptk::stf_set_launch_filter(c->S, c->stf.enable != 0u, c->stf.filter);      // the pad word is the library's: the texture filter of the launches (pt_set_texture_filtering), whatever the caller left in it
+    return PT_OK;
+}
+// RTXPT_STOCHASTIC_TEXTURE_FILTERING_ENABLE and the three STF settings of PathTracerConstants (PathTracerShared.h:88-90; defaults SampleUI.h:185-187)
+int32_t pt_texture_filtering_default_params(PtTextureFiltering* p) {
+    if (!p) return PT_ERROR_INVALID_ARGUMENT;
+    p->enable = 0u; p->filter = PT_STF_FILTER_LINEAR; p->magnification = 0u; p->gaussianSigma = 0.3f;
+    return PT_OK;
+}
+int32_t pt_set_texture_filtering(pt_context* c, const PtTextureFiltering* p) {
+    if (!c || !p) return fail(c, PT_ERROR_INVALID_ARGUMENT, "null argument");
+    if (p->enable > 1u || p->filter > PT_STF_FILTER_GAUSSIAN || p->magnification > 3u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture filtering: enable 0 / 1, filter 0 .. 3 (PT_STF_FILTER_*), magnification 0 .. 3");
+    if (p->filter == PT_STF_FILTER_GAUSSIAN) return fail(c, PT_ERROR_UNSUPPORTED, "texture filtering: the Gaussian filter is not built (rtxpt_amd/csrc/pt_stf.h)");
+    if (p->magnification != 0u) return fail(c, PT_ERROR_UNSUPPORTED, "texture filtering: only the Default magnification method (0) is built");
+    (void)hipSetDevice(c->device);
+    const bool changed = c->stf.enable != p->enable || (p->enable && c->stf.filter != p->filter);
+    c->stf.enable = p->enable; c->stf.filter = p->filter; c->stf.magnification = p->magnification; c->stf.gaussianSigma = p->gaussianSigma;
+    ptk::stf_set_launch_filter(c->S, c->stf.enable != 0u, c->stf.filter);
+    if (changed && c->width) return pt_reset_accumulation(c);      // another estimator: what was accumulated is not its average
     return PT_OK;
 }
 int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
@@ -1747,7 +1766,13 @@ int32_t pt_probe(pt_context* c, int32_t kind, const void* in, size_t inBytes, vo
     if (!c || !in || !out || !n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
     (void)hipSetDevice(c->device);
     // the surface, environment and alpha-test probes read the scene
-    if (kind == 8 || kind == 9 || kind == 10 || kind == 11) { int r = prepare(c); if (r != PT_OK) return r; }
+    if (kind == 8 || kind == 9 || kind == 10 || kind == 11 || kind == 12) { int r = prepare(c); if (r != PT_OK) return r; }
+    if (kind == 12) {      // the stochastic-filter probe indexes the texture table with what its rows say, and knows three filters
+        if (inBytes < (size_t)n * 48u || outBytes < (size_t)n * 32u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "stochastic texture probe: 12 words in and 8 words out per row");
+        const uint32_t* a = (const uint32_t*)in;
+        for (uint32_t i = 0; i < n; i++, a += 12)
+            if (a[0] > 1u || (a[0] == 0u && ((a[1] & 0xFFFFu) >= c->textures.size() || a[5] > PT_STF_FILTER_CUBIC))) return fail(c, PT_ERROR_INVALID_ARGUMENT, "stochastic texture probe: mode, texture or filter out of range");
+    }
     if (kind == 11) {      // the texture probe indexes the texture table and a texture's mip offsets with what its rows say: hold both to the scene here, the kernel does not
         if (inBytes < (size_t)n * 32u || outBytes < (size_t)n * 16u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture probe: 8 words in and 4 floats out per row");
         const uint32_t* a = (const uint32_t*)in;

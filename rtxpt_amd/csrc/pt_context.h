@@ -124,6 +124,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     int device = 0; hipStream_t stream = nullptr; uint shardRank = 0, shardCount = 1;
     // streams / hostCounters: one stream and one pinned counter block per pipelined batch (pt_render, pt_fill_stable_planes)
     hipStream_t streams[PT_PIPELINE_BATCHES] = {}; WaveCounters* hostCounters = nullptr; bool serialKernels = false;
+    struct { uint enable = 0u, filter = 1u, magnification = 0u; float gaussianSigma = 0.3f; } stf;      // pt_set_texture_filtering (defaults: SampleUI.h:185-187); S._pad carries enable + filter to the launchers (pt_path.h stf_set_launch_filter)
     uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool occlusionSlotOrder = true, compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
     // vertex 0 as packets (ptk::FirstPackets): the switch (0 / 1 / 2, as above), the step cap and stack bound of a packet (0: T8_PACKET_STEP_CAP or T8_PACKET64_STEP_CAP / T8_PACKET_STACK), the leftover list (one word per path)
     uint firstVertexPackets = PT_FIRST_VERTEX_PACKETS; uint packetStepCap = 0, packetStack = 0; DevBuf<uint> dFirstLeftover;

@@ -14,6 +14,7 @@
 #include "pt_bsdf.h"
 #include "pt_rng.h"
 #include "pt_scene.h"
+#include "pt_stf.h"
 
 #ifndef PT_SHADE_TRI
 // 1: loadSurface reads the flat 128-byte ShadeTri record of the hit primitive; 0: the five-hop gather through primInfo / sub-instance / geometry / index /
@@ -41,6 +42,11 @@ struct PtSettings {
     uint NEEEnabled, NEEType, NEECandidateSamples, NEEFullSamples, enableRussianRoulette, nestedDielectricsQuality, enableLDSamplerForBSDF, diffuseBrdf, useFp16Types, _pad;      // useFp16Types: lp types in 16 bits (the reference's default build)
 };
 static_assert(sizeof(PtSettings) == 64, "PtSettings layout");
+// The stochastic texture filter of a launch (pt_set_texture_filtering, pt_stf.h) travels in the pad word of the kernel context's copy of the settings: 0 = off, 1 + filter
+// otherwise. No kernel reads it — the filter is a compile-time parameter of the context — the launchers pick the instantiation by it (dispatch_stf). The public
+// PtSettings is untouched: the frame drivers write the word when they form a context (pt_frame.hip kernel_context).
+static inline void stf_set_launch_filter(PtSettings& S, bool enable, uint filter) { S._pad = enable ? 1u + filter : 0u; }
+static inline int stf_launch_filter(const PtSettings& S) { return (int)S._pad - 1; }
 
 // TexLODHelpers.hlsli:57-123
 struct RayCone {
@@ -223,7 +229,9 @@ static inline float TriangleCurvatureApprox_GradN(const float3 vertexPositions[3
 struct MVBlockInputs { float curvatureWS, projectionTerm; };
 
 // LP16: which build of the reference's lp types this instance restates (PtSettings::useFp16Types selects it at launch; the data members are the same)
-template <bool LP16> struct PathKernelContextT {
+// STF: the material lookups' filter — STF_OFF: sample_trilinear, as ever; STF_POINT / STF_LINEAR / STF_CUBIC: one texel per lookup (pt_stf.h). The deterministic contexts
+// keep their type names (PathKernelContextT<LP16>, below), so the kernels instantiated over them keep theirs.
+template <bool LP16, int STF> struct PathKernelContextStfT {
     typedef LPOps<LP16> LP;
     DeviceScene sc; PtSettings S; PathTracerCameraData cam;
 
@@ -285,6 +293,13 @@ template <bool LP16> struct PathKernelContextT {
         lambda = fminf_(lambda, fmaxf_((float)mipLevels - 5.0f, 0.0f));
         return sample_trilinear(sc, sc.textures[textureIndex], uv, lambda);
     }
+    // the same lookup through the stochastic filter: lambda as above, unchanged; u = the loadSurface call's four numbers (stf_draw), shared by its lookups
+    PT_SHADE_NOINLINE float4 sampleTextureStochastic(uint textureIndexAndInfo, float lambdaNoDims, float2 uv, float4 u) const {
+        uint textureIndex = textureIndexAndInfo & 0xFFFFu, baseLOD = textureIndexAndInfo >> 24, mipLevels = (textureIndexAndInfo >> 16) & 0xFFu;
+        float lambda = 0.5f * (float)baseLOD + lambdaNoDims;
+        lambda = fminf_(lambda, fmaxf_((float)mipLevels - 5.0f, 0.0f));
+        return sample_stochastic<STF == STF_OFF ? STF_LINEAR : STF>(sc, sc.textures[textureIndex], uv, lambda, u);
+    }
     static void computeTangentSpace(ShadingData& sd, float4 tangentW, bool ignoreTangent) {     // ShadingUtils.hlsli:110-139
         float3 t3 = xyz(tangentW);
         float NdotT = dot(t3, sd.N);
@@ -328,8 +343,17 @@ template <bool LP16> struct PathKernelContextT {
     // touches before it returns — position, flat normal and facing, material header, emission (with its texture), the two light links, the interior IoR — so
     // the vertex normals and tangents, the base / normal / metal-rough / transmission fetches, the normal map, the tangent frame and the BSDF inputs are not
     // formed at all. What IS formed is formed by the same expressions: the values HandleHit reads are the same floats.
-    template <bool LEAN = false>
-    SurfaceData loadSurface(uint prim, float bu, float bv, float3 rayDir, RayCone rayCone, MVBlockInputs* mvBlock = nullptr) const {
+    // what loadSurface takes as its last argument for a path whose vertex index is `vertexAhead` behind the reference's at its loadSurface call
+    auto stfKeyOf(const PathState& path, uint vertexAhead) const {
+        if constexpr (STF == STF_OFF) return StfNoKey();
+        else return StfKey{path.id, path.getVertexIndex() + vertexAhead, path.sampleIndex};
+    }
+    // KEY (a context with a stochastic filter: StfKey, otherwise nothing): pixel, vertex index as the reference passes it to Bridge::loadSurface (after UpdatePathTravelled's
+    // increment: PathTracer.hlsli:395, 515) and sample index of the call's random numbers (BridgeDonut:648-650). ONE draw per call, shared by its up to five lookups — the
+    // reference builds one STF_SamplerState per loadSurface, and what its library does between lookups is not in its tree; the project's choice: equal-sized textures of a
+    // material read the same texel position. The traversal's alpha test, the emissive bake's anisotropic sampler, the environment cube and the sky look-ups stay deterministic.
+    template <bool LEAN = false, class KEY = StfNoKey>
+    SurfaceData loadSurface(uint prim, float bu, float bv, float3 rayDir, RayCone rayCone, MVBlockInputs* mvBlock = nullptr, KEY stfKey = KEY()) const {
 #if PT_SHADE_TRI
         // one 128-byte line per primitive (pt_scene.h ShadeTri) instead of primInfo -> subInstToInstGeom -> {instance, subInstance, geometry} -> indices ->
         // vertex streams
@@ -418,11 +442,23 @@ template <bool LP16> struct PathKernelContextT {
         float4 texBase = make_float4(1, 1, 1, 1), texEmissive = make_float4(1, 1, 1, 1), texNormal = make_float4(0.5f, 0.5f, 1.0f, 0.f),
                texMR = make_float4(1, 1, 1, 1), texTrans = make_float4(1, 1, 1, 1);
         bool hasUV = (g.flags & GEOM_HAS_UV) != 0;
+        if constexpr (STF == STF_OFF) {
         if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseBaseOrDiffuseTexture)) texBase = sampleTexture(material.BaseOrDiffuseTextureIndex, lambda, texcoord);
         if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseNormalTexture)) texNormal = sampleTexture(material.NormalTextureIndex, lambda, texcoord);
         if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseMetalRoughOrSpecularTexture)) texMR = sampleTexture(material.MetalRoughOrSpecularTextureIndex, lambda, texcoord);
         if (hasUV && (mflags & PTMaterialFlags_UseEmissiveTexture)) texEmissive = sampleTexture(material.EmissiveTextureIndex, lambda, texcoord);
         if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseTransmissionTexture)) texTrans = sampleTexture(material.TransmissionTextureIndex, lambda, texcoord);
+        } else {
+        static_assert(STF == STF_OFF || sizeof(KEY) == sizeof(StfKey), "a context with a stochastic filter needs the key of the call's random numbers");
+        const uint texFlags = PTMaterialFlags_UseEmissiveTexture | (LEAN ? 0u : (PTMaterialFlags_UseBaseOrDiffuseTexture | PTMaterialFlags_UseNormalTexture | PTMaterialFlags_UseMetalRoughOrSpecularTexture | PTMaterialFlags_UseTransmissionTexture));
+        float4 u = make_float4(0, 0, 0, 0);
+        if (hasUV && (mflags & texFlags)) u = stf_draw(stfKey.pixel, stfKey.vertex, stfKey.sample);
+        if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseBaseOrDiffuseTexture)) texBase = sampleTextureStochastic(material.BaseOrDiffuseTextureIndex, lambda, texcoord, u);
+        if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseNormalTexture)) texNormal = sampleTextureStochastic(material.NormalTextureIndex, lambda, texcoord, u);
+        if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseMetalRoughOrSpecularTexture)) texMR = sampleTextureStochastic(material.MetalRoughOrSpecularTextureIndex, lambda, texcoord, u);
+        if (hasUV && (mflags & PTMaterialFlags_UseEmissiveTexture)) texEmissive = sampleTextureStochastic(material.EmissiveTextureIndex, lambda, texcoord, u);
+        if (!LEAN && hasUV && (mflags & PTMaterialFlags_UseTransmissionTexture)) texTrans = sampleTextureStochastic(material.TransmissionTextureIndex, lambda, texcoord, u);
+        }
 
         float3 emissiveColor = LP::r3(material.EmissiveColor);
         if (mflags & PTMaterialFlags_UseEmissiveTexture) emissiveColor = LP::mul3(emissiveColor, LP::r3(xyz(texEmissive)));
@@ -711,7 +747,8 @@ template <bool LP16> struct PathKernelContextT {
     // vertex's register peak, which then carries 5 words of the path instead of 21 — and
     // (iii) stores the last group ({firefly K | pdf, MIS info | roulette correction, flags | vertex index, sample index}) at the end. Same values either way:
     //       order of loads and stores only.
-    struct PathInRegisters { static constexpr bool streams = false; void mark(int) const {} void load_rest(PathState&) const {} void store_front(const PathState&) const {} void store_back(const PathState&) const {} void store_all(const PathState&) const {} };
+    // load_key (contexts with a stochastic filter only): the pixel id and the sample index, which key loadSurface's random numbers, before the surface is loaded.
+    struct PathInRegisters { static constexpr bool streams = false; void mark(int) const {} void load_key(PathState&) const {} void load_rest(PathState&) const {} void store_front(const PathState&) const {} void store_back(const PathState&) const {} void store_all(const PathState&) const {} };
     // PathTracer.hlsli:505-762 (reference mode), shadow test deferred through `req` (a split of this vertex at NEE — a light-sample kernel and a scatter kernel
     // — was built and measured in round 4: 21.5 -> 27.5 ms, profiles/r04p_shade_split_ab.txt; history: af4c2b2)
     template <bool MULTI, bool NEEAT, class IO = PathInRegisters>
@@ -722,7 +759,9 @@ template <bool LP16> struct PathKernelContextT {
         path.rayCone = path.rayCone.propagateDistance(hit.t); path.sceneLength = fminf_(path.sceneLength + hit.t, kMaxRayTravel);
         // a vertex that ends right after its emission term needs a fraction of the surface (loadSurface<LEAN>); the flag is in the word group the IO loads
         // first
-        SurfaceData sfd = path.isTerminatingAtNextBounce() ? loadSurface<true>(hit.prim, hit.u, hit.v, rayDir, path.rayCone) : loadSurface<false>(hit.prim, hit.u, hit.v, rayDir, path.rayCone);
+        if constexpr (STF != STF_OFF) io.load_key(path);
+        const auto stfKey = stfKeyOf(path, 1u);      // (the vertex index the reference passes: incremented before its loadSurface, after ours)
+        SurfaceData sfd = path.isTerminatingAtNextBounce() ? loadSurface<true>(hit.prim, hit.u, hit.v, rayDir, path.rayCone, nullptr, stfKey) : loadSurface<false>(hit.prim, hit.u, hit.v, rayDir, path.rayCone, nullptr, stfKey);
         io.mark(1);
         io.load_rest(path);
         // ... and the third, once the flags word is there
@@ -805,7 +844,19 @@ template <bool LP16> struct PathKernelContextT {
     }
     static void ResolveShadow(uint pack45[2], float3 radiance) { uint nee[2] = {0u, 0u}; NeeAccumulate(nee, radiance); NeeCommit(pack45, nee); }
 };
+// the deterministic contexts: what every launch without a stochastic filter runs
+template <bool LP16> struct PathKernelContextT : PathKernelContextStfT<LP16, STF_OFF> {};
 typedef PathKernelContextT<false> PathKernelContext;      // the fp32 build of the lp types; PathKernelContextT<true> has the same data members
+
+// The instantiation of a launch: f(ctx) with ctx = the context of k's lp build and stochastic filter (all of them share one data layout). Only called with a filter on —
+// the launchers keep their deterministic branches as they were.
+template <class F> static inline void dispatch_stf(const PathKernelContext& k, F&& f) {
+    const int filter = stf_launch_filter(k.S);
+#define PT_STF_CASE(LP, FILTER) do { PathKernelContextStfT<LP, FILTER> c; static_assert(sizeof(c) == sizeof(k), "one context layout"); __builtin_memcpy(&c, &k, sizeof(c)); f(c); } while (0)
+    if (k.S.useFp16Types) { if (filter == STF_POINT) PT_STF_CASE(true, STF_POINT); else if (filter == STF_CUBIC) PT_STF_CASE(true, STF_CUBIC); else PT_STF_CASE(true, STF_LINEAR); }
+    else { if (filter == STF_POINT) PT_STF_CASE(false, STF_POINT); else if (filter == STF_CUBIC) PT_STF_CASE(false, STF_CUBIC); else PT_STF_CASE(false, STF_LINEAR); }
+#undef PT_STF_CASE
+}
 
 #pragma clang force_cuda_host_device end
 } // namespace ptk

@@ -377,6 +377,12 @@ static inline SPMaterialInfo SP_material_info(uint flags, const MVBlockInputs& g
     return m;
 }
 
+// Bridge::loadSurface of a pass's vertex, as both sides have it. A side whose material lookups take random numbers (the device contexts with a stochastic texture filter,
+// pt_stableplanes_device.h) has a more specialised overload that also reads the path's pixel and vertex index and the pass's sample index.
+template <class PT> static inline SurfaceData SP_load_surface(const PT& pt, uint prim, float bu, float bv, float3 rayDir, const PathState& path, uint /*sampleIndex*/, MVBlockInputs* mv) {
+    return pt.loadSurface(prim, bu, bv, rayDir, path.rayCone, mv);
+}
+
 // ---- the BUILD pass over one path vertex. PT is the path tracer of the side that includes this header (the wavefront kernels' PathKernelContextT<LP16>, or the CPU restatement's PathTracer):
 // loadSurface, HandleNestedDielectrics, volumeTransmittance, UpdatePathTravelled, HasFinishedSurfaceBounces and the scene's materials come from it.
 template <class PT> struct StablePlanesBuilder {
@@ -545,7 +551,7 @@ template <class PT> struct StablePlanesBuilder {
     void HandleHit(PathState& path, float3 rayOrigin, float3 rayDir, uint prim, float rayTCurrent, float bu, float bv) const {
         pt.UpdatePathTravelled(path, rayTCurrent);
         MVBlockInputs mvGeo;
-        SurfaceData surfaceData = pt.loadSurface(prim, bu, bv, rayDir, path.rayCone, &mvGeo);
+        SurfaceData surfaceData = SP_load_surface(pt, prim, bu, bv, rayDir, path, sampleIndex, &mvGeo);
         const SPMaterialInfo mi = SP_material_info(SP_material_flags(pt, surfaceData.shadingData.materialID), mvGeo, path.rayCone, path.id, path.getVertexIndex(), sampleIndex);
         if (pt.S.nestedDielectricsQuality > 0 && !path.interiorList.isEmpty()) {
             const float3 transmittance = pt.volumeTransmittance(path.interiorList.getTopMaterialID(), rayTCurrent);
@@ -862,7 +868,7 @@ template <class PT> struct StablePlanesFiller {
         req.valid = false;
         pt.UpdatePathTravelled(path, rayTCurrent);
         MVBlockInputs mvGeo;
-        SurfaceData surfaceData = pt.loadSurface(prim, bu, bv, rayDir, path.rayCone, &mvGeo);
+        SurfaceData surfaceData = SP_load_surface(pt, prim, bu, bv, rayDir, path, sampleIndex, &mvGeo);
         const SPMaterialInfo mi = SP_material_info(SP_material_flags(pt, surfaceData.shadingData.materialID), mvGeo, path.rayCone, path.id, path.getVertexIndex(), sampleIndex);
         if (pt.S.nestedDielectricsQuality > 0 && !path.interiorList.isEmpty()) {
             const float3 transmittance = pt.volumeTransmittance(path.interiorList.getTopMaterialID(), rayTCurrent);

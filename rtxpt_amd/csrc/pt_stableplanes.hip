@@ -5,6 +5,7 @@
 // launches (launch_extend: k_extend + straggler rounds); k_sp_build_shade is the pass's hit / miss shader. Only delta paths are followed: no random numbers beyond the camera ray,
 // no NEE, no shadow rays, no Russian roulette. The pass is a few rays per pixel; its kernels are written for clarity, not tuned.
 #include "pt_stableplanes_launch.h"
+#include <type_traits>
 
 namespace ptk {
 
@@ -176,6 +177,9 @@ void launch_sp_fill_shade(const PathKernelContext& k, const StablePlanesContext&
                           uint sampleIndex, WaveCounters* wc, uint* classScratch, uint* classCount, hipStream_t st) {
     // class-ordered shading as in reference mode (k_classify): a shading wave lives as long as its longest lane, misses and hits that end after their emission leave early when they sit together
     if (classScratch) { launch_classify(pool, queueIn, countInPtr, countIn, classScratch, classCount, st); queueIn = classScratch; } else classCount = nullptr;
+    // (a stochastic texture filter, pt_set_texture_filtering: the shading kernels' instantiations over that context; the other kernels of the pass load no surface)
+    if (stf_launch_filter(k.S) != STF_OFF) { dispatch_stf(k, [&](const auto& c) { typedef typename std::decay<decltype(c)>::type PKC;
+        hipLaunchKernelGGL((k_sp_fill_shade<PKC>), dim3((countIn + 255u) / 256u), dim3(256), 0, st, c, sp, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, newL, sampleIndex, wc, (const uint*)classCount); }); return; }
     SP_LAUNCH(k_sp_fill_shade, dim3((countIn + 255u) / 256u), sp, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, newL, sampleIndex, wc, (const uint*)classCount);
 }
 void launch_sp_fill_resolve(PathPool pool, uint4* mark, ShadowQueue sq, const float4* newL, const uint* countPtr, uint count, hipStream_t st) {
@@ -239,6 +243,8 @@ void launch_sp_generate(const PathKernelContext& k, const StablePlanesContext& s
 void launch_sp_build_shade(const PathKernelContext& k, const StablePlanesContext& sp, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr,
                            uint sampleIndex, WaveCounters* wc, hipStream_t st) {
     const dim3 g((countIn + 255u) / 256u), b(256);
+    if (stf_launch_filter(k.S) != STF_OFF) { dispatch_stf(k, [&](const auto& c) { typedef typename std::decay<decltype(c)>::type PKC;
+        hipLaunchKernelGGL((k_sp_build_shade<PKC>), g, b, 0, st, c, sp, pool, queueIn, countInPtr, queueOut, countOutPtr, sampleIndex, wc); }); return; }
     if (k.S.useFp16Types) { PathKernelContextT<true> k16; __builtin_memcpy(&k16, &k, sizeof(k16));
         hipLaunchKernelGGL((k_sp_build_shade<PathKernelContextT<true>>), g, b, 0, st, k16, sp, pool, queueIn, countInPtr, queueOut, countOutPtr, sampleIndex, wc); }
     else hipLaunchKernelGGL((k_sp_build_shade<PathKernelContext>), g, b, 0, st, k, sp, pool, queueIn, countInPtr, queueOut, countOutPtr, sampleIndex, wc);

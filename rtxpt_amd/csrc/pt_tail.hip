@@ -20,6 +20,7 @@
 #include "pt_traverse8.h"
 #include "pt_traverse8p.h"
 #include "pt_wavefront_device.h"
+#include <type_traits>
 
 namespace ptk {
 
@@ -154,7 +155,8 @@ void launch_tail(const PathKernelContext& k, PathPool pool, const uint* queueIn,
     const bool neeat = k.sc.lights.LocalSamplingBuffer != nullptr || k.sc.lights.TemporalFeedbackRequired != 0u;
 #define PT_LAUNCH_TAIL(PKC, CTX) do { if (neeat) hipLaunchKernelGGL((k_tail<PKC, true>), dim3(g), dim3(T8_BLOCK), 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, maxBounces, deferIters); \
                                       else hipLaunchKernelGGL((k_tail<PKC, false>), dim3(g), dim3(T8_BLOCK), 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, maxBounces, deferIters); } while (0)
-    if (k.S.useFp16Types) { PathKernelContextT<true> k16; __builtin_memcpy(&k16, &k, sizeof(k16)); PT_LAUNCH_TAIL(PathKernelContextT<true>, k16); }
+    if (stf_launch_filter(k.S) != STF_OFF) dispatch_stf(k, [&](const auto& c) { typedef typename std::decay<decltype(c)>::type PKC; PT_LAUNCH_TAIL(PKC, c); });      // a stochastic texture filter (pt_set_texture_filtering): that context's instantiations
+    else if (k.S.useFp16Types) { PathKernelContextT<true> k16; __builtin_memcpy(&k16, &k, sizeof(k16)); PT_LAUNCH_TAIL(PathKernelContextT<true>, k16); }
     else PT_LAUNCH_TAIL(PathKernelContext, k);
 #undef PT_LAUNCH_TAIL
 }

@@ -8,6 +8,7 @@
 #include "pt_traverse8k.h"
 #include "pt_wavefront_device.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace ptk {
 
@@ -832,6 +833,19 @@ __global__ void __launch_bounds__(64) k_probe(PathKernelContext k, int kind, con
         else if (a[0] == 1u) r = sample_bilinear(k.sc, k.sc.textures[a[1]], a[4], uv);                                   // one integer mip
         else r = sample_grad_anisotropic(k.sc, k.sc.textures[a[1]], uv, make_float2(asfloat(a[4]), asfloat(a[5])), make_float2(asfloat(a[6]), asfloat(a[7])));
         out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w; } break;
+    // stochastic texture filtering (pt_stf.h; include/mi355pt_testhooks.h kind 12): twelve words in, eight out; pt_probe has checked mode, texture and filter against the scene
+    case 12: { const uint* a = reinterpret_cast<const uint*>(in) + 12 * i; uint* o = reinterpret_cast<uint*>(out) + 8 * i;
+        for (int q = 0; q < 8; q++) o[q] = 0u;
+        if (a[0] == 0u) {      // the lookup of a context with filter a[5], at the four numbers of words 6-9: the texel, then the level and the position it was taken from
+            const uint textureIndex = a[1] & 0xFFFFu, baseLOD = a[1] >> 24, mipLevels = (a[1] >> 16) & 0xFFu;
+            float lambda = 0.5f * (float)baseLOD + asfloat(a[4]);      // sampleTexture's two lines (pt_path.h)
+            lambda = fminf_(lambda, fmaxf_((float)mipLevels - 5.0f, 0.0f));
+            const TexInfo& t = k.sc.textures[textureIndex];
+            const StfPick p = stf_pick_filter((int)a[5], t, make_float2(asfloat(a[2]), asfloat(a[3])), lambda, make_float4(asfloat(a[6]), asfloat(a[7]), asfloat(a[8]), asfloat(a[9])));
+            const float4 r = stf_texel(k.sc, t, p);
+            o[0] = asuint(r.x); o[1] = asuint(r.y); o[2] = asuint(r.z); o[3] = asuint(r.w); o[4] = p.mip; o[5] = (uint)p.x; o[6] = (uint)p.y;
+        } else { const float4 u = stf_draw(a[6], a[7], a[8]); o[0] = asuint(u.x); o[1] = asuint(u.y); o[2] = asuint(u.z); o[3] = asuint(u.w); }      // the four numbers loadSurface draws for (packed pixel, vertex, sample)
+        } break;
     default: break;
     }
 }
@@ -983,7 +997,9 @@ void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn
                                               else if (pool.home && !MULTI && fv) hipLaunchKernelGGL((k_shade<false, PKC, false, true, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
                                               else if (pool.home && !MULTI) hipLaunchKernelGGL((k_shade<false, PKC, false, true>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); \
                                               else hipLaunchKernelGGL((k_shade<MULTI, PKC, false>), g, b, 0, st, CTX, pool, queueIn, countInPtr, queueOut, countOutPtr, sq, wc, classCount, outPool, fv0); } while (0)
-    if (k.S.useFp16Types) {          // the reference's default build of its lp types (binary16): same context data, the other instantiation of the shading code
+    if (stf_launch_filter(k.S) != STF_OFF) {      // a stochastic texture filter (pt_set_texture_filtering): the same launches over that context's instantiations
+        dispatch_stf(k, [&](const auto& c) { typedef typename std::decay<decltype(c)>::type PKC; if (sq.group) PT_LAUNCH_SHADE(true, PKC, c); else PT_LAUNCH_SHADE(false, PKC, c); });
+    } else if (k.S.useFp16Types) {          // the reference's default build of its lp types (binary16): same context data, the other instantiation of the shading code
         static_assert(sizeof(PathKernelContextT<true>) == sizeof(PathKernelContext), "the two lp builds share one context layout");
         PathKernelContextT<true> k16; __builtin_memcpy(&k16, &k, sizeof(k16));
         if (sq.group) PT_LAUNCH_SHADE(true, PathKernelContextT<true>, k16); else PT_LAUNCH_SHADE(false, PathKernelContextT<true>, k16);

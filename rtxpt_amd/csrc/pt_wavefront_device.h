@@ -75,6 +75,8 @@ struct PathPoolIO {
         p.flagsAndVertexIndex = reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)i + 2u];
         return p;
     }
+    // (contexts with a stochastic texture filter: the two words that key loadSurface's random numbers; load_rest brings them again with their groups)
+    __device__ __forceinline__ void load_key(PathState& p) const { p.id = reinterpret_cast<const uint*>(pool.s0)[4u * (size_t)i + 3u]; p.sampleIndex = reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)i + 3u]; }
     __device__ __forceinline__ void load_rest(PathState& p) const {
         asm volatile("" ::: "memory");      // (not before the surface is loaded: these twelve registers are what the load order is about)
         uint4 a = pool.s0[i], c = pool.s2[i], e = pool.s4[i];
@@ -105,6 +107,7 @@ struct PathCompactIO {
         p.flagsAndVertexIndex = reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)i + 2u];
         return p;
     }
+    __device__ __forceinline__ void load_key(PathState& p) const { p.id = reinterpret_cast<const uint*>(pool.s0)[4u * (size_t)i + 3u]; p.sampleIndex = reinterpret_cast<const uint*>(pool.s4)[4u * (size_t)i + 3u]; }
     __device__ __forceinline__ void load_rest(PathState& p) const {
         asm volatile("" ::: "memory");
         uint4 a = pool.s0[i], c = pool.s2[hp], e = pool.s4[i];
@@ -131,6 +134,7 @@ template <class PKC> struct PathFirstVertexIO {
         k.computeCameraRay(px >> 16, px & 0xFFFFu, sample, o, p.dir);
         return p;
     }
+    __device__ __forceinline__ void load_key(PathState&) const {}      // (generateState has set the pixel id and the sample index)
     __device__ __forceinline__ void load_rest(PathState& p) const {
         uint q = px, s = sample; asm volatile("" : "+v"(q), "+v"(s) :: "memory");
         const PathState g = k.generate(q >> 16, q & 0xFFFFu, s);
