@@ -675,6 +675,48 @@ int32_t pt_reset_accumulation(pt_context* ctx);                                 
 int32_t pt_map_radiance(pt_context* ctx, const float** rgba32f, size_t* rowPitchBytes);
 int32_t pt_unmap_radiance(pt_context* ctx);
 
+/* Adaptive sampling in reference mode (docs/WIDENING.md N12; ours — the reference accumulates to a fixed AccumulationTarget and has no other stopping rule). The rank's pixels
+ * are sampled in rounds of `step` samples; after every round from minSamples on, each 8 x 8 screen block that is still active gets an error estimate E, and the blocks with
+ * E < threshold retire: the later rounds trace the remaining pixels only.
+ *     n = 0; active = the rank's pixel list
+ *     while active is not empty and n < maxSamples:
+ *         samples [n, n + step) of the active pixels are traced and folded into the accumulation buffer;  n += step
+ *         if n >= minSamples:  E of every active block;  active = the pixels of the blocks with !(E < threshold), in list order
+ * The estimate compares the accumulation buffer A (the mean of a pixel's samples) with a second buffer H, the running mean of its even-indexed samples, kept by the same
+ * kernel. Per pixel, one binary32 operation at a time in the written order:
+ *     d = |A.x - H.x| + |A.y - H.y| + |A.z - H.z|;  b = A.x + A.y + A.z;  e = d / sqrtf(fmaxf(b, darkFloor));  e = 0 unless e < +inf   (NaN and inf cannot be sampled away)
+ * Per block, the block's pixels in list order in v[0 .. count), zeros up to v[63]:  for off in 32, 16, 8, 4, 2, 1: v[i] = v[i] + v[i + off] for i < off;  E = v[0] / (float)count.
+ * What makes the result checkable: a pixel that received n samples holds exactly what pt_render(0, n) gives it, bit for bit (a sample is a function of the pixel, its index,
+ * the settings and the scene only). The accumulation buffer holds every pixel's mean over its own samples, so pt_tonemap, pt_bloom, pt_average_luminance, pt_map_radiance,
+ * pt_pack_shard and pt_gather work on the result unchanged.
+ * Limits: the granularity is the 8 x 8 block; a block's decision reads no neighbour (no dilation), so that the shards of a frame decide what the whole frame decides; not with
+ * NEE-AT (the reservoirs couple pixels and frames); the sample counts are per rank and are not gathered by pt_gather. */
+typedef struct PtAdaptiveParams {
+    uint32_t minSamples, maxSamples, step;   /* step even and >= 2; minSamples and maxSamples multiples of step; step <= minSamples <= maxSamples */
+    float    threshold;                      /* a block retires when E < threshold (strictly: 0 never retires, +inf retires everything at minSamples); not NaN */
+    float    darkFloor;                      /* > 0: lower bound of the brightness the error is taken relative to */
+} PtAdaptiveParams;
+typedef struct PtAdaptiveStats {
+    uint32_t rounds, evaluations;
+    uint64_t samplesTraced;                  /* sum over the rank's pixels of their sample counts */
+    uint32_t unconvergedPixels;              /* still active after the last evaluation */
+    uint32_t minCount, maxCount;             /* the smallest and the largest sample count of a pixel of this rank */
+    float    errorPassMs;                    /* device time of the error and compaction launches, summed over the call */
+} PtAdaptiveStats;
+/* minSamples 16, step 8, maxSamples 1024, threshold 0.02, darkFloor 0.01: starting values that nobody has measured against pictures yet, not a recommendation. */
+int32_t pt_adaptive_default_params(PtAdaptiveParams* out);
+/* Starts a new accumulation (as pt_reset_accumulation does) and runs the loop above. frameStats (may be NULL): pt_render's statistics summed over the rounds.
+ * PT_ERROR_NOT_READY before pt_resize; PT_ERROR_INVALID_ARGUMENT for parameters outside the constraints above, with NEE-AT enabled (pt_set_neeat) or with the temporal feedback
+ * of pt_set_local_light_sampling required. Afterwards the accumulation is per pixel: pt_render returns PT_ERROR_NOT_READY until the accumulation is reset — by
+ * pt_reset_accumulation, pt_resize, whatever else resets it (pt_animate*, a changed texture filter), or the next pt_render_adaptive. */
+int32_t pt_render_adaptive(pt_context* ctx, const PtAdaptiveParams* params, PtAdaptiveStats* stats, PtFrameStats* frameStats);
+/* The state the last pt_render_adaptive left; any pointer may be NULL. sampleCounts: width x height; halfRgba32f: the even-sample means, width x height x 4; both full-frame
+ * maps with the pixels of other shards zero. blockError: ((width + 7) / 8) x ((height + 7) / 8), the E of each block at its last evaluation (0 if never evaluated). */
+int32_t pt_get_adaptive_state(pt_context* ctx, uint32_t* sampleCounts, float* halfRgba32f, float* blockError);
+/* The pixels still active after the last evaluation, packed x << 16 | y, in list order. Returns their count (capacity 0: a query, nothing written) or the negative error
+ * (PT_ERROR_NOT_READY without an adaptive render of this frame size, PT_ERROR_INVALID_ARGUMENT for a capacity below the count). */
+int32_t pt_get_adaptive_active(pt_context* ctx, uint32_t* pixels, uint32_t capacity);
+
 /* RTXPT `.material.json` (the part the reference tree defines completely): PTMaterial::Read + PTMaterial::FillData
    (Rtxpt/Materials/MaterialsBaker.cpp:150-259, 516-591; defaults Rtxpt/Materials/MaterialsBaker.h:126-193). Host only, no context needed.
    textureWords[5]: packed PTMaterialData texture words (baseLOD << 24 | mipLevels << 16 | texture index, GetBindlessTextureIndex :487-509) of the

@@ -44,6 +44,7 @@ EXPORTS = [
     "pt_bloom_default_params", "pt_bloom_kernel", "pt_bloom", "pt_bloomed_device_buffer", "pt_get_bloomed", "pt_tonemap_bloomed", "pt_average_luminance_bloomed",
     "pt_taa_upscale_default_params", "pt_taa_upscale", "pt_upscaled_size", "pt_upscaled_device_buffer", "pt_get_upscaled", "pt_bloom_upscaled", "pt_get_upscaled_bloomed",
     "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
+    "pt_adaptive_default_params", "pt_render_adaptive", "pt_get_adaptive_state", "pt_get_adaptive_active",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal", "pt_get_bvh8", "pt_trace_route"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -856,6 +857,24 @@ def bloom_kernel(radius, lib=None, capacity=BLOOM_MAX_TAPS + 1):
     return g[:n.value + 1].copy(), np.float32(G.value)
 
 
+# PtAdaptiveParams / PtAdaptiveStats (include/mi355pt.h): adaptive sampling in reference mode (pt_render_adaptive)
+ADAPTIVE_PARAMS_DTYPE = np.dtype([("minSamples", "<u4"), ("maxSamples", "<u4"), ("step", "<u4"), ("threshold", "<f4"), ("darkFloor", "<f4")])
+ADAPTIVE_STATS_DTYPE = np.dtype([("rounds", "<u4"), ("evaluations", "<u4"), ("samplesTraced", "<u8"), ("unconvergedPixels", "<u4"), ("minCount", "<u4"), ("maxCount", "<u4"),
+                                 ("errorPassMs", "<f4")])
+assert ADAPTIVE_PARAMS_DTYPE.itemsize == 20 and ADAPTIVE_STATS_DTYPE.itemsize == 32
+
+
+def adaptive_default_params(lib=None, **overrides):
+    """pt_adaptive_default_params: minSamples 16, step 8, maxSamples 1024, threshold 0.02, darkFloor 0.01 (starting values, unmeasured); keywords override"""
+    L = lib or load_library()
+    out = np.zeros((), ADAPTIVE_PARAMS_DTYPE)
+    f = L.pt_adaptive_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_adaptive_default_params")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -1414,6 +1433,36 @@ class PathTracer:
         st = PtFrameStats()
         self._chk(self.L.pt_render(self.h, first, count, ctypes.byref(st)), "pt_render")
         return st.as_dict()
+
+    def render_adaptive(self, params=None):
+        """pt_render_adaptive: a new accumulation sampled in rounds of `step` samples, the 8 x 8 blocks whose error estimate is below the threshold leaving between rounds
+        (ADAPTIVE_PARAMS_DTYPE; defaults if None). Returns (PtAdaptiveStats as a dict, PtFrameStats summed over the rounds as a dict). render() is refused afterwards
+        until reset_accumulation()."""
+        ap = np.ascontiguousarray(adaptive_default_params(self.L) if params is None else params); assert ap.dtype == ADAPTIVE_PARAMS_DTYPE
+        st = np.zeros((), ADAPTIVE_STATS_DTYPE); fs = PtFrameStats()
+        f = self.L.pt_render_adaptive; f.argtypes = [ctypes.c_void_p] * 4; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(ap), _p(st), ctypes.byref(fs)), "pt_render_adaptive")
+        return {n: st[n].item() for n in ADAPTIVE_STATS_DTYPE.names}, fs.as_dict()
+
+    def adaptive_state(self):
+        """pt_get_adaptive_state: what the last render_adaptive left — counts [h, w] u32 and half [h, w, 4] f32 (the means of the even-indexed samples), full-frame maps
+        with the pixels of other shards zero, and block_error [ceil(h / 8), ceil(w / 8)] f32, every block's error at its last evaluation"""
+        h, w = self.height, self.width
+        out = dict(counts=np.zeros((h, w), np.uint32), half=np.zeros((h, w, 4), np.float32), block_error=np.zeros(((h + 7) // 8, (w + 7) // 8), np.float32))
+        f = self.L.pt_get_adaptive_state; f.argtypes = [ctypes.c_void_p] * 4; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out["counts"]), _p(out["half"]), _p(out["block_error"])), "pt_get_adaptive_state")
+        return out
+
+    def adaptive_active(self):
+        """pt_get_adaptive_active: the pixels still active after the last evaluation, packed x << 16 | y, in list order (u32)"""
+        f = self.L.pt_get_adaptive_active; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        n = f(self.h, None, 0)
+        if n < 0: self._chk(-n, "pt_get_adaptive_active")
+        out = np.zeros(n, np.uint32)
+        if n:
+            r = f(self.h, _p(out), n)
+            if r < 0: self._chk(-r, "pt_get_adaptive_active")
+        return out
 
     def radiance(self):
         ptr = ctypes.POINTER(ctypes.c_float)()

@@ -7,6 +7,7 @@
 #include "pt_stableplanes_launch.h"
 #include "pt_denoiser.h"
 #include "pt_build.h"
+#include "pt_adaptive.h"
 #include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
 #include <string>
 #include <vector>
@@ -256,6 +257,16 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     DevBuf<ptk::float4> dTaau[2], dTaauBloom, dTaauBloomQ[2]; uint taauW = 0, taauH = 0, taauRenderW = 0, taauRenderH = 0, taauSide = 0, taauFrameSerial = 0;
     bool taauHistory = false, taauResolved = false, taauBloomReady = false;
     hipEvent_t taauEvents[2] = {nullptr, nullptr}, taauBloomEvents[2] = {nullptr, nullptr};
+    // adaptive sampling (pt_render_adaptive; pt_adaptive.h). perPixel: the accumulation buffer holds per-pixel sample counts — pt_render refuses until the accumulation is reset.
+    // tableValid: ownedBlocks / dBlkOwned describe the current owned list (its 8 x 8 blocks as runs of the list; built at first use, dropped by pt_resize). stateValid: dHalf,
+    // dCounts, dBlockError and the active lists are the last adaptive render's, of this frame size. The active lists: the owned list and its block table before the first
+    // evaluation that retires something, then one of the two list pairs (activePix / activeBlk point at the current one). hostTotals: pinned, two words.
+    struct Adaptive {
+        bool perPixel = false, tableValid = false, stateValid = false;
+        std::vector<ptk::AdaptiveBlock> ownedBlocks; DevBuf<ptk::AdaptiveBlock> dBlkOwned, dBlk[2]; DevBuf<uint> dPix[2], dCounts, dTotals; DevBuf<ptk::float4> dHalf;
+        DevBuf<float> dBlockError; DevBuf<ptk::uint2> dFlags, dChunks; uint* hostTotals = nullptr;
+        const uint* activePix = nullptr; const ptk::AdaptiveBlock* activeBlk = nullptr; uint activeCount = 0, activeBlocks = 0;
+    } adaptive;
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -308,7 +319,13 @@ void bloom_free(pt_context* c);
 // ---- pt_taau_api.hip: the upscaling resolve's history, picture and bloomed picture are dropped (resize to another size, new scene) / its buffers freed
 void taau_drop_history(pt_context* c);
 void taau_free(pt_context* c);
+// ---- pt_adaptive_api.hip: the adaptive state is dropped (resize, new shard lists) / its buffers freed
+void adaptive_drop(pt_context* c);
+void adaptive_free(pt_context* c);
 // ---- pt_frame.hip
+// pt_render's frame over `numPixels` entries of a device pixel list (x << 16 | y) whose pixels all hold accumBase samples: samples [first, first + count) traced and folded in.
+// pt_render passes the owned list and no round (and the call advances c->accumCount); pt_render_adaptive passes the active list and the round's AdaptiveRound.
+int32_t render_pixel_list(pt_context* c, const uint* pixels, uint numPixels, uint32_t first, uint32_t count, uint accumBase, ptk::AdaptiveRound* round, PtFrameStats* stats);
 // the stable-plane buffers of the context with a frame's constants; params == nullptr: zeroed params with all planes active (what the
 // passes that only address the buffers need: pack / unpack, merge, read-back)
 StablePlanesContext sp_context(pt_context* c, const PtStablePlanesParams* params);

@@ -79,12 +79,13 @@ uint batch_count(const pt_context* c, uint paths) {
     if (c->serialKernels || paths < (1u << 20)) return 1u;
     return paths < PT_PIPELINE_FULL_AT ? (uint)PT_PIPELINE_MID_BATCHES : (uint)PT_PIPELINE_BATCHES;
 }
-// Batch b of numBatches with all its slices. pathsPerPixel: pt_render's sample count, 1 in the realtime passes; frameSq: the shadow queue of
+// Batch b of numBatches with all its slices. numPixels: the entries of the pixel list the frame is traced over (the owned list, or pt_render_adaptive's active list);
+// pathsPerPixel: pt_render's sample count, 1 in the realtime passes; frameSq: the shadow queue of
 // the whole frame (shadowPerPath entries per path); maxBlocks: the grid bound of the batch's traversal launches (0: T8_MAX_BLOCKS). The
 // host's copy of the batch's counters is left zeroed.
-void slice_batch(pt_context* c, const PathKernelContext& k, uint b, uint numBatches, uint pathsPerPixel, uint shadowPerPath,
+void slice_batch(pt_context* c, const PathKernelContext& k, uint numPixels, uint b, uint numBatches, uint pathsPerPixel, uint shadowPerPath,
                  const ShadowQueue& frameSq, uint maxBlocks, Batch& t) {
-    const unsigned long long numOwned = c->owned.size();
+    const unsigned long long numOwned = numPixels;
     t.pixFirst = (uint)(numOwned * b / numBatches); t.numPix = (uint)(numOwned * (b + 1) / numBatches) - t.pixFirst;
     t.total = t.numPix * pathsPerPixel; t.base = t.pixFirst * pathsPerPixel;
     t.st = c->streams[b]; t.wc = c->dCounters.p + b; t.hwc = c->hostCounters + b;
@@ -168,9 +169,11 @@ struct RenderBatch : Batch {
     void span(size_t a, size_t b, int kind, uint items) { if (timed) spans.push_back({a, b, kind, items}); }
 };
 
-// One pt_render call: the batches and what every pass of every batch needs to know.
+// One frame of render_pixel_list (a pt_render call, a round of pt_render_adaptive): the batches and what every pass of every batch needs to know. pixels / numPixels: the
+// device pixel list the frame is traced over, whose pixels all hold accumBase samples; round: pt_render_adaptive's (nullptr: pt_render).
 struct RenderFrame {
     pt_context* c; uint first, count, total, shadowGroup, shadowPerPath; bool feedback;
+    const uint* pixels; uint numPixels, accumBase; AdaptiveRound* round;
     uint numBatches = 0; RenderBatch B[PT_PIPELINE_BATCHES];
     uint maxIter = 0, tailBelow = 0, wavefrontPasses = 0; bool fused = false, passLog = false;
 
@@ -197,7 +200,7 @@ struct RenderFrame {
         passLog = getenv("MI355PT_PASS_LOG") != nullptr;
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b];
-            slice_batch(c, k, b, numBatches, count, shadowPerPath, sq, maxBlocks, t);
+            slice_batch(c, k, numPixels, b, numBatches, count, shadowPerPath, sq, maxBlocks, t);
             t.timed = c->serialKernels || c->countersEnabled || passLog;
             t.hwc->extendCount[0] = t.active = t.total;
         }
@@ -289,7 +292,7 @@ struct RenderFrame {
             RenderBatch& t = B[b];
             t.t0 = t.mark();
             PT_CHECK_HIP(c, hipMemcpyAsync(t.wc, t.hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, t.st));
-            if (!t.firstInPlace) launch_generate(t.k, t.pool, c->dOwned.p + t.pixFirst, t.numPix, first, count, 0u, t.total, t.queue[0], nullptr, t.st);
+            if (!t.firstInPlace) launch_generate(t.k, t.pool, pixels + t.pixFirst, t.numPix, first, count, 0u, t.total, t.queue[0], nullptr, t.st);
         }
         return PT_OK;
     }
@@ -309,7 +312,7 @@ struct RenderFrame {
         const uint* countIn = &t.wc->extendCount[t.cur];
         // (pass 0 of a batch has no visibility rays pending)
         const bool vertex0 = t.firstInPlace && t.iterations == 0u;
-        const FirstVertex fv{c->dOwned.p + t.pixFirst, t.numPix, first, count};
+        const FirstVertex fv{pixels + t.pixFirst, t.numPix, first, count};
         if (vertex0) launch_extend_first(t.k, pin, fv, countIn, t.active, t.wc, t.aux, t.packets, t.st);
         else if (t.pendingShadow) {
             launch_trace_pair(t.sc, pin, t.queue[t.cur], countIn, t.active, t.sq, &t.wc->shadowCount, t.pendingShadow, t.wc, t.aux, t.auxSh, t.st);
@@ -435,9 +438,23 @@ struct RenderFrame {
     void accumulate() {
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b];
-            launch_accumulate(t.pool, c->dOwned.p + t.pixFirst, t.numPix, count, c->dAccum.p, c->accumCount, c->width, t.st);
+            if (round) launch_adaptive_accumulate(t.pool, pixels + t.pixFirst, t.numPix, count, c->dAccum.p, round->half, round->counts, accumBase, c->width, t.st);
+            else launch_accumulate(t.pool, pixels + t.pixFirst, t.numPix, count, c->dAccum.p, accumBase, c->width, t.st);
             t.t1 = t.mark();
         }
+    }
+    // pt_render_adaptive's evaluation behind the round's accumulation: the main stream waits for every batch's, runs the error and compaction launches between two events of
+    // `ev` (returned through a / b) and sends the new lists' sizes to the host. drain_frame's synchronisation of the main stream is what the host waits on: no point of its own.
+    int32_t evaluate(Events& ev, size_t& a, size_t& b) {
+        for (uint q = 0; q < numBatches; q++) {
+            if (B[q].st == c->stream) continue;
+            PT_CHECK_HIP(c, ev.record(B[q].st)); PT_CHECK_HIP(c, hipStreamWaitEvent(c->stream, ev.ev.back(), 0));
+        }
+        PT_CHECK_HIP(c, ev.record(c->stream)); a = ev.ev.size() - 1;
+        launch_adaptive_evaluate(round->eval, c->stream);
+        PT_CHECK_HIP(c, ev.record(c->stream)); b = ev.ev.size() - 1;
+        PT_CHECK_HIP(c, hipMemcpyAsync(round->hostTotals, round->eval.totals, 2 * sizeof(uint), hipMemcpyDeviceToHost, c->stream));
+        return PT_OK;
     }
     // frameMs: from the first batch's start to the last batch's end (all streams were idle before and are drained now)
     void harvest(PtFrameStats& stats, float frameMs) const {
@@ -533,7 +550,7 @@ struct FillFrame {
         }
         for (uint b = 0; b < numBatches; b++) {
             FillBatch& t = B[b];
-            slice_batch(c, k, b, numBatches, 1u, 1u, sq, (numBatches >= 3u) ? 256u * 7u : 0u, t);
+            slice_batch(c, k, (uint)c->owned.size(), b, numBatches, 1u, 1u, sq, (numBatches >= 3u) ? 256u * 7u : 0u, t);
             t.markPool = t.pool; t.markPool.s2 = c->dSpMark.p + t.base; t.newL = c->dSpNewL.p + t.base;
         }
         maxIter = c->S.bounceCount + 2 + nested_dielectric_allowance(c->S) * (c->S.bounceCount + 1u);
@@ -633,6 +650,8 @@ extern "C" {
 int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* stats) {
     if (!c) return PT_ERROR_INVALID_ARGUMENT;
     if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
+    if (c->adaptive.perPixel)
+        return fail(c, PT_ERROR_NOT_READY, "the accumulation buffer holds an adaptive render (per-pixel sample counts): pt_reset_accumulation first");
     if (!count) return PT_OK;
     (void)hipSetDevice(c->device);
     int r = prepare(c); if (r != PT_OK) return r;
@@ -642,11 +661,19 @@ int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* s
         r = neeat_exchange_feedback(c); if (r != PT_OK) return r;
         r = neeat_frame(c); if (r != PT_OK) return r;
     }
-    const uint numOwned = (uint)c->owned.size();
-    if ((unsigned long long)numOwned * count > 0xF0000000ull) return fail(c, PT_ERROR_INVALID_ARGUMENT, "too many paths in one pt_render call");
-    const uint total = numOwned * count;
+    return render_pixel_list(c, c->dOwned.p, (uint)c->owned.size(), first, count, c->accumCount, nullptr, stats);
+}
+
+} // extern "C"
+
+// The frame both reference-mode entry points share: everything of it — pool, batches, vertex-0 packets, compacted pool, fused traversal, tail kernel — runs on whatever
+// count the list has. With a round, k_adaptive_accumulate replaces k_accumulate and the round's evaluation follows it.
+int32_t render_pixel_list(pt_context* c, const uint* pixels, uint numPixels, uint32_t first, uint32_t count, uint accumBase, AdaptiveRound* round, PtFrameStats* stats) {
+    int r = PT_OK;
+    if ((unsigned long long)numPixels * count > 0xF0000000ull) return fail(c, PT_ERROR_INVALID_ARGUMENT, "too many paths in one pt_render call");
+    const uint total = numPixels * count;
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (total == 0) { c->accumCount += count; return PT_OK; }
+    if (total == 0) { if (!round) c->accumCount += count; return PT_OK; }
     // min(RTXPT_LIGHTING_MAX_SAMPLE_COUNT, NEEFullSamples), PathTracerNEE.hlsli:312
     const uint neeSamples = c->S.NEEFullSamples < 63u ? c->S.NEEFullSamples : 63u;
     // 0: one shadow-queue entry per path vertex, written by k_shade itself
@@ -659,7 +686,7 @@ int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* s
     // `applyNEE &= fullSamples > 0` (PathTracerNEE.hlsli:322): the vertices behave as without NEE; the light tables stay as baked
     if (neeSamples == 0u) k.S.NEEEnabled = 0;
 
-    RenderFrame f{c, first, count, total, shadowGroup, shadowPerPath, feedback};
+    RenderFrame f{c, first, count, total, shadowGroup, shadowPerPath, feedback, pixels, numPixels, accumBase, round};
     r = f.setup(k); if (r != PT_OK) return r;
     // uploads issued on the main stream (prepare) must be visible to the other streams
     if (f.numBatches > 1) PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
@@ -668,8 +695,11 @@ int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* s
     r = f.lockstep(); if (r != PT_OK) return r;
     r = f.free_run(); if (r != PT_OK) return r;
     f.accumulate();
+    Events evalMarks; size_t e0 = 0, e1 = 0;
+    if (round && round->evaluate) { r = f.evaluate(evalMarks, e0, e1); if (r != PT_OK) return r; }
     r = drain_frame(c, f.B, f.numBatches, frame); if (r != PT_OK) return r;
-    c->accumCount += count;
+    if (round) round->errorPassMs = round->evaluate ? evalMarks.ms(e0, e1) : 0.0f;
+    else c->accumCount += count;
     if (feedback) c->fbSamples = count;
     if (stats) f.harvest(*stats, frame.ms());
     c->droppedTerminal = 0; for (uint b = 0; b < f.numBatches; b++) c->droppedTerminal += f.B[b].hwc->droppedTerminal;
@@ -677,6 +707,8 @@ int32_t pt_render(pt_context* c, uint32_t first, uint32_t count, PtFrameStats* s
     return check_frame_end(c, f.B, f.numBatches,
                            "pt_render: paths still alive at the pass bound (bounceCount + 2 + the nested-dielectric allowance): the bound must be raised");
 }
+
+extern "C" {
 
 int32_t pt_build_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStablePlanesParams* params, PtFrameStats* stats) {
     if (!c || !params) return PT_ERROR_INVALID_ARGUMENT;
@@ -692,7 +724,7 @@ int32_t pt_build_stable_planes(pt_context* c, uint32_t sampleIndex, const PtStab
     if (!numOwned) return PT_OK;
     PathKernelContext k = kernel_context(c);
     // a batch of one, but on the context's main stream: what later calls synchronise with
-    Batch t; slice_batch(c, k, 0u, 1u, 1u, 1u, frame_shadow_queue(c, 0u), 0u, t);
+    Batch t; slice_batch(c, k, numOwned, 0u, 1u, 1u, 1u, frame_shadow_queue(c, 0u), 0u, t);
     t.st = c->stream; t.hwc->extendCount[0] = t.active = t.total;
     Events frame; PT_CHECK_HIP(c, frame.record(t.st));
     PT_CHECK_HIP(c, hipMemcpyAsync(t.wc, t.hwc, sizeof(WaveCounters), hipMemcpyHostToDevice, t.st));
