@@ -990,7 +990,9 @@ int32_t pt_set_tail_paths(pt_context* ctx, uint32_t maxPaths);
    That pass's first traversal launch traces the camera rays as packets: the rays of 32 consecutive paths walk the tree together on one stack per wave, and the few packets that
    take more than 128 steps are traced again ray by ray behind it (on by default; environment MI355PT_FIRST_VERTEX_PACKETS=0 at pt_create: every camera ray is traced on its own, as
    before; MI355PT_PACKET_STEP_CAP / MI355PT_PACKET_STACK, also read at pt_create, set the step cap and the stack entries of a packet — test switches). The closest hit does not
-   depend on the order in which triangles are looked at: same hits, same image, same counts (tests/test_gpu_packet_first.py).
+   depend on the order in which triangles are looked at: same hits, same image, same counts (tests/test_gpu_packet_first.py). The 64-ray packets test each child of a node once
+   against the packet as a whole before the rays' own tests (on by default; environment MI355PT_PACKET_PRECULL=0 at pt_create: every child is tested for every ray, as before); it
+   drops only children that no ray enters: same hits again (tests/test_gpu_packet_precull.py).
    Every pt_render pass that shades in class order (65 536 paths and more) leaves out the hits of terminating paths — paths shaded at their next hit for that hit's emission term
    alone — on primitives whose material can neither emit (EmissiveColor exactly zero) nor stand in for an analytic light, and whose hit the nested-dielectric check cannot reject
    (nestedDielectricsQuality 0, or a thin surface): such a vertex adds no radiance and ends the path, so nothing that is read again depends on it. The hit is still counted in

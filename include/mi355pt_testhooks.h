@@ -53,7 +53,7 @@ int32_t pt_get_bvh8(pt_context* ctx, uint32_t* numNodes, void* nodes, uint32_t c
  *   PT_ROUTE_PACKETS        64 or 32 rays per wave on one stack (traverse8_packets64 / traverse8_packets, by the context's packet mode), read from the same pool; the packets over the step cap or the stack bound leave their rays on a
  *                           list that launch_extend then traces one by one, task rounds included — what launch_extend_first does for camera rays. Fixed interval, as EXTEND.
  * options (may be null; a zero field is the product's value): taskCap = entries of a task queue (TASK_QUEUE_CAPACITY); maxBlocks = TravAux::maxBlocks, the grid bound of the
- * traversal launches; stepCap / stackBound = FirstPackets' (T8_PACKET_STEP_CAP or, for the 64-ray packets, T8_PACKET64_STEP_CAP; T8_PACKET_STACK). The packet route runs the traverser of the context's MI355PT_FIRST_VERTEX_PACKETS mode.
+ * traversal launches; stepCap / stackBound = FirstPackets' (T8_PACKET_STEP_CAP or, for the 64-ray packets, T8_PACKET64_STEP_CAP; T8_PACKET_STACK). The packet route runs the traverser of the context's MI355PT_FIRST_VERTEX_PACKETS mode, the 64-ray one with or without the packet's interval test (MI355PT_PACKET_PRECULL).
  * stats (may be null), written whenever the launches ran: splitRays = the resolve list's length (rays cut into sub-trees); taskCounts[r] = sub-trees fed to task round r;
  * packetRays = rays the packets committed themselves, leftoverRays = rays they left over (both 0 on the other routes); overflow = WaveCounters::overflow after the launches
  * (1: a stack tail, 2: a task queue or the leftover list ran out of room). A set overflow word is PT_ERROR_HIP, as at the end of pt_render — `out` is then not the answer.

@@ -631,6 +631,7 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
     { const char* e = getenv("MI355PT_COMPACT_POOL"); if (e) c->compactPool = atoi(e) != 0; }      // developer A/B / test switch, read at pt_create like the others
     { const char* e = getenv("MI355PT_FIRST_VERTEX_IN_PLACE"); if (e) c->firstVertexInPlace = atoi(e) != 0; }      // (0: k_generate in front of every batch, as before)
     { const char* e = getenv("MI355PT_FIRST_VERTEX_PACKETS"); if (e) { const int v = atoi(e); c->firstVertexPackets = v <= 0 ? 0u : (v == 1 ? 1u : 2u); } }      // (0: k_extend_first, one ray per lane pair; 1: 32-ray pair packets; 2: 64-ray packets, one lane per ray)
+    { const char* e = getenv("MI355PT_PACKET_PRECULL"); if (e) c->packetPrecull = atoi(e) != 0; }      // (0: the 64-ray packets test every child of a node for every ray)
     // test switches: the steps after which a packet goes to the per-ray kernel, and the entries of its stack (small values send most packets there)
     { const char* e = getenv("MI355PT_PACKET_STEP_CAP"); if (e) c->packetStepCap = (uint)strtoul(e, nullptr, 10); }
     { const char* e = getenv("MI355PT_PACKET_STACK"); if (e) c->packetStack = (uint)strtoul(e, nullptr, 10); }
@@ -1892,7 +1893,7 @@ int32_t pt_trace_route(pt_context* c, int32_t route, const float* rays, uint32_t
         PathPool pool{}; pool.s0 = B.s0.p; pool.s1 = B.s1.p; pool.hit = B.hit.p;      // (home == nullptr: every array is indexed by the queue's entries)
         if (route == PT_ROUTE_PACKETS) {
             PT_CHECK_HIP(c, B.leftover.resize(n));
-            const FirstPackets pk{B.leftover.p, B.words.p + PASS_LEFTOVER, n, opt.stepCap ? opt.stepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), opt.stackBound ? opt.stackBound : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u};      // (the traverser of the context's mode)
+            const FirstPackets pk{B.leftover.p, B.words.p + PASS_LEFTOVER, n, opt.stepCap ? opt.stepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), opt.stackBound ? opt.stackBound : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u, c->packetPrecull ? 1u : 0u};      // (the traverser of the context's mode)
             launch_route_packets(c->dsc, pool, countPtr, n, B.wc.p, pk, B.words.p + ROUTE_WORD_COMMITTED, aux.maxBlocks, st);
             launch_extend(c->dsc, pool, pk.leftover, pk.leftoverCount, n, B.wc.p, false, aux, st);      // (n: the host's bound of the list's length, as launch_extend_first sizes k_extend_first_listed)
         } else launch_extend(c->dsc, pool, B.queue.p, countPtr, n, B.wc.p, false, aux, st, route == PT_ROUTE_EXTEND_RANGED);

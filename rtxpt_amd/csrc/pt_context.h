@@ -101,6 +101,11 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 // 0: k_extend_first, one ray per lane pair; 1: 32-ray packets in the lane-pair layout; 2: 64-ray packets, one lane per ray
 #define PT_FIRST_VERTEX_PACKETS 2
 #endif
+#ifndef PT_PACKET_PRECULL
+// ... and a node step of the 64-ray packets culls the node's children against the packet as a whole before the per-ray slab tests (pt_packet_precull.h; environment
+// MI355PT_PACKET_PRECULL overrides; 0: every child is tested for every ray)
+#define PT_PACKET_PRECULL 1
+#endif
 #ifndef PT_DROP_INERT_TERMINAL
 // pt_render: k_classify leaves out the hits of terminating paths (PF_terminateAtNextBounce) on primitives that can neither emit nor stand in for an analytic light — their
 // vertex would change nothing anybody reads (pt_wavefront.hip k_classify; environment MI355PT_DROP_INERT_TERMINAL overrides)
@@ -129,6 +134,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     uint tailBelow = PT_TAIL_PATHS, tailDefer = 0, fusedTraversal = PT_FUSED_TRAVERSAL; bool occlusionSlotOrder = true, compactPool = PT_COMPACT_POOL != 0, firstVertexInPlace = PT_FIRST_VERTEX_IN_PLACE != 0;
     // vertex 0 as packets (ptk::FirstPackets): the switch (0 / 1 / 2, as above), the step cap and stack bound of a packet (0: T8_PACKET_STEP_CAP or T8_PACKET64_STEP_CAP / T8_PACKET_STACK), the leftover list (one word per path)
     uint firstVertexPackets = PT_FIRST_VERTEX_PACKETS; uint packetStepCap = 0, packetStack = 0; DevBuf<uint> dFirstLeftover;
+    bool packetPrecull = PT_PACKET_PRECULL != 0;      // the 64-ray packets' interval test of a node's children (FirstPackets::precull)
     // pt_render's classified passes drop the terminal hits that can add nothing (k_classify, pt_wavefront.hip); droppedTerminal: how many the last pt_render call dropped
     bool dropInertTerminal = PT_DROP_INERT_TERMINAL != 0; unsigned long long droppedTerminal = 0;
     std::string lastError;

@@ -162,7 +162,7 @@ struct RenderBatch : Batch {
     uint pendingShadow = 0; TravAux auxSh;                          // fused traversal launches (enable_fused)
     PathPool poolSet[2]; uint set = 0; bool compact = false;        // the compacted pool (enable_compact_pool)
     bool firstInPlace = false;                                      // no k_generate: the first pass forms the vertex-0 state itself (enable_first_vertex_in_place)
-    FirstPackets packets = {nullptr, nullptr, 0u, 0u, 0u, 0u};          // ... and traces its camera rays as packets (leftover == nullptr: one by one)
+    FirstPackets packets = {nullptr, nullptr, 0u, 0u, 0u, 0u, 0u};         // ... and traces its camera rays as packets (leftover == nullptr: one by one)
     bool timed = false; Events marks; size_t t0 = 0, t1 = 0;
     struct Span { size_t a, b; int kind; uint items; }; std::vector<Span> spans;      // kind: 0 extend, 1 shade, 2 shadow, 3 tail
     size_t mark() { return timed ? marks.mark(st) : 0; }
@@ -283,7 +283,8 @@ struct RenderFrame {
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b]; if (!t.firstInPlace) continue;
             t.packets = FirstPackets{c->dFirstLeftover.p + t.base, t.aux.counts + PASS_LEFTOVER, t.total,
-                                     c->packetStepCap ? c->packetStepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u};
+                                     c->packetStepCap ? c->packetStepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u,
+                                     c->packetPrecull ? 1u : 0u};
         }
         return PT_OK;
     }

@@ -98,13 +98,18 @@ __device__ __forceinline__ void t8_slab_selectors(float ix, float iy, float iz, 
 #else
 #define T8_HIT(ref, tn, tf) ((tn) <= (tf) * 1.0000012f)
 #endif
+// a child's six planes in world space, (near, far) per axis by the selectors: they depend on the ray through the selectors alone, so rays with the same signs see the same
+// values (what the packet's interval test, pt_packet_precull.h, relies on)
+__device__ __forceinline__ void t8_slab_planes(uint q0, uint q1, uint selN, uint selF, float nx, float ny, float nz, float sx, float sy, float sz, f32x2& px, f32x2& py, f32x2& pz) {
+    const uint N = __builtin_amdgcn_perm(q1, q0, selN), F = __builtin_amdgcn_perm(q1, q0, selF);
+    px = __builtin_elementwise_fma((f32x2){(float)(N & 0xFFu), (float)(N >> 24)}, (f32x2){sx, sx}, (f32x2){nx, nx});
+    py = __builtin_elementwise_fma((f32x2){(float)((N >> 8) & 0xFFu), (float)(F & 0xFFu)}, (f32x2){sy, sy}, (f32x2){ny, ny});
+    pz = __builtin_elementwise_fma((f32x2){(float)((N >> 16) & 0xFFu), (float)((F >> 8) & 0xFFu)}, (f32x2){sz, sz}, (f32x2){nz, nz});
+}
 // one child's slab test: the quantised planes (q0, q1: the child's six bytes) against the ray, clipped to [tmin, bestT]; n* / s* are the node's origin and scales
 __device__ __forceinline__ void t8_slab(uint q0, uint q1, uint selN, uint selF, float nx, float ny, float nz, float sx, float sy, float sz, float ox, float oy, float oz, float ix, float iy, float iz,
                                         float tmin, float bestT, float& tn, float& tf) {
-    const uint N = __builtin_amdgcn_perm(q1, q0, selN), F = __builtin_amdgcn_perm(q1, q0, selF);
-    f32x2 px = __builtin_elementwise_fma((f32x2){(float)(N & 0xFFu), (float)(N >> 24)}, (f32x2){sx, sx}, (f32x2){nx, nx});
-    f32x2 py = __builtin_elementwise_fma((f32x2){(float)((N >> 8) & 0xFFu), (float)(F & 0xFFu)}, (f32x2){sy, sy}, (f32x2){ny, ny});
-    f32x2 pz = __builtin_elementwise_fma((f32x2){(float)((N >> 16) & 0xFFu), (float)((F >> 8) & 0xFFu)}, (f32x2){sz, sz}, (f32x2){nz, nz});
+    f32x2 px, py, pz; t8_slab_planes(q0, q1, selN, selF, nx, ny, nz, sx, sy, sz, px, py, pz);
     f32x2 tx = (px - (f32x2){ox, ox}) * (f32x2){ix, ix}, ty = (py - (f32x2){oy, oy}) * (f32x2){iy, iy}, tz = (pz - (f32x2){oz, oz}) * (f32x2){iz, iz};
     tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tmin));
     tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, bestT));

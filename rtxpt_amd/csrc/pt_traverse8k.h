@@ -17,10 +17,12 @@
 // per-ray kernel traces from scratch behind this launch (pt_wavefront.hip launch_extend_first).
 //
 // Two traversers: traverse8_packets (32 rays, the lane-pair layout described above) and, further down, traverse8_packets64 (64 rays, one lane per ray, the uniform part
-// of a step in scalar registers), which the frame uses by default (MI355PT_FIRST_VERTEX_PACKETS, pt_context.h).
+// of a step in scalar registers), which the frame uses by default (MI355PT_FIRST_VERTEX_PACKETS, pt_context.h) — with a test of each child against the packet as a whole in
+// front of the per-ray slab tests (MI355PT_PACKET_PRECULL, pt_packet_precull.h).
 #pragma once
 #include "pt_traverse8p.h"
 #include "pt_wavefront.h"
+#include "pt_packet_precull.h"
 
 namespace ptk {
 
@@ -207,13 +209,25 @@ __device__ __forceinline__ void t8k_sort8(uint (&s)[8]) {
 #undef T8K_CE
 }
 
+// a float as a uint that orders like it (negative values below positive ones), and back: the wave minimum / maximum of floats through t8k_wave_min / t8k_wave_max
+__device__ __forceinline__ uint t8k_float_key(float f) { const uint b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ float t8k_key_float(uint k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+__device__ __forceinline__ float t8k_wave_fmin(float v) { return t8k_key_float(t8k_wave_min(t8k_float_key(v))); }
+__device__ __forceinline__ float t8k_wave_fmax(float v) { return t8k_key_float(t8k_wave_max(t8k_float_key(v))); }
+
+// PRECULL (MI355PT_PACKET_PRECULL, FirstPackets::precull): before the eight per-ray slab tests of a node step, lane c < 8 tests child c against the packet as a whole
+// (pt_packet_precull.h: the intervals of the rays' origins and reciprocals, formed once per packet and kept in the wave's sixteen words of LDS at `intervalBase`), and the
+// per-ray test of a child runs only under a scalar branch on its bit of the ballot. The interval test drops a child only if NO ray's own T8_HIT can be true, so the hit mask,
+// the keys, the order and the pushes — and with them the three invariants above — are what they are without it. A packet whose rays' reciprocals have both signs on an axis has
+// no test: every child is kept.
 // Ray: void form(uint i, float3& o, float3& d) — ray i of the launch, formed once, by the lane that holds it. Dst: void commit(uint i, const HitInfo&), by the same lane.
-template <class Ray, class Dst>
-__device__ __forceinline__ void traverse8_packets64(const DeviceScene& sc, const uint count, uint2* stackBase, Ray form, Dst commit, const FirstPackets pk, uint* overflowFlag) {
+template <bool PRECULL, class Ray, class Dst>
+__device__ __forceinline__ void traverse8_packets64(const DeviceScene& sc, const uint count, uint2* stackBase, float* intervalBase, Ray form, Dst commit, const FirstPackets pk, uint* overflowFlag) {
     const uint lane = threadIdx.x & 63u;
     const uint wavesPerBlock = T8_BLOCK / 64u;
     const uint waveId = t8k_uniform(blockIdx.x * wavesPerBlock + (threadIdx.x >> 6)), numWaves = t8k_uniform(gridDim.x * wavesPerBlock);
     uint2* stack = stackBase + t8k_uniform(threadIdx.x >> 6) * T8_PACKET_STACK;
+    float* interval = PRECULL ? intervalBase + t8k_uniform(threadIdx.x >> 6) * T8_PACKET_INTERVAL_WORDS : nullptr;
     const char* nodesBase = reinterpret_cast<const char*>(sc.nodes8);
     const char* trisBase = reinterpret_cast<const char*>(sc.tris);
     const uint INF_BITS = 0x7F800000u;
@@ -233,6 +247,18 @@ __device__ __forceinline__ void traverse8_packets64(const DeviceScene& sc, const
         // wave-uniform: the node in hand, the stack pointer, the steps so far, the largest best t of the packet (as bits: t > 0)
         uint cur = sc.rootIsValid ? 0u : BVH_EMPTY, sp = 0u, steps = 0u, maxBest = __float_as_uint(tmax);
         bool handOff = false;
+        // the packet's interval: every lane holds a ray of THIS packet (an idle lane the launch's last ray, which the last packet holds), so the extremes are taken over all
+        // lanes, and when the signs are definite every lane's selectors are the packet's
+        bool culls = false;
+        if (PRECULL) {
+            T8PacketInterval pi;
+            culls = t8_packet_interval(t8k_wave_fmin(o.x), t8k_wave_fmin(o.y), t8k_wave_fmin(o.z), t8k_wave_fmax(o.x), t8k_wave_fmax(o.y), t8k_wave_fmax(o.z),
+                                       t8k_wave_fmin(ix), t8k_wave_fmin(iy), t8k_wave_fmin(iz), t8k_wave_fmax(ix), t8k_wave_fmax(iy), t8k_wave_fmax(iz), pi);
+            if (lane == 0u) {
+                f32x4* dst = reinterpret_cast<f32x4*>(interval);
+                dst[0] = (f32x4){pi.oNx, pi.oNy, pi.oNz, pi.oFx}; dst[1] = (f32x4){pi.oFy, pi.oFz, pi.iLox, pi.iLoy}; dst[2] = (f32x4){pi.iLoz, pi.iHix, pi.iHiy, pi.iHiz};
+            }
+        }
 
         for (;;) {
             if (cur == BVH_EMPTY) {
@@ -261,16 +287,29 @@ __device__ __forceinline__ void traverse8_packets64(const DeviceScene& sc, const
                 const uint q0[8] = {w0[5], w0[8], w0[11], w0[14], w1[1], w1[4], w1[7], w1[10]};
                 const uint q1[8] = {w0[6], w0[9], w0[12], w0[15], w1[2], w1[5], w1[8], w1[11]};
                 const uint ref[8] = {w0[4], w0[7], w0[10], w0[13], w1[0], w1[3], w1[6], w1[9]};
+                // the children some ray may enter: lane c < 8 holds child c's plane bytes (the two words behind its reference) and tests its box against the packet's interval,
+                // read at a uniform LDS address; t8_slab_planes on the lane's own selectors, which are the packet's
+                uint keep = 0xFFu;
+                if (PRECULL && culls) {
+                    const uint vq0 = *reinterpret_cast<const uint*>(nodesBase + nodeOff + refOff + 4u), vq1 = *reinterpret_cast<const uint*>(nodesBase + nodeOff + refOff + 8u);
+                    const f32x4* src = reinterpret_cast<const f32x4*>(interval);
+                    const f32x4 a = src[0], b = src[1], c = src[2];
+                    const T8PacketInterval pi = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+                    f32x2 px, py, pz; t8_slab_planes(vq0, vq1, selN, selF, nx, ny, nz, sx, sy, sz, px, py, pz);
+                    keep = (uint)t8_ballot(t8_packet_keeps(px.x, px.y, py.x, py.y, pz.x, pz.y, pi, tmin, __uint_as_float(maxBest))) & 0xFFu;
+                }
                 // a child's key: the minimum over the rays that enter it of the entry distance (tn >= 0: the bits order like the value; the sign is cleared with the index
                 // bits, so a -0 is a 0), then the child index in the low bits (unique keys, ties to the lower child); +inf for a child that nothing enters
                 uint sk[8]; uint nhit = 0u;
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
-                    float tn, tf;
-                    t8_slab(q0[k], q1[k], selN, selF, nx, ny, nz, sx, sy, sz, o.x, o.y, o.z, ix, iy, iz, tmin, bestT, tn, tf);
-                    const bool hit = T8_HIT(ref[k], tn, tf);      // (an empty slot is an inverted box, which nothing enters: pt_traverse8.h T8_EMPTY_SLOT_CHECK)
                     uint mk = INF_BITS;
-                    if (t8_ballot(hit) != 0ull) { mk = t8k_wave_min(hit ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS); nhit++; }
+                    if (!PRECULL || ((keep >> k) & 1u)) {
+                        float tn, tf;
+                        t8_slab(q0[k], q1[k], selN, selF, nx, ny, nz, sx, sy, sz, o.x, o.y, o.z, ix, iy, iz, tmin, bestT, tn, tf);
+                        const bool hit = T8_HIT(ref[k], tn, tf);      // (an empty slot is an inverted box, which nothing enters: pt_traverse8.h T8_EMPTY_SLOT_CHECK)
+                        if (t8_ballot(hit) != 0ull) { mk = t8k_wave_min(hit ? (__float_as_uint(tn) & 0x7FFFFFF8u) : INF_BITS); nhit++; }
+                    }
                     sk[k] = mk | (uint)k;
                 }
                 uint next = BVH_EMPTY;

@@ -70,7 +70,10 @@ void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, cons
 #endif
 static const uint T8_PACKET_RAYS = 32, T8_PACKET64_RAYS = 64;
 // wide != 0: 64-ray packets, one lane per ray (k_extend_first_packets64, traverse8_packets64); 0: the 32-ray pair packets
-struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound, wide; };
+// precull != 0 (64-ray packets only): a node step first tests each child against the packet's interval of origins and reciprocals, and runs the per-ray slab tests only for
+// the children that test keeps (pt_packet_precull.h; environment MI355PT_PACKET_PRECULL)
+struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound, wide, precull; };
+static const uint T8_PACKET_INTERVAL_WORDS = 16;      // a wave's LDS words for its packet's interval (twelve floats, read as three 16-byte groups)
 void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, FirstPackets pk, hipStream_t st);
 // classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (4 words, zero on entry: three classes and the dropped hits): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)

@@ -112,8 +112,11 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first
 }
 // The same as 64-ray packets, one lane per ray (traverse8_packets64): 64 consecutive paths — two rows of an 8 x 8 block x 4 samples at 4 spp. The lane that holds a ray reports
 // its hit, so there is no barycentrics parking lot; the wave's stack is all the LDS the kernel has.
+// PRECULL: the node step culls its children against the packet's interval first (pk.precull; the wave's interval is sixteen more words of LDS)
+template <bool PRECULL>
 __global__ void __launch_bounds__(T8_BLOCK, T8_PACKET64_MIN_BLOCKS) k_extend_first_packets64(DeviceScene sc, PathPool pool, FirstVertex fv, const uint* __restrict__ countPtr, WaveCounters* wc, FirstPackets pk) {
     __shared__ uint2 stack[(T8_BLOCK / 64u) * T8_PACKET_STACK];
+    __shared__ __attribute__((aligned(16))) float interval[PRECULL ? (T8_BLOCK / 64u) * T8_PACKET_INTERVAL_WORDS : 4u];
     auto form = [&](uint i, float3& o, float3& d) {
         asm volatile("" ::: "memory");      // (the camera from memory where a ray is formed, as t8_extend_body<..., FIRST> reads it)
         const FirstVertexCamera fc = wc->firstCamera;
@@ -121,7 +124,7 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_PACKET64_MIN_BLOCKS) k_extend_fir
         PathKernelContext::cameraRay(fc.cam, fc.perPixelJitterAAScale, px >> 16, px & 0xFFFFu, sample, o, d);
     };
     auto commit = [&](uint p, const HitInfo& h) { pool.hit[p] = make_uint4(asuint(h.t), h.prim, asuint(h.u), asuint(h.v)); };
-    traverse8_packets64(sc, *countPtr, stack, form, commit, pk, &wc->overflow);
+    traverse8_packets64<PRECULL>(sc, *countPtr, stack, interval, form, commit, pk, &wc->overflow);
 }
 // ... and the per-ray kernel over the rays the packets left over: k_extend_first reading i through the list (its count: what the packet launch appended)
 __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_extend_first_listed(DeviceScene sc, PathPool pool, FirstVertex fv, FirstPackets pk, WaveCounters* wc, TravAux aux, uint rpc) {
@@ -910,7 +913,8 @@ void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex 
     if (pk.leftover) {
         // the packets, then the per-ray kernel over what they left (its count is on the device: the grid that would hold all of it, and the waves without a chunk end at once)
         const uint gp = grid_for(count, (T8_BLOCK / 64u) * (pk.wide ? T8_PACKET64_RAYS : T8_PACKET_RAYS), (aux.maxBlocks && aux.maxBlocks < T8_MAX_BLOCKS) ? aux.maxBlocks : T8_MAX_BLOCKS);
-        if (pk.wide) hipLaunchKernelGGL(k_extend_first_packets64, dim3(gp), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, pk);
+        if (pk.wide && pk.precull) hipLaunchKernelGGL(k_extend_first_packets64<true>, dim3(gp), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, pk);
+        else if (pk.wide) hipLaunchKernelGGL(k_extend_first_packets64<false>, dim3(gp), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, pk);
         else hipLaunchKernelGGL(k_extend_first_packets, dim3(gp), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, countPtr, wc, pk);
         hipLaunchKernelGGL(k_extend_first_listed, dim3(g), dim3(T8_BLOCK), 0, st, k.sc, pool, fv, pk, wc, aux, rpc);
     } else
@@ -1255,19 +1259,22 @@ __global__ void __launch_bounds__(T8_BLOCK, T8_EXTEND_MIN_BLOCKS) k_route_packet
     auto commit = [&](uint p, const HitInfo& h) { pool.hit[p] = make_uint4(asuint(h.t), h.prim, asuint(h.u), asuint(h.v)); atomicAdd(committed, 1u); };
     traverse8_packets(sc, *countPtr, stack, mineUV, form, commit, pk, &wc->overflow);
 }
-// ... and k_extend_first_packets64 for stored rays (pk.wide)
+// ... and k_extend_first_packets64 for stored rays (pk.wide), with or without the interval test (pk.precull)
+template <bool PRECULL>
 __global__ void __launch_bounds__(T8_BLOCK, T8_PACKET64_MIN_BLOCKS) k_route_packets64(DeviceScene sc, PathPool pool, const uint* __restrict__ countPtr, WaveCounters* wc, FirstPackets pk, uint* committed) {
     __shared__ uint2 stack[(T8_BLOCK / 64u) * T8_PACKET_STACK];
+    __shared__ __attribute__((aligned(16))) float interval[PRECULL ? (T8_BLOCK / 64u) * T8_PACKET_INTERVAL_WORDS : 4u];
     auto form = [&](uint i, float3& o, float3& d) {
         const uint4 a = pool.s0[i], b = pool.s1[i];
         o = make_float3(asfloat(a.x), asfloat(a.y), asfloat(a.z)); d = make_float3(asfloat(b.x), asfloat(b.y), asfloat(b.z));
     };
     auto commit = [&](uint p, const HitInfo& h) { pool.hit[p] = make_uint4(asuint(h.t), h.prim, asuint(h.u), asuint(h.v)); atomicAdd(committed, 1u); };
-    traverse8_packets64(sc, *countPtr, stack, form, commit, pk, &wc->overflow);
+    traverse8_packets64<PRECULL>(sc, *countPtr, stack, interval, form, commit, pk, &wc->overflow);
 }
 void launch_route_packets(const DeviceScene& sc, PathPool pool, const uint* countPtr, uint count, WaveCounters* wc, FirstPackets pk, uint* committed, uint maxBlocks, hipStream_t st) {
     const uint gp = grid_for(count, (T8_BLOCK / 64u) * (pk.wide ? T8_PACKET64_RAYS : T8_PACKET_RAYS), (maxBlocks && maxBlocks < T8_MAX_BLOCKS) ? maxBlocks : T8_MAX_BLOCKS);      // (launch_extend_first's packet grid)
-    if (pk.wide) hipLaunchKernelGGL(k_route_packets64, dim3(gp), dim3(T8_BLOCK), 0, st, sc, pool, countPtr, wc, pk, committed);
+    if (pk.wide && pk.precull) hipLaunchKernelGGL(k_route_packets64<true>, dim3(gp), dim3(T8_BLOCK), 0, st, sc, pool, countPtr, wc, pk, committed);
+    else if (pk.wide) hipLaunchKernelGGL(k_route_packets64<false>, dim3(gp), dim3(T8_BLOCK), 0, st, sc, pool, countPtr, wc, pk, committed);
     else hipLaunchKernelGGL(k_route_packets, dim3(gp), dim3(T8_BLOCK), 0, st, sc, pool, countPtr, wc, pk, committed);
 }
 #endif

@@ -15,6 +15,7 @@
 #include <functional>
 #include <numeric>
 #include <vector>
+#include "../../rtxpt_amd/csrc/pt_packet_precull.h"      // the packet's interval test (LAB_PACKET's column "kept per node")
 #include <omp.h>
 #include "../../rtxpt_amd/csrc/pt_build_sah.h"      // LAB_PRODUCT: the product's host builder (link rtxpt_amd/csrc/pt_build_sah.cpp)
 #include "../../rtxpt_amd/csrc/pt_build_reinsert.h" // LAB_PARALLEL_REINS: the product's device-side optimiser, run on the CPU
@@ -464,11 +465,16 @@ static inline float frand(uint32_t& s) { s ^= s << 13; s ^= s >> 17; s ^= s << 5
 // LAB_PACKET: a packet of rays on ONE shared stack. A child is visited if any ray's own slab test (against its own best t) enters it; the children are ordered, and a stack
 // entry is culled, by the minimum entry distance over the rays that entered it — an entry is dropped only when that minimum lies beyond the largest best t of the packet. Every
 // ray tests every triangle of a visited leaf. Returns node steps, leaf steps and the children entered over all node steps (what a per-child reduction over the packet pays for).
-struct PacketSteps { int nodes = 0, leaves = 0, entered = 0; };
+struct PacketSteps { int nodes = 0, leaves = 0, entered = 0, kept = 0; };      // kept: the children the packet's interval test (pt_packet_precull.h) leaves to the per-ray tests, over all node steps
 static PacketSteps trace8_packet(const Bvh8& w, const std::vector<Ray>& rs, std::vector<Hit>& hits) {
     const int R = (int)rs.size(); PacketSteps ps; hits.assign(R, Hit{1e30f, -1});
     std::vector<V3> id(R); for (int i = 0; i < R; i++) id[i] = {1.f / rs[i].d.x, 1.f / rs[i].d.y, 1.f / rs[i].d.z};
     struct E { int ref; float t; }; std::vector<E> stack; int cur = 0; bool have = true;
+    // the packet's interval, as traverse8_packets64 forms it once per packet: the extremes of the origins and of the reciprocals; no test where the reciprocals straddle zero
+    T8PacketInterval pi; V3 omn = rs[0].o, omx = rs[0].o, imn = id[0], imx = id[0];
+    for (int i = 1; i < R; i++) { omn = vmin(omn, rs[i].o); omx = vmax(omx, rs[i].o); imn = vmin(imn, id[i]); imx = vmax(imx, id[i]); }
+    const bool culls = t8_packet_interval(omn.x, omn.y, omn.z, omx.x, omx.y, omx.z, imn.x, imn.y, imn.z, imx.x, imx.y, imx.z, pi);
+    const bool ngx = imx.x < 0.f, ngy = imx.y < 0.f, ngz = imx.z < 0.f;
     while (true) {
         if (!have) { float far = 0.f; for (int i = 0; i < R; i++) far = std::max(far, hits[i].t);
             bool got = false; while (!stack.empty()) { E e = stack.back(); stack.pop_back(); if (e.t <= far) { cur = e.ref; got = true; break; } } if (!got) break; }
@@ -484,6 +490,9 @@ static PacketSteps trace8_packet(const Bvh8& w, const std::vector<Ray>& rs, std:
                     float tf = std::min(std::min(std::max(tx1, tx2), std::max(ty1, ty2)), std::min(std::max(tz1, tz2), hits[i].t));
                     if (tn <= tf) tmin = std::min(tmin, tn); }
                 if (tmin < 3e38f) hs[nh++] = {n.ref[k], tmin};
+                float far = 0.f; for (int i = 0; i < R; i++) far = std::max(far, hits[i].t);
+                const bool keeps = !culls || t8_packet_keeps(ngx ? b.mx.x : b.mn.x, ngx ? b.mn.x : b.mx.x, ngy ? b.mx.y : b.mn.y, ngy ? b.mn.y : b.mx.y, ngz ? b.mx.z : b.mn.z, ngz ? b.mn.z : b.mx.z, pi, 0.f, far);
+                if (keeps) ps.kept++; else if (tmin < 3e38f) { fprintf(stderr, "the interval test dropped a child that a ray enters\n"); exit(1); }
             }
             ps.entered += nh;
             if (!nh) continue;
@@ -501,11 +510,11 @@ static PacketSteps trace8_packet(const Bvh8& w, const std::vector<Ray>& rs, std:
 static void packet_table(const Bvh8& w, int packets) {
     const V3 pos{4.0f, 1.7f, 20.0f}, dir = normalize(V3{1.0f, 0.12f, 0.05f}), up{0, 1, 0}; const V3 U = normalize(cross(dir, up)), Vv = normalize(cross(U, dir));
     const float th = std::tan(0.5f * 1.0471975512f), asp = 16.f / 9.f; const int W = 3840, H = 2160, spp = 4;
-    printf("%-28s %12s %12s %18s %16s %17s %10s | single ray: nodes leaves | mismatches\n", "packet", "node steps", "leaf steps", "entered per node", "over 64 steps %", "over 128 steps %", "longest");
+    printf("%-28s %12s %12s %18s %15s %16s %17s %10s | single ray: nodes leaves | mismatches\n", "packet", "node steps", "leaf steps", "entered per node", "kept per node", "over 64 steps %", "over 128 steps %", "longest");
     const int shapes[4][2] = {{8, 1}, {4, 2}, {2, 2}, {8, 2}};
     for (auto& sh : shapes) {
         const int px = sh[0], py = sh[1]; uint32_t s = 4242u;
-        uint64_t N = 0, L = 0, E = 0, over = 0, over128 = 0, sn = 0, sl = 0, rays = 0, mism = 0; int longest = 0;
+        uint64_t N = 0, L = 0, E = 0, K = 0, over = 0, over128 = 0, sn = 0, sl = 0, rays = 0, mism = 0; int longest = 0;
         for (int p = 0; p < packets; p++) {
             const int x0 = (int)(frand(s) * (W / px)) * px, y0 = (int)(frand(s) * (H / py)) * py;
             std::vector<Ray> rs;
@@ -513,11 +522,11 @@ static void packet_table(const Bvh8& w, int packets) {
                 const float fx = ((x0 + x + frand(s)) / W) * 2 - 1, fy = 1 - ((y0 + y + frand(s)) / H) * 2;
                 rs.push_back(Ray{pos, normalize(dir + U * (fx * th * asp) + Vv * (fy * th))}); }
             std::vector<Hit> hp; const PacketSteps ps = trace8_packet(w, rs, hp);
-            N += ps.nodes; L += ps.leaves; E += ps.entered; if (ps.nodes + ps.leaves > 64) over++; if (ps.nodes + ps.leaves > 128) over128++; longest = std::max(longest, ps.nodes + ps.leaves);
+            N += ps.nodes; L += ps.leaves; E += ps.entered; K += ps.kept; if (ps.nodes + ps.leaves > 64) over++; if (ps.nodes + ps.leaves > 128) over128++; longest = std::max(longest, ps.nodes + ps.leaves);
             for (size_t i = 0; i < rs.size(); i++) { Ctr c; Hit h1 = trace8(w, rs[i], c); sn += c.nodes; sl += c.leaves; rays++; if (h1.prim != hp[i].prim) mism++; }      // (ties in t go to the visiting order here: not the product's rule)
         }
         char nm[64]; snprintf(nm, 64, "%d x %d px x %d (%d rays)", px, py, spp, px * py * spp);
-        printf("%-28s %12.1f %12.1f %18.2f %16.1f %17.2f %10d | %18.1f %6.1f | %.3f %%\n", nm, (double)N / packets, (double)L / packets, (double)E / (N ? N : 1), 100.0 * over / packets, 100.0 * over128 / packets, longest, (double)sn / rays, (double)sl / rays, 100.0 * mism / rays);
+        printf("%-28s %12.1f %12.1f %18.2f %15.2f %16.1f %17.2f %10d | %18.1f %6.1f | %.3f %%\n", nm, (double)N / packets, (double)L / packets, (double)E / (N ? N : 1), (double)K / (N ? N : 1), 100.0 * over / packets, 100.0 * over128 / packets, longest, (double)sn / rays, (double)sl / rays, 100.0 * mism / rays);
         fflush(stdout);
     }
 }
