@@ -717,6 +717,56 @@ int32_t pt_get_adaptive_state(pt_context* ctx, uint32_t* sampleCounts, float* ha
  * (PT_ERROR_NOT_READY without an adaptive render of this frame size, PT_ERROR_INVALID_ARGUMENT for a capacity below the count). */
 int32_t pt_get_adaptive_active(pt_context* ctx, uint32_t* pixels, uint32_t capacity);
 
+/* A denoiser for reference mode (docs/WIDENING.md N13): the seam is the reference's "Photo mode screenshot" (SampleUI.cpp:926-932, Sample::DenoisedScreenshot,
+ * Sample.cpp:2782-2815), which sends the accumulated picture through an external tool because there is "no built-in denoiser available in 'Reference' mode". The filter is ours: a
+ * dual-buffer non-local-means filter (Rousselle, Knaus, Zwicker 2012) over the two means an adaptive render leaves — A, the mean of a pixel's samples (the accumulation buffer),
+ * and H, the mean of its even-indexed ones (pt_get_adaptive_state). No guide buffers, no change to any path tracing launch. Per pixel, one binary32 operation at a time in
+ * the written order (no contraction, / correctly rounded); the order of the additions is part of the interface. All coordinates are clamped to the frame.
+ *   prepare   O = (A + A) - H per colour channel: the mean of the odd-indexed samples.  valid(p): every one of A.xyz, H.xyz, O.xyz is finite with |.| <= maxRadiance.
+ *             H' = H, O' = O for a valid pixel, both 0 for an invalid one.  s = ((H' - O') * (H' - O')) * 0.5 per channel.
+ *             V = the 3 x 3 box mean of s: rows (s[x-1] + s[x]) + s[x+1], columns (row[y-1] + row[y]) + row[y+1], then / 9.0f — the variance of one half, shared by both directions.
+ *   distance  for each search offset o = (ox, oy), oy outer and ox inner, both from -r to r, and for a source U of {H', O'}, per channel
+ *             e_c(x) = ((U(x) - U(x+o))^2 - alpha * (V(x) + min(V(x), V(x+o)))) / (epsilon + (k*k) * (V(x) + V(x+o)));   e = (e_r + e_g) + e_b
+ *   patch     row(x, y) = e(x-f, y) + e(x-f+1, y) + ... + e(x+f, y), left to right;  S(x, y) = row(x, y-f) + ... + row(x, y+f), top to bottom;  D2 = S / (float)(3 (2f+1)^2).
+ *             (e at a clamped position is that pixel's own e: it pairs the clamped pixel with its own clamped neighbour.)
+ *   weight    t = max(1 - max(D2, 0) * 0.25f, 0);  t2 = t * t;  w = t2 * t2 — a polynomial stand-in for exp(-D2);  w = 0 where x+o is outside the frame or invalid.
+ *             Offset 0 gives a valid pixel w = 1, so its weight sum is >= 1.
+ *   sums      from 0, in offset order:  sumW += w;  sumC += w * Other(x+o) — weights taken from H' average O', weights taken from O' average H'.
+ *   result    FO = sumC_H / sumW_H,  FH = sumC_O / sumW_O (the subscript: where the weights came from);  D.xyz = (FO + FH) * 0.5 for a valid pixel, A.xyz's bytes for an
+ *             invalid one;  D.w = A.w.
+ * Limits: the context must own the whole frame; no feature guides (albedo, normal); a single filter scale; the variance comes from two halves only; the weight is a
+ * polynomial, not exp. */
+typedef struct PtAccumDenoiseParams {
+    uint32_t searchRadius;                   /* r: 1 .. 8 */
+    uint32_t patchRadius;                    /* f: 0 .. 3 */
+    float    k;                              /* [0.05, 4]: the distance's scale */
+    float    alpha;                          /* [0, 4]: how much of the noise's own squared difference is subtracted */
+    float    epsilon;                        /* [1e-20, 1] */
+    float    maxRadiance;                    /* (0, 1e15]: a pixel with a larger or non-finite channel passes through and gives no weight */
+} PtAccumDenoiseParams;
+/* searchRadius 5, patchRadius 2, k 0.45, alpha 1, epsilon 1e-10, maxRadiance 65504: starting values that nobody has measured against pictures yet, not a recommendation. */
+int32_t pt_accum_denoise_default_params(PtAccumDenoiseParams* out);
+/* Filters what the last pt_render_adaptive left (threshold 0 gives the bits of pt_render(0, maxSamples), so plain fixed-count frames are covered) into a picture of the
+ * context's own; the radiance buffer, the even-sample buffer and the counts are only read. gpuMs (may be NULL): the device time of the two launches.
+ * PT_ERROR_INVALID_ARGUMENT for a parameter out of range or NaN; PT_ERROR_UNSUPPORTED on a context that owns only a shard of the frame (PtDeviceDesc.shardCount > 1: the filter
+ * reads neighbours and the even-sample buffer is not gathered); PT_ERROR_NOT_READY where pt_get_adaptive_state gives it, and once the accumulation has been reset since
+ * (pt_reset_accumulation, pt_resize, pt_animate*, a changed texture filter) — the denoised picture is dropped at the same moments, and by the next pt_render_adaptive. */
+int32_t pt_accum_denoise(pt_context* ctx, const PtAccumDenoiseParams* params, float* gpuMs);
+/* The same launches over two tightly packed host pictures of the frame size (width x height x 4 floats: A and H), uploaded to buffers of the call's own: the accumulation
+ * buffer and the adaptive state are not touched, and only pt_resize is needed (any shard layout). For a host that accumulates elsewhere, and for the tests. */
+int32_t pt_accum_denoise_host_inputs(pt_context* ctx, const PtAccumDenoiseParams* params, const float* meanRgba32f, const float* halfRgba32f, float* gpuMs);
+/* The denoised picture (RGBA32F, the frame size) of the last of the two calls: on the device / read back. PT_ERROR_NOT_READY without one. */
+int32_t pt_accum_denoised_device_buffer(pt_context* ctx, void** devicePtr, size_t* rowPitchBytes);
+int32_t pt_get_accum_denoised(pt_context* ctx, float* rgba32f);
+/* What the prepare launch of that call left, for tests; any pointer may be NULL. oddRgb: O', width x height x 3; variance: V, width x height x 3; validMask: width x height
+ * bytes, 1 for a valid pixel. */
+int32_t pt_get_accum_denoise_state(pt_context* ctx, float* oddRgb, float* variance, uint8_t* validMask);
+/* The display tail on the denoised picture: pt_tonemap's and pt_average_luminance's kernels pointed at it, and pt_bloom's pass with it as the source — the bloomed picture is
+ * the one pt_get_bloomed, pt_tonemap_bloomed and pt_average_luminance_bloomed read. PT_ERROR_NOT_READY without a denoised picture. */
+int32_t pt_tonemap_accum_denoised(pt_context* ctx, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes);
+int32_t pt_average_luminance_accum_denoised(pt_context* ctx, float* avgLuminance);
+int32_t pt_bloom_accum_denoised(pt_context* ctx, const PtBloomParams* params, float* gpuMs);
+
 /* RTXPT `.material.json` (the part the reference tree defines completely): PTMaterial::Read + PTMaterial::FillData
    (Rtxpt/Materials/MaterialsBaker.cpp:150-259, 516-591; defaults Rtxpt/Materials/MaterialsBaker.h:126-193). Host only, no context needed.
    textureWords[5]: packed PTMaterialData texture words (baseLOD << 24 | mipLevels << 16 | texture index, GetBindlessTextureIndex :487-509) of the

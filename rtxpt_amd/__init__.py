@@ -45,6 +45,8 @@ EXPORTS = [
     "pt_taa_upscale_default_params", "pt_taa_upscale", "pt_upscaled_size", "pt_upscaled_device_buffer", "pt_get_upscaled", "pt_bloom_upscaled", "pt_get_upscaled_bloomed",
     "pt_tonemap_upscaled", "pt_average_luminance_upscaled", "pt_upscale_tex_lod_bias",
     "pt_adaptive_default_params", "pt_render_adaptive", "pt_get_adaptive_state", "pt_get_adaptive_active",
+    "pt_accum_denoise_default_params", "pt_accum_denoise", "pt_accum_denoise_host_inputs", "pt_accum_denoised_device_buffer", "pt_get_accum_denoised",
+    "pt_get_accum_denoise_state", "pt_tonemap_accum_denoised", "pt_average_luminance_accum_denoised", "pt_bloom_accum_denoised",
     "pt_comm_unique_id", "pt_comm_init", "pt_comm_destroy", "pt_gather", "pt_shard_layout", "pt_gather_host", "pt_neeat_exchange_host",
 ]
 TEST_HOOK_EXPORTS = ["pt_probe", "pt_get_inert_terminal", "pt_get_bvh8", "pt_trace_route"]      # include/mi355pt_testhooks.h: libmi355pt_testhooks.so only
@@ -875,6 +877,22 @@ def adaptive_default_params(lib=None, **overrides):
     return out
 
 
+# PtAccumDenoiseParams (include/mi355pt.h): the reference-mode denoiser's parameters (pt_accum_denoise)
+ACCUM_DENOISE_PARAMS_DTYPE = np.dtype([("searchRadius", "<u4"), ("patchRadius", "<u4"), ("k", "<f4"), ("alpha", "<f4"), ("epsilon", "<f4"), ("maxRadiance", "<f4")])
+assert ACCUM_DENOISE_PARAMS_DTYPE.itemsize == 24
+
+
+def accum_denoise_default_params(lib=None, **overrides):
+    """pt_accum_denoise_default_params: searchRadius 5, patchRadius 2, k 0.45, alpha 1, epsilon 1e-10, maxRadiance 65504 (starting values, unmeasured); keywords override"""
+    L = lib or load_library()
+    out = np.zeros((), ACCUM_DENOISE_PARAMS_DTYPE)
+    f = L.pt_accum_denoise_default_params; f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_int32
+    r = f(_p(out))
+    if r != PT_OK: raise PtError(r, "pt_accum_denoise_default_params")
+    for k, v in overrides.items(): out[k] = v
+    return out
+
+
 class PathTracer:
     """One pt_context (one GPU). Method names follow the C-ABI; the call order follows Sample::Render."""
 
@@ -1463,6 +1481,76 @@ class PathTracer:
             r = f(self.h, _p(out), n)
             if r < 0: self._chk(-r, "pt_get_adaptive_active")
         return out
+
+    def _accum_denoise_params(self, params):
+        dp = np.ascontiguousarray(accum_denoise_default_params(self.L) if params is None else params); assert dp.dtype == ACCUM_DENOISE_PARAMS_DTYPE
+        return dp
+
+    def accum_denoise(self, params=None, timed=False):
+        """pt_accum_denoise: the dual-buffer non-local-means filter over what the last render_adaptive left (the radiance buffer and the even-sample means), into a picture
+        of the context's own (ACCUM_DENOISE_PARAMS_DTYPE; defaults if None). Returns accum_denoised(), or with timed (accum_denoised, the two launches' event-timed
+        milliseconds). Refused on a rank of a sharded layout."""
+        dp = self._accum_denoise_params(params); ms = ctypes.c_float(0.0)
+        f = self.L.pt_accum_denoise; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(dp), ctypes.byref(ms) if timed else None), "pt_accum_denoise")
+        return (self.accum_denoised(), float(ms.value)) if timed else self.accum_denoised()
+
+    def accum_denoise_host_inputs(self, mean, half, params=None, timed=False):
+        """pt_accum_denoise_host_inputs: accum_denoise()'s launches over two host pictures [h, w, 4] f32 (the mean of all samples, the mean of the even-indexed ones); neither
+        the radiance buffer nor the adaptive state is touched, and only resize() is needed"""
+        dp = self._accum_denoise_params(params); ms = ctypes.c_float(0.0)
+        a = np.ascontiguousarray(mean, np.float32); hh = np.ascontiguousarray(half, np.float32)
+        assert a.shape == hh.shape == (self.height, self.width, 4), (a.shape, hh.shape)
+        f = self.L.pt_accum_denoise_host_inputs; f.argtypes = [ctypes.c_void_p] * 5; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(dp), _p(a), _p(hh), ctypes.byref(ms) if timed else None), "pt_accum_denoise_host_inputs")
+        return (self.accum_denoised(), float(ms.value)) if timed else self.accum_denoised()
+
+    def accum_denoised(self):
+        """pt_get_accum_denoised: the denoised picture of the last accum_denoise / accum_denoise_host_inputs, [h, w, 4] f32"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        f = self.L.pt_get_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out)), "pt_get_accum_denoised")
+        return out
+
+    def accum_denoised_device_buffer(self):
+        """pt_accum_denoised_device_buffer: (device pointer, row pitch in bytes) of the denoised picture"""
+        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
+        f = self.L.pt_accum_denoised_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_accum_denoised_device_buffer")
+        return d.value, int(pitch.value)
+
+    def accum_denoise_state(self):
+        """pt_get_accum_denoise_state: what the prepare launch of the last denoiser call left — odd [h, w, 3] f32 (the staged odd-sample means), variance [h, w, 3] f32 and
+        valid [h, w] u8"""
+        h, w = self.height, self.width
+        out = dict(odd=np.zeros((h, w, 3), np.float32), variance=np.zeros((h, w, 3), np.float32), valid=np.zeros((h, w), np.uint8))
+        f = self.L.pt_get_accum_denoise_state; f.argtypes = [ctypes.c_void_p] * 4; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out["odd"]), _p(out["variance"]), _p(out["valid"])), "pt_get_accum_denoise_state")
+        return out
+
+    def tonemap_accum_denoised(self, params=None):
+        """pt_tonemap_accum_denoised: tonemap() over the denoised picture instead of the radiance buffer -> (H, W, 4) uint8"""
+        t = default_tonemap() if params is None else params
+        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        f = self.L.pt_tonemap_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_accum_denoised")
+        return out
+
+    def average_luminance_accum_denoised(self):
+        """pt_average_luminance_accum_denoised: average_luminance() of the denoised picture"""
+        v = ctypes.c_float(0.0)
+        f = self.L.pt_average_luminance_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(v)), "pt_average_luminance_accum_denoised")
+        return float(v.value)
+
+    def bloom_accum_denoised(self, params=None, timed=False):
+        """pt_bloom_accum_denoised: bloom()'s pass with the denoised picture as the source; the result is bloomed()'s picture, which tonemap_bloomed() and
+        average_luminance_bloomed() read. Returns bloomed(), or with timed (bloomed, the pass's event-timed milliseconds)"""
+        bp = np.ascontiguousarray(bloom_default_params(self.L) if params is None else params); assert bp.dtype == BLOOM_PARAMS_DTYPE
+        ms = ctypes.c_float(0.0)
+        f = self.L.pt_bloom_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(bp), ctypes.byref(ms) if timed else None), "pt_bloom_accum_denoised")
+        return (self.bloomed(), float(ms.value)) if timed else self.bloomed()
 
     def radiance(self):
         ptr = ctypes.POINTER(ctypes.c_float)()

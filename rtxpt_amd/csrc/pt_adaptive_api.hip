@@ -75,7 +75,7 @@ int32_t pt_render_adaptive(pt_context* c, const PtAdaptiveParams* params, PtAdap
     const size_t N = (size_t)c->width * c->height, NB = (size_t)blocks_x(c) * blocks_y(c);
     PT_CHECK_HIP(c, A.dHalf.resize(N)); PT_CHECK_HIP(c, A.dCounts.resize(N)); PT_CHECK_HIP(c, A.dBlockError.resize(NB));
     // a new accumulation: the first sample of a pixel overwrites both means (blend 1), the maps start from zero for the pixels of other shards' sake
-    A.stateValid = false; A.perPixel = true; c->accumCount = 0;
+    A.stateValid = false; A.perPixel = true; c->accumCount = 0; accum_denoise_drop(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(A.dHalf.p, 0, sizeof(ptk::float4) * N, c->stream));
     PT_CHECK_HIP(c, hipMemsetAsync(A.dCounts.p, 0, sizeof(uint) * N, c->stream)); PT_CHECK_HIP(c, hipMemsetAsync(A.dBlockError.p, 0, sizeof(float) * NB, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));

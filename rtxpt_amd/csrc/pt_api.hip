@@ -658,7 +658,7 @@ int32_t pt_destroy(pt_context* c) {
     if (c->comm && g_rccl.lib) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
     c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
-    relax_free(c); taa_free(c); bloom_free(c); taau_free(c); adaptive_free(c);
+    relax_free(c); taa_free(c); bloom_free(c); taau_free(c); adaptive_free(c); accum_denoise_free(c);
     skin_drop(c); for (int e = 0; e < 2; e++) if (c->skinEvents[e]) (void)hipEventDestroy(c->skinEvents[e]);
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
     c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
@@ -1041,7 +1041,7 @@ int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
     if (!c || !w || !h || w > 65535 || h > 65535) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad size");
     (void)hipSetDevice(c->device);
     if (w != c->width || h != c->height) { relax_drop_history(c); taa_drop_history(c); bloom_drop(c); taau_drop_history(c); }
-    c->width = w; c->height = h; c->accumCount = 0; c->adaptive.perPixel = false; c->fbSamples = 0;
+    c->width = w; c->height = h; c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c); c->fbSamples = 0;
     build_shards(c); adaptive_drop(c);
     PT_CHECK_HIP(c, c->dAccum.resize((size_t)w * h));
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)w * h, c->stream));
@@ -1052,7 +1052,7 @@ int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
 int32_t pt_reset_accumulation(pt_context* c) {
     if (!c || !c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
     (void)hipSetDevice(c->device);
-    c->accumCount = 0; c->adaptive.perPixel = false;
+    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     return PT_OK;
 }
@@ -1151,7 +1151,7 @@ int32_t pt_animate_ranges(pt_context* c, const PtInstanceDesc* inst, uint32_t nI
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); if (rebuild) c->buildMs = ms; else c->refitMs = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     const bool lightsWereDirty = c->lightsDirty;      // something besides the geometry changed since the last bake (environment, analytic lights, NEE settings)
     c->lightsDirty = true;                    // emissive triangle lights move with the geometry (Sample.cpp:1170-1198)
-    c->accumCount = 0; c->adaptive.perPixel = false;                        // any scene change resets accumulation in reference mode
+    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);                        // any scene change resets accumulation in reference mode
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     // geometry moved, nothing else: environment lights kept, emissive re-bake + weights + proxy table on the device
     const int32_t rb = bake_lights(c, !lightsWereDirty);
@@ -1170,7 +1170,7 @@ int32_t pt_animate_normals(pt_context* c, const uint32_t* normals, const uint32_
     if (tangents) { memcpy(c->tangents.data(), tangents, 4 * (size_t)nVerts); PT_CHECK_HIP(c, c->dTangents.upload(c->tangents, c->stream)); }
     refresh_scene_view(c);
     launch_shade_tris(c->dsc, 0u, c->numTris, c->dShadeTris.p, c->stream);      // the shading records hold the packed vertex normals and tangents
-    c->accumCount = 0; c->adaptive.perPixel = false;
+    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -1260,7 +1260,7 @@ int32_t pt_animate_skinned(pt_context* c, const PtInstanceDesc* inst, uint32_t n
     ms = 0; (void)hipEventElapsedTime(&ms, c->skinEvents[0], c->skinEvents[1]); c->skinMs = ms;
     const bool lightsWereDirty = c->lightsDirty;
     c->lightsDirty = true;                    // emissive triangle lights move with the geometry
-    c->accumCount = 0; c->adaptive.perPixel = false;
+    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     return bake_lights(c, !lightsWereDirty);
 }

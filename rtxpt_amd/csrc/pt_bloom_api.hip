@@ -63,9 +63,15 @@ int32_t pt_bloom(pt_context* c, const PtBloomParams* params, uint32_t source, fl
     if (!params_ok(*params)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bloom parameters out of range (radius in [0, 64], intensity in [0, 1], maxRadiance > 0, all finite)");
     if (source == 0u) { if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first"); }
     else { int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r; }
+    return bloom_run(c, params, source == 0u ? c->dAccum.p : c->dTaa[c->taaSide].p, gpuMs);
+}
+
+}
+
+int32_t bloom_run(pt_context* c, const PtBloomParams* params, const ptk::float4* src, float* gpuMs) {
+    if (!params_ok(*params)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bloom parameters out of range (radius in [0, 64], intensity in [0, 1], maxRadiance > 0, all finite)");
     (void)hipSetDevice(c->device);
     const size_t N = (size_t)c->width * c->height, NQ = (size_t)bloom_reduced(c->width) * bloom_reduced(c->height);
-    const ptk::float4* src = source == 0u ? c->dAccum.p : c->dTaa[c->taaSide].p;
     const bool skipped = !(params->enable && params->intensity > 0.0f && params->radius > 0.0f);      // Sample.cpp:1834
     BloomTaps K;
     if (!skipped && !taps(params->radius, K)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bloom radius");
@@ -84,6 +90,8 @@ int32_t pt_bloom(pt_context* c, const PtBloomParams* params, uint32_t source, fl
     c->bloomReady = true;
     return PT_OK;
 }
+
+extern "C" {
 
 int32_t pt_bloomed_device_buffer(pt_context* c, void** devicePtr, size_t* pitch) {
     if (!c || !devicePtr) return PT_ERROR_INVALID_ARGUMENT;

@@ -273,6 +273,13 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
         DevBuf<float> dBlockError; DevBuf<ptk::uint2> dFlags, dChunks; uint* hostTotals = nullptr;
         const uint* activePix = nullptr; const ptk::AdaptiveBlock* activeBlk = nullptr; uint activeCount = 0, activeBlocks = 0;
     } adaptive;
+    // the reference-mode denoiser (pt_accum_denoise; pt_accum_denoise.h): the denoised picture and the prepare launch's three outputs (H' with valid(p) in .w, O', V), of
+    // w x h pixels; ready: they are a call's, of this frame size, and the accumulation has not been reset since. dInA / dInH: pt_accum_denoise_host_inputs' copies of the
+    // caller's pictures (dAccum and adaptive.dHalf are never written). events: created by the first call that asks for its time.
+    struct AccumDenoise {
+        DevBuf<ptk::float4> dOut, dStageH, dStageO, dVar, dInA, dInH; uint w = 0, h = 0; bool ready = false;
+        hipEvent_t events[2] = {nullptr, nullptr};
+    } accumDenoise;
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
     std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
@@ -322,12 +329,17 @@ int32_t taa_resolved_ready(pt_context* c);           // PT_OK with a resolved pi
 // ---- pt_bloom_api.hip: the bloomed picture is dropped (resize to another size) / the pass's buffers freed
 void bloom_drop(pt_context* c);
 void bloom_free(pt_context* c);
+// pt_bloom's body for a source picture of the frame size that the caller has checked: `src` bloomed into dBloom (pt_bloom, pt_bloom_accum_denoised)
+int32_t bloom_run(pt_context* c, const PtBloomParams* params, const ptk::float4* src, float* gpuMs);
 // ---- pt_taau_api.hip: the upscaling resolve's history, picture and bloomed picture are dropped (resize to another size, new scene) / its buffers freed
 void taau_drop_history(pt_context* c);
 void taau_free(pt_context* c);
 // ---- pt_adaptive_api.hip: the adaptive state is dropped (resize, new shard lists) / its buffers freed
 void adaptive_drop(pt_context* c);
 void adaptive_free(pt_context* c);
+// ---- pt_accum_denoise_api.hip: the denoised picture is dropped (resize, every reset of the accumulation) / the pass's buffers freed
+void accum_denoise_drop(pt_context* c);
+void accum_denoise_free(pt_context* c);
 // ---- pt_frame.hip
 // pt_render's frame over `numPixels` entries of a device pixel list (x << 16 | y) whose pixels all hold accumBase samples: samples [first, first + count) traced and folded in.
 // pt_render passes the owned list and no round (and the call advances c->accumCount); pt_render_adaptive passes the active list and the round's AdaptiveRound.
