@@ -1182,6 +1182,36 @@ class PathTracer:
         self._chk(f(self.h, _p(prm), _p(dn), _p(ds), 1 if reset_history else 0), "pt_denoise_frame")
         return self.radiance()
 
+    # ---- the display tail (pt_display.hip): one mirror per kind of entry point; `size` is (W, H) of the picture, `selector` the uint32 arguments that pick it
+    def _tonemap(self, name, params, size, *selector):
+        """a tone map entry point (TONEMAP_DTYPE; default_tonemap() if None) -> (H, W, 4) uint8"""
+        t = default_tonemap() if params is None else params
+        out = np.empty((size[1], size[0], 4), dtype=np.uint8)
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_uint32] * len(selector) + [ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(t), *selector, _p(out), out.nbytes), name)
+        return out
+
+    def _average_luminance(self, name, *selector):
+        """an average luminance entry point -> float"""
+        v = ctypes.c_float(0.0)
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * len(selector) + [ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, *selector, ctypes.byref(v)), name)
+        return float(v.value)
+
+    def _device_buffer(self, name):
+        """a device buffer entry point -> (device pointer, row pitch in bytes)"""
+        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), name)
+        return d.value, int(pitch.value)
+
+    def _read_back(self, name, size, capacity=False):
+        """a read-back entry point -> [H, W, 4] f32; capacity: it takes the buffer's size in floats"""
+        out = np.empty((size[1], size[0], 4), np.float32)
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_size_t] * capacity; f.restype = ctypes.c_int32
+        self._chk(f(self.h, _p(out), *([out.size] * capacity)), name)
+        return out
+
     def taa_resolve(self, params=None, reset_history=False, timed=False):
         """pt_taa_resolve: the radiance buffer resolved against the previous call's result (TAA_PARAMS_DTYPE; defaults if None). Returns get_resolved(), or with timed
         (resolved, the kernel's event-timed milliseconds)"""
@@ -1193,25 +1223,15 @@ class PathTracer:
 
     def get_resolved(self):
         """pt_get_resolved: the resolved picture of the last taa_resolve, [h, w, 4] f32, alpha 1"""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        f = self.L.pt_get_resolved; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(out)), "pt_get_resolved")
-        return out
+        return self._read_back("pt_get_resolved", (self.width, self.height))
 
     def resolved_device_buffer(self):
         """pt_resolved_device_buffer: (device pointer, row pitch in bytes) of the resolved picture"""
-        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
-        f = self.L.pt_resolved_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_resolved_device_buffer")
-        return d.value, int(pitch.value)
+        return self._device_buffer("pt_resolved_device_buffer")
 
     def tonemap_resolved(self, params=None):
         """pt_tonemap_resolved: tonemap() over the resolved picture instead of the radiance buffer -> (H, W, 4) uint8"""
-        t = default_tonemap() if params is None else params
-        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
-        f = self.L.pt_tonemap_resolved; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_resolved")
-        return out
+        return self._tonemap("pt_tonemap_resolved", params, (self.width, self.height))
 
     def bloom(self, params=None, source=0, timed=False):
         """pt_bloom: source 0 (the radiance buffer) or 1 (the resolved picture of taa_resolve) bloomed into a third buffer (BLOOM_PARAMS_DTYPE; defaults if None). Returns
@@ -1224,32 +1244,19 @@ class PathTracer:
 
     def bloomed(self):
         """pt_get_bloomed: the bloomed picture of the last bloom, [h, w, 4] f32"""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        f = self.L.pt_get_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(out)), "pt_get_bloomed")
-        return out
+        return self._read_back("pt_get_bloomed", (self.width, self.height))
 
     def bloomed_device_buffer(self):
         """pt_bloomed_device_buffer: (device pointer, row pitch in bytes) of the bloomed picture"""
-        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
-        f = self.L.pt_bloomed_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_bloomed_device_buffer")
-        return d.value, int(pitch.value)
+        return self._device_buffer("pt_bloomed_device_buffer")
 
     def tonemap_bloomed(self, params=None):
         """pt_tonemap_bloomed: tonemap() over the bloomed picture instead of the radiance buffer -> (H, W, 4) uint8"""
-        t = default_tonemap() if params is None else params
-        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
-        f = self.L.pt_tonemap_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_bloomed")
-        return out
+        return self._tonemap("pt_tonemap_bloomed", params, (self.width, self.height))
 
     def average_luminance_bloomed(self):
         """pt_average_luminance_bloomed: average_luminance() of the bloomed picture — the picture the reference's auto exposure measures"""
-        v = ctypes.c_float(0.0)
-        f = self.L.pt_average_luminance_bloomed; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(v)), "pt_average_luminance_bloomed")
-        return float(v.value)
+        return self._average_luminance("pt_average_luminance_bloomed")
 
     def taa_upscale(self, params=None, display=None, jitter=(0.0, 0.0), reset_history=False, timed=False):
         """pt_taa_upscale: the radiance buffer (the frame size is the render size) resolved into the display-size history (TAA_UPSCALE_PARAMS_DTYPE; defaults if None).
@@ -1270,23 +1277,13 @@ class PathTracer:
         self._chk(f(self.h, ctypes.byref(W), ctypes.byref(H)), "pt_upscaled_size")
         return int(W.value), int(H.value)
 
-    def _upscaled_picture(self, name):
-        W, H = self.upscaled_size()
-        out = np.empty((H, W, 4), np.float32)
-        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(out), out.size), name)
-        return out
-
     def upscaled(self):
         """pt_get_upscaled: the upscaled picture of the last taa_upscale, [H, W, 4] f32, alpha 1"""
-        return self._upscaled_picture("pt_get_upscaled")
+        return self._read_back("pt_get_upscaled", self.upscaled_size(), capacity=True)
 
     def upscaled_device_buffer(self):
         """pt_upscaled_device_buffer: (device pointer, row pitch in bytes) of the upscaled picture"""
-        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
-        f = self.L.pt_upscaled_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_upscaled_device_buffer")
-        return d.value, int(pitch.value)
+        return self._device_buffer("pt_upscaled_device_buffer")
 
     def bloom_upscaled(self, params=None, timed=False):
         """pt_bloom_upscaled: bloom()'s pass over the upscaled picture at the display size, into a bloomed picture of its own. Returns upscaled_bloomed(), or with timed
@@ -1299,23 +1296,15 @@ class PathTracer:
 
     def upscaled_bloomed(self):
         """pt_get_upscaled_bloomed: the bloomed picture of the last bloom_upscaled, [H, W, 4] f32"""
-        return self._upscaled_picture("pt_get_upscaled_bloomed")
+        return self._read_back("pt_get_upscaled_bloomed", self.upscaled_size(), capacity=True)
 
     def tonemap_upscaled(self, params=None, bloomed=False):
         """pt_tonemap_upscaled: tonemap() over the upscaled picture, or with bloomed over its bloom -> (H, W, 4) uint8 at the display size"""
-        t = default_tonemap() if params is None else params
-        W, H = self.upscaled_size()
-        out = np.empty((H, W, 4), dtype=np.uint8)
-        f = self.L.pt_tonemap_upscaled; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(t), int(bloomed), _p(out), out.nbytes), "pt_tonemap_upscaled")
-        return out
+        return self._tonemap("pt_tonemap_upscaled", params, self.upscaled_size(), int(bloomed))
 
     def average_luminance_upscaled(self, bloomed=False):
         """pt_average_luminance_upscaled: average_luminance() of the upscaled picture, or with bloomed of its bloom"""
-        v = ctypes.c_float(0.0)
-        f = self.L.pt_average_luminance_upscaled; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, int(bloomed), ctypes.byref(v)), "pt_average_luminance_upscaled")
-        return float(v.value)
+        return self._average_luminance("pt_average_luminance_upscaled", int(bloomed))
 
     def denoise_pass_times(self, enable=True):
         """pt_denoise_pass_times: switches the event timing of denoise_plane's passes on / off and returns the last timed call's milliseconds [temporal, clamp, a-trous 0, 1, ...]"""
@@ -1507,17 +1496,11 @@ class PathTracer:
 
     def accum_denoised(self):
         """pt_get_accum_denoised: the denoised picture of the last accum_denoise / accum_denoise_host_inputs, [h, w, 4] f32"""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        f = self.L.pt_get_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(out)), "pt_get_accum_denoised")
-        return out
+        return self._read_back("pt_get_accum_denoised", (self.width, self.height))
 
     def accum_denoised_device_buffer(self):
         """pt_accum_denoised_device_buffer: (device pointer, row pitch in bytes) of the denoised picture"""
-        d, pitch = ctypes.c_void_p(), ctypes.c_size_t()
-        f = self.L.pt_accum_denoised_device_buffer; f.argtypes = [ctypes.c_void_p] * 3; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(d), ctypes.byref(pitch)), "pt_accum_denoised_device_buffer")
-        return d.value, int(pitch.value)
+        return self._device_buffer("pt_accum_denoised_device_buffer")
 
     def accum_denoise_state(self):
         """pt_get_accum_denoise_state: what the prepare launch of the last denoiser call left — odd [h, w, 3] f32 (the staged odd-sample means), variance [h, w, 3] f32 and
@@ -1530,18 +1513,11 @@ class PathTracer:
 
     def tonemap_accum_denoised(self, params=None):
         """pt_tonemap_accum_denoised: tonemap() over the denoised picture instead of the radiance buffer -> (H, W, 4) uint8"""
-        t = default_tonemap() if params is None else params
-        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
-        f = self.L.pt_tonemap_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap_accum_denoised")
-        return out
+        return self._tonemap("pt_tonemap_accum_denoised", params, (self.width, self.height))
 
     def average_luminance_accum_denoised(self):
         """pt_average_luminance_accum_denoised: average_luminance() of the denoised picture"""
-        v = ctypes.c_float(0.0)
-        f = self.L.pt_average_luminance_accum_denoised; f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.byref(v)), "pt_average_luminance_accum_denoised")
-        return float(v.value)
+        return self._average_luminance("pt_average_luminance_accum_denoised")
 
     def bloom_accum_denoised(self, params=None, timed=False):
         """pt_bloom_accum_denoised: bloom()'s pass with the denoised picture as the source; the result is bloomed()'s picture, which tonemap_bloomed() and
@@ -1576,19 +1552,12 @@ class PathTracer:
 
     def tonemap(self, params=None):
         """pt_tonemap: the accumulation buffer through ToneMappingPass into sRGB RGBA8 -> (H, W, 4) uint8."""
-        t = default_tonemap() if params is None else params
-        out = np.empty((self.height, self.width, 4), dtype=np.uint8)
-        self.L.pt_tonemap.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-        self._chk(self.L.pt_tonemap(self.h, _p(t), _p(out), out.nbytes), "pt_tonemap")
-        return out
+        return self._tonemap("pt_tonemap", params, (self.width, self.height))
 
     # ---- multi-GPU shard plumbing (device pointers come from torch tensors)
     def average_luminance(self):
         """pt_average_luminance: the auto-exposure luminance capture (ToneMappingPasses.cpp:225-288) of the current accumulation buffer."""
-        v = ctypes.c_float(0.0)
-        self.L.pt_average_luminance.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-        self._chk(self.L.pt_average_luminance(self.h, ctypes.byref(v)), "pt_average_luminance")
-        return float(v.value)
+        return self._average_luminance("pt_average_luminance")
 
     def shard_info(self):
         n, b = ctypes.c_uint32(), ctypes.c_size_t()

@@ -1,11 +1,12 @@
 // mi355pt — the reference-mode denoiser's entry points (include/mi355pt.h: pt_accum_denoise_default_params, pt_accum_denoise, pt_accum_denoise_host_inputs,
-// pt_accum_denoised_device_buffer, pt_get_accum_denoised, pt_get_accum_denoise_state, pt_tonemap_accum_denoised, pt_average_luminance_accum_denoised, pt_bloom_accum_denoised):
-// the host side of pt_accum_denoise.h / pt_accum_denoise.hip. The context keeps a picture of its own for the result and the three buffers the prepare launch writes; the
+// pt_accum_denoised_device_buffer, pt_get_accum_denoised, pt_get_accum_denoise_state; the display tail on the denoised picture — pt_tonemap_accum_denoised and
+// pt_average_luminance_accum_denoised in pt_display.hip, pt_bloom_accum_denoised in pt_bloom_api.hip — goes over view_accum_denoised): the host side of pt_accum_denoise.h /
+// pt_accum_denoise.hip. The context keeps a picture of its own for the result and the three buffers the prepare launch writes; the
 // radiance buffer, the even-sample buffer and the counts are only read. Both calls run the same two launches; they differ in where A and H come from.
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include "pt_context.h"
+#include "pt_display.h"
 #include "pt_accum_denoise.h"
 
 using namespace ptk;
@@ -14,8 +15,14 @@ void accum_denoise_drop(pt_context* c) { c->accumDenoise.ready = false; }
 void accum_denoise_free(pt_context* c) {
     pt_context::AccumDenoise& D = c->accumDenoise;
     D.dOut.free(); D.dStageH.free(); D.dStageO.free(); D.dVar.free(); D.dInA.free(); D.dInH.free();
-    for (int s = 0; s < 2; s++) if (D.events[s]) { (void)hipEventDestroy(D.events[s]); D.events[s] = nullptr; }
-    D.w = D.h = 0; accum_denoise_drop(c);
+    D.events.destroy(); D.w = D.h = 0; accum_denoise_drop(c);
+}
+
+int32_t view_accum_denoised(pt_context* c, PictureView* v) {
+    const pt_context::AccumDenoise& D = c->accumDenoise;
+    if (!D.ready || D.w != c->width || D.h != c->height) return fail(c, PT_ERROR_NOT_READY, "no denoised picture of this accumulation yet: pt_accum_denoise");
+    *v = {D.dOut.p, D.w, D.h};
+    return PT_OK;
 }
 
 namespace {
@@ -23,16 +30,11 @@ bool params_ok(const PtAccumDenoiseParams& p) {      // (every comparison is fal
     return p.searchRadius >= 1u && p.searchRadius <= (uint)kAccumDenoiseMaxSearch && p.patchRadius <= (uint)kAccumDenoiseMaxPatch && p.k >= 0.05f && p.k <= 4.0f &&
            p.alpha >= 0.0f && p.alpha <= 4.0f && p.epsilon >= 1e-20f && p.epsilon <= 1.0f && p.maxRadiance > 0.0f && p.maxRadiance <= 1e15f;
 }
-int32_t denoised_ready(pt_context* c) {
-    const pt_context::AccumDenoise& D = c->accumDenoise;
-    if (!D.ready || D.w != c->width || D.h != c->height) return fail(c, PT_ERROR_NOT_READY, "no denoised picture of this accumulation yet: pt_accum_denoise");
-    return PT_OK;
-}
 // the two launches over A and H (device pictures of the frame size), timed if asked
 int32_t run(pt_context* c, const PtAccumDenoiseParams& p, const ptk::float4* A, const ptk::float4* H, float* gpuMs) {
     pt_context::AccumDenoise& D = c->accumDenoise;
     const size_t N = (size_t)c->width * c->height;
-    if (gpuMs) for (int s = 0; s < 2; s++) if (!D.events[s]) PT_CHECK_HIP(c, hipEventCreate(&D.events[s]));
+    if (gpuMs) PT_CHECK_HIP(c, D.events.create());
     // the previous picture is given up only here, after the last host step that can fail without touching it
     accum_denoise_drop(c); D.w = c->width; D.h = c->height;
     PT_CHECK_HIP(c, D.dOut.resize(N)); PT_CHECK_HIP(c, D.dStageH.resize(N)); PT_CHECK_HIP(c, D.dStageO.resize(N)); PT_CHECK_HIP(c, D.dVar.resize(N));
@@ -41,11 +43,11 @@ int32_t run(pt_context* c, const PtAccumDenoiseParams& p, const ptk::float4* A, 
     a.width = (int)c->width; a.height = (int)c->height; a.r = (int)p.searchRadius; a.f = (int)p.patchRadius;
     a.kk = p.k * p.k; a.alpha = p.alpha; a.epsilon = p.epsilon; a.maxRadiance = p.maxRadiance;
     hipStream_t st = c->stream;
-    if (gpuMs) PT_CHECK_HIP(c, hipEventRecord(D.events[0], st));
+    PT_CHECK_HIP(c, D.events.begin(st, gpuMs != nullptr));
     PT_CHECK_HIP(c, launch_accum_denoise(a, st));
-    if (gpuMs) PT_CHECK_HIP(c, hipEventRecord(D.events[1], st));
+    PT_CHECK_HIP(c, D.events.end(st));
     PT_CHECK_HIP(c, hipStreamSynchronize(st)); PT_CHECK_HIP(c, hipGetLastError());
-    if (gpuMs) PT_CHECK_HIP(c, hipEventElapsedTime(gpuMs, D.events[0], D.events[1]));
+    PT_CHECK_HIP(c, D.events.read(gpuMs));
     D.ready = true;
     return PT_OK;
 }
@@ -86,25 +88,22 @@ int32_t pt_accum_denoise_host_inputs(pt_context* c, const PtAccumDenoiseParams* 
 
 int32_t pt_accum_denoised_device_buffer(pt_context* c, void** devicePtr, size_t* pitch) {
     if (!c || !devicePtr) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
-    *devicePtr = c->accumDenoise.dOut.p; if (pitch) *pitch = (size_t)c->width * 16u;
-    return PT_OK;
+    PictureView v; int32_t r = view_accum_denoised(c, &v);
+    return r != PT_OK ? r : display_device_buffer(v, devicePtr, pitch);
 }
 
 int32_t pt_get_accum_denoised(pt_context* c, float* rgba) {
     if (!c || !rgba) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
-    (void)hipSetDevice(c->device);
-    PT_CHECK_HIP(c, hipMemcpy(rgba, c->accumDenoise.dOut.p, 16u * (size_t)c->width * c->height, hipMemcpyDeviceToHost));
-    return PT_OK;
+    PictureView v; int32_t r = view_accum_denoised(c, &v);
+    return r != PT_OK ? r : display_read_back(c, v, rgba, nullptr);
 }
 
 int32_t pt_get_accum_denoise_state(pt_context* c, float* oddRgb, float* variance, uint8_t* validMask) {
     if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
+    PictureView v; int32_t r = view_accum_denoised(c, &v); if (r != PT_OK) return r;
     (void)hipSetDevice(c->device);
     const pt_context::AccumDenoise& D = c->accumDenoise;
-    const size_t N = (size_t)c->width * c->height;
+    const size_t N = (size_t)v.w * v.h;
     std::vector<ptk::float4> t(N);
     if (oddRgb) {
         PT_CHECK_HIP(c, hipMemcpy(t.data(), D.dStageO.p, 16u * N, hipMemcpyDeviceToHost));
@@ -119,46 +118,6 @@ int32_t pt_get_accum_denoise_state(pt_context* c, float* oddRgb, float* variance
         for (size_t i = 0; i < N; i++) validMask[i] = t[i].w != 0.0f ? 1u : 0u;
     }
     return PT_OK;
-}
-
-int32_t pt_tonemap_accum_denoised(pt_context* c, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes) {
-    if (!c || !params || !rgba8) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
-    const size_t n = (size_t)c->width * c->height;
-    if (bytes < n * 4) return fail(c, PT_ERROR_INVALID_ARGUMENT, "rgba8 buffer too small");
-    if (params->toneMapOperator > 5u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "unknown tone map operator");
-    (void)hipSetDevice(c->device);
-    static_assert(sizeof(PtToneMapParams) == sizeof(ptk::ToneMapParams), "tone map parameter layout");
-    ptk::ToneMapParams p; memcpy(&p, params, sizeof(p));
-    DevBuf<uint> d; PT_CHECK_HIP(c, d.resize(n));
-    launch_tonemap(c->accumDenoise.dOut.p, (uint)n, p, d.p, c->stream);      // pt_tonemap's kernel, pointed at the denoised picture
-    PT_CHECK_HIP(c, hipMemcpyAsync(rgba8, d.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    d.free();
-    return PT_OK;
-}
-
-int32_t pt_average_luminance_accum_denoised(pt_context* c, float* avgLuminance) {
-    if (!c || !avgLuminance) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
-    (void)hipSetDevice(c->device);
-    const size_t n = (size_t)ptk::tm_pow2_floor(c->width) * ptk::tm_pow2_floor(c->height);
-    DevBuf<float> d; PT_CHECK_HIP(c, d.resize(2 * n));
-    float* result = nullptr; float logLum = 0.f;
-    launch_average_log_luminance(c->accumDenoise.dOut.p, c->width, c->height, d.p, &result, c->stream);      // pt_average_luminance's kernels, pointed at the denoised picture
-    PT_CHECK_HIP(c, hipMemcpyAsync(&logLum, result, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    d.free();
-    *avgLuminance = exp2f(logLum);                      // ToneMappingPasses.cpp:284
-    return PT_OK;
-}
-
-int32_t pt_bloom_accum_denoised(pt_context* c, const PtBloomParams* params, float* gpuMs) {
-    if (!c || !params) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = denoised_ready(c); if (r != PT_OK) return r;
-    return bloom_run(c, params, c->accumDenoise.dOut.p, gpuMs);      // pt_bloom's body; the bloomed picture is pt_tonemap_bloomed's
 }
 
 }

@@ -1,5 +1,5 @@
 // mi355pt — C-ABI implementation (include/mi355pt.h): context, scene upload, BVH build/refit orchestration, light baking and
-// read-back; the frame drivers (pt_render and the realtime passes) are in pt_frame.hip. Host side of the seam `Sample` implements in the reference
+// read-back; the frame drivers (pt_render and the realtime passes) are in pt_frame.hip, the display tail (pt_tonemap, pt_average_luminance) in pt_display.hip. Host side of the seam `Sample` implements in the reference
 // (Rtxpt/Sample.cpp:1891-2313 Render, :2438-2559 PathTrace, :1464-1556 UpdatePathTracerConstants, :2770-2778 accumulation).
 // There is NO CPU fallback: every entry point that needs the device fails with PT_ERROR_NO_DEVICE / PT_ERROR_HIP.
 #include <cstring>
@@ -46,6 +46,9 @@ void host_convert_texture(const PtTextureDesc& d, HostTexture& t) {
     build_mips(t);
 }
 size_t host_texture_bytes(const HostTexture& t) { size_t n = 0; for (auto& m : t.mips) n += m.size() * sizeof(ptk::float4); return n; }
+
+// the accumulation starts again: no samples, uniform sample counts, and what was derived from the old one (the denoised picture) is gone. The callers clear dAccum.
+void reset_accumulation(pt_context* c) { c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c); }
 
 uint morton2(uint x, uint y) {
     auto part = [](uint v) { v &= 0xFFFF; v = (v | (v << 8)) & 0x00FF00FF; v = (v | (v << 4)) & 0x0F0F0F0F; v = (v | (v << 2)) & 0x33333333; v = (v | (v << 1)) & 0x55555555; return v; };
@@ -1041,7 +1044,7 @@ int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
     if (!c || !w || !h || w > 65535 || h > 65535) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad size");
     (void)hipSetDevice(c->device);
     if (w != c->width || h != c->height) { relax_drop_history(c); taa_drop_history(c); bloom_drop(c); taau_drop_history(c); }
-    c->width = w; c->height = h; c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c); c->fbSamples = 0;
+    c->width = w; c->height = h; reset_accumulation(c); c->fbSamples = 0;
     build_shards(c); adaptive_drop(c);
     PT_CHECK_HIP(c, c->dAccum.resize((size_t)w * h));
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)w * h, c->stream));
@@ -1052,7 +1055,7 @@ int32_t pt_resize(pt_context* c, uint32_t w, uint32_t h) {
 int32_t pt_reset_accumulation(pt_context* c) {
     if (!c || !c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
     (void)hipSetDevice(c->device);
-    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
+    reset_accumulation(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     return PT_OK;
 }
@@ -1151,7 +1154,7 @@ int32_t pt_animate_ranges(pt_context* c, const PtInstanceDesc* inst, uint32_t nI
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); if (rebuild) c->buildMs = ms; else c->refitMs = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     const bool lightsWereDirty = c->lightsDirty;      // something besides the geometry changed since the last bake (environment, analytic lights, NEE settings)
     c->lightsDirty = true;                    // emissive triangle lights move with the geometry (Sample.cpp:1170-1198)
-    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);                        // any scene change resets accumulation in reference mode
+    reset_accumulation(c);                        // any scene change resets accumulation in reference mode
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     // geometry moved, nothing else: environment lights kept, emissive re-bake + weights + proxy table on the device
     const int32_t rb = bake_lights(c, !lightsWereDirty);
@@ -1170,7 +1173,7 @@ int32_t pt_animate_normals(pt_context* c, const uint32_t* normals, const uint32_
     if (tangents) { memcpy(c->tangents.data(), tangents, 4 * (size_t)nVerts); PT_CHECK_HIP(c, c->dTangents.upload(c->tangents, c->stream)); }
     refresh_scene_view(c);
     launch_shade_tris(c->dsc, 0u, c->numTris, c->dShadeTris.p, c->stream);      // the shading records hold the packed vertex normals and tangents
-    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
+    reset_accumulation(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     return PT_OK;
@@ -1260,7 +1263,7 @@ int32_t pt_animate_skinned(pt_context* c, const PtInstanceDesc* inst, uint32_t n
     ms = 0; (void)hipEventElapsedTime(&ms, c->skinEvents[0], c->skinEvents[1]); c->skinMs = ms;
     const bool lightsWereDirty = c->lightsDirty;
     c->lightsDirty = true;                    // emissive triangle lights move with the geometry
-    c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c);
+    reset_accumulation(c);
     PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(ptk::float4) * (size_t)c->width * c->height, c->stream));
     return bake_lights(c, !lightsWereDirty);
 }
@@ -1593,38 +1596,6 @@ int32_t pt_default_tonemap(PtToneMapParams* out, float exposureCompensation, flo
     float manualExposureScale = ((1.f / 100.f) * filmSpeed) / (shutter * fNumber * fNumber);
     float s = exposureScale * manualExposureScale;
     out->colorTransform[0] = s; out->colorTransform[4] = s; out->colorTransform[8] = s;
-    return PT_OK;
-}
-int32_t pt_average_luminance(pt_context* c, float* avgLuminance) {
-    if (!c || !avgLuminance) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    (void)hipSetDevice(c->device);
-    size_t n = (size_t)ptk::tm_pow2_floor(c->width) * ptk::tm_pow2_floor(c->height);
-    DevBuf<float> d; PT_CHECK_HIP(c, d.resize(2 * n));
-    float* result = nullptr; float logLum = 0.f;
-    launch_average_log_luminance(c->dAccum.p, c->width, c->height, d.p, &result, c->stream);
-    PT_CHECK_HIP(c, hipMemcpyAsync(&logLum, result, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    d.free();
-    *avgLuminance = exp2f(logLum);                      // ToneMappingPasses.cpp:284
-    return PT_OK;
-}
-int32_t pt_tonemap(pt_context* c, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes) {
-    if (!c || !params || !rgba8) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    size_t n = (size_t)c->width * c->height;
-    if (bytes < n * 4) return fail(c, PT_ERROR_INVALID_ARGUMENT, "rgba8 buffer too small");
-    if (params->toneMapOperator > 5u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "unknown tone map operator");
-    (void)hipSetDevice(c->device);
-    static_assert(sizeof(PtToneMapParams) == sizeof(ptk::ToneMapParams), "tone map parameter layout");
-    ptk::ToneMapParams p; memcpy(&p, params, sizeof(p));
-    DevBuf<uint> d; PT_CHECK_HIP(c, d.resize(n));
-    launch_tonemap(c->dAccum.p, (uint)n, p, d.p, c->stream);
-    PT_CHECK_HIP(c, hipMemcpyAsync(rgba8, d.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    d.free();
     return PT_OK;
 }
 

@@ -40,6 +40,29 @@ template <typename T> struct DevBuf {
     hipError_t upload(const std::vector<T>& v, hipStream_t st) { return upload(v.data(), v.size(), st); }
     void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
+// the optional event timing of a pass (its gpuMs argument): two events, created by the first call that asks for its time; begin / end record them around the launches,
+// read gives the time between them once the caller has waited for the stream. A call that does not ask creates and records nothing.
+struct EventBracket {
+    hipEvent_t ev[2] = {nullptr, nullptr}; bool on = false;
+    hipError_t create() {      // (on its own: for a pass that wants every step that can fail on the host done before it gives its previous picture up)
+        for (int s = 0; s < 2; s++) if (!ev[s]) { hipError_t e = hipEventCreate(&ev[s]); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    hipError_t begin(hipStream_t st, bool wanted) {
+        on = wanted; if (!on) return hipSuccess;
+        hipError_t e = create();
+        return e != hipSuccess ? e : hipEventRecord(ev[0], st);
+    }
+    hipError_t end(hipStream_t st) { return on ? hipEventRecord(ev[1], st) : hipSuccess; }
+    hipError_t read(float* ms) { return on ? hipEventElapsedTime(ms, ev[0], ev[1]) : hipSuccess; }
+    void destroy() { for (int s = 0; s < 2; s++) if (ev[s]) { (void)hipEventDestroy(ev[s]); ev[s] = nullptr; } }
+};
+// a bloomed picture (pt_bloom_api.hip bloom_run): the result — a buffer of its own, the source is never written — and the two quarter-resolution images of the blur.
+// ready: a bloomed picture of w x h is there.
+struct BloomState {
+    DevBuf<ptk::float4> out, q[2]; uint w = 0, h = 0; bool ready = false; EventBracket timer;
+    void free() { out.free(); q[0].free(); q[1].free(); timer.destroy(); w = h = 0; ready = false; }
+};
 
 struct HostTexture { uint w, h, mipLevels; std::vector<std::vector<ptk::float4>> mips; };
 
@@ -250,19 +273,17 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     bool rxTiming = false; std::vector<float> rxPassMs; std::vector<hipEvent_t> rxEvents;
     // the temporal anti-aliasing resolve (pt_taa_resolve; pt_taa.h): the reference's two feedback buffers; taaSide: the one written last (the resolved picture), the other one
     // is its history. taaFrameSerial: the build pass the resolved picture is of (rxFrameSerial's rule). dnNrdSerial: the build pass of the last pt_denoiser_prepare_nrd — the
-    // relax buffer is read only when it is the current one. taaEvents: created by the first call that asks for its time.
+    // relax buffer is read only when it is the current one.
     DevBuf<ptk::float4> dTaa[2]; uint taaW = 0, taaH = 0, taaSide = 0, taaFrameSerial = 0, dnNrdSerial = 0; bool taaHistory = false, taaResolved = false;
-    hipEvent_t taaEvents[2] = {nullptr, nullptr};
-    // the bloom pass (pt_bloom; pt_bloom.h): the bloomed picture — a third buffer, the source (the radiance buffer or dTaa[taaSide]) is never written — and the two
-    // quarter-resolution images of the blur. bloomReady: a bloomed picture of bloomW x bloomH is there. bloomEvents: created by the first call that asks for its time.
-    DevBuf<ptk::float4> dBloom, dBloomQ[2]; uint bloomW = 0, bloomH = 0; bool bloomReady = false;
-    hipEvent_t bloomEvents[2] = {nullptr, nullptr};
+    EventBracket taaEvents;
+    // the bloom pass (pt_bloom; pt_bloom.h) at the frame size: the source (the radiance buffer, dTaa[taaSide] or the denoised accumulation) is never written
+    BloomState bloom;
     // the temporal upscaling resolve (pt_taa_upscale; pt_taau.h): two display-size buffers that swap as dTaa's do (taauSide: the upscaled picture, the other one its history),
-    // of taauW x taauH pixels, resolved from a frame of taauRenderW x taauRenderH; a serial of its own under taaFrameSerial's rule. The display tail's bloomed picture
-    // (pt_bloom_upscaled) and its two quarter-resolution images: separate from dBloom. taauEvents / taauBloomEvents: created by the first call that asks for its time.
-    DevBuf<ptk::float4> dTaau[2], dTaauBloom, dTaauBloomQ[2]; uint taauW = 0, taauH = 0, taauRenderW = 0, taauRenderH = 0, taauSide = 0, taauFrameSerial = 0;
-    bool taauHistory = false, taauResolved = false, taauBloomReady = false;
-    hipEvent_t taauEvents[2] = {nullptr, nullptr}, taauBloomEvents[2] = {nullptr, nullptr};
+    // of taauW x taauH pixels, resolved from a frame of taauRenderW x taauRenderH; a serial of its own under taaFrameSerial's rule. taauBloom: the display tail's bloomed
+    // picture (pt_bloom_upscaled), of the display size: separate from `bloom`.
+    DevBuf<ptk::float4> dTaau[2]; uint taauW = 0, taauH = 0, taauRenderW = 0, taauRenderH = 0, taauSide = 0, taauFrameSerial = 0;
+    bool taauHistory = false, taauResolved = false;
+    EventBracket taauEvents; BloomState taauBloom;
     // adaptive sampling (pt_render_adaptive; pt_adaptive.h). perPixel: the accumulation buffer holds per-pixel sample counts — pt_render refuses until the accumulation is reset.
     // tableValid: ownedBlocks / dBlkOwned describe the current owned list (its 8 x 8 blocks as runs of the list; built at first use, dropped by pt_resize). stateValid: dHalf,
     // dCounts, dBlockError and the active lists are the last adaptive render's, of this frame size. The active lists: the owned list and its block table before the first
@@ -275,10 +296,10 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     } adaptive;
     // the reference-mode denoiser (pt_accum_denoise; pt_accum_denoise.h): the denoised picture and the prepare launch's three outputs (H' with valid(p) in .w, O', V), of
     // w x h pixels; ready: they are a call's, of this frame size, and the accumulation has not been reset since. dInA / dInH: pt_accum_denoise_host_inputs' copies of the
-    // caller's pictures (dAccum and adaptive.dHalf are never written). events: created by the first call that asks for its time.
+    // caller's pictures (dAccum and adaptive.dHalf are never written).
     struct AccumDenoise {
         DevBuf<ptk::float4> dOut, dStageH, dStageO, dVar, dInA, dInH; uint w = 0, h = 0; bool ready = false;
-        hipEvent_t events[2] = {nullptr, nullptr};
+        EventBracket events;
     } accumDenoise;
     // frame gather (pt_comm_init / pt_gather)
     ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
@@ -325,12 +346,9 @@ void relax_free(pt_context* c);
 // ---- pt_taa_api.hip: the same two hooks for the temporal anti-aliasing resolve
 void taa_drop_history(pt_context* c);
 void taa_free(pt_context* c);
-int32_t taa_resolved_ready(pt_context* c);           // PT_OK with a resolved picture of the current frame size, else PT_ERROR_NOT_READY
-// ---- pt_bloom_api.hip: the bloomed picture is dropped (resize to another size) / the pass's buffers freed
+// ---- pt_bloom_api.hip: the frame-size bloomed picture is dropped (resize to another size) / the pass's buffers freed
 void bloom_drop(pt_context* c);
 void bloom_free(pt_context* c);
-// pt_bloom's body for a source picture of the frame size that the caller has checked: `src` bloomed into dBloom (pt_bloom, pt_bloom_accum_denoised)
-int32_t bloom_run(pt_context* c, const PtBloomParams* params, const ptk::float4* src, float* gpuMs);
 // ---- pt_taau_api.hip: the upscaling resolve's history, picture and bloomed picture are dropped (resize to another size, new scene) / its buffers freed
 void taau_drop_history(pt_context* c);
 void taau_free(pt_context* c);

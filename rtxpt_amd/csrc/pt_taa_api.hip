@@ -1,8 +1,9 @@
 // mi355pt — the temporal anti-aliasing resolve's entry points (include/mi355pt.h: pt_taa_default_params, pt_taa_resolve, pt_resolved_device_buffer, pt_get_resolved,
-// pt_tonemap_resolved, pt_taa_jitter): the host side of pt_taa.h / pt_taa.hip. The context keeps two RGBA32F buffers (the reference's TemporalFeedback1 / 2) and swaps them
-// after every call: the one just written is the resolved picture (ProcessedOutputColor), the other one the history it was resolved against.
+// pt_taa_jitter; pt_tonemap_resolved is in pt_display.hip, over view_resolved): the host side of pt_taa.h / pt_taa.hip. The context keeps two RGBA32F buffers (the
+// reference's TemporalFeedback1 / 2) and swaps them after every call: the one just written is the resolved picture (ProcessedOutputColor), the other one the history it
+// was resolved against.
 #include <cstring>
-#include "pt_context.h"
+#include "pt_display.h"
 #include "pt_taa.h"
 
 using namespace ptk;
@@ -10,13 +11,14 @@ using namespace ptk;
 static_assert(sizeof(::PtTaaParams) == sizeof(ptk::TaaParams), "TAA parameter ABI");
 
 void taa_drop_history(pt_context* c) { c->taaHistory = false; c->taaResolved = false; }
-int32_t taa_resolved_ready(pt_context* c) {
+int32_t view_resolved(pt_context* c, PictureView* v) {
     if (!c->taaResolved || c->taaW != c->width || c->taaH != c->height) return fail(c, PT_ERROR_NOT_READY, "no resolved picture of this frame size yet: pt_taa_resolve");
+    *v = {c->dTaa[c->taaSide].p, c->width, c->height};
     return PT_OK;
 }
 void taa_free(pt_context* c) {
-    for (int s = 0; s < 2; s++) { c->dTaa[s].free(); if (c->taaEvents[s]) { (void)hipEventDestroy(c->taaEvents[s]); c->taaEvents[s] = nullptr; } }
-    c->taaW = c->taaH = 0; taa_drop_history(c);
+    for (int s = 0; s < 2; s++) c->dTaa[s].free();
+    c->taaEvents.destroy(); c->taaW = c->taaH = 0; taa_drop_history(c);
 }
 
 namespace {
@@ -49,7 +51,6 @@ int32_t pt_taa_resolve(pt_context* c, const PtTaaParams* params, uint32_t resetH
     const size_t N = (size_t)c->width * c->height;
     if (c->taaW != c->width || c->taaH != c->height) { taa_drop_history(c); c->taaW = c->width; c->taaH = c->height; }
     for (int s = 0; s < 2; s++) PT_CHECK_HIP(c, c->dTaa[s].resize(N));
-    if (gpuMs) for (int s = 0; s < 2; s++) if (!c->taaEvents[s]) PT_CHECK_HIP(c, hipEventCreate(&c->taaEvents[s]));
     TaaParams P; memcpy(&P, params, sizeof(P));
     // the history must be of this build pass (a second call on one frame) or of the one before: the rule of the denoiser's rxFrameSerial
     const bool hasHistory = c->taaHistory && !resetHistory && c->spFrameSerial - c->taaFrameSerial <= 1u;
@@ -57,46 +58,25 @@ int32_t pt_taa_resolve(pt_context* c, const PtTaaParams* params, uint32_t resetH
     const bool haveRelax = P.useHistoryClampRelax && c->dnW == c->width && c->dnH == c->height && c->dnW && c->dnNrdSerial == c->spFrameSerial;
     const uint side = c->taaSide ^ 1u;
     hipStream_t st = c->stream;
-    if (gpuMs) PT_CHECK_HIP(c, hipEventRecord(c->taaEvents[0], st));
+    PT_CHECK_HIP(c, c->taaEvents.begin(st, gpuMs != nullptr));
     launch_taa_resolve(c->dAccum.p, c->dSpMotion.p, haveRelax ? c->dDnHistoryClamp.p : nullptr, hasHistory ? c->dTaa[side ^ 1u].p : nullptr, c->dTaa[side].p, P, c->width, c->height, st);
-    if (gpuMs) PT_CHECK_HIP(c, hipEventRecord(c->taaEvents[1], st));
+    PT_CHECK_HIP(c, c->taaEvents.end(st));
     c->taaSide = side; c->taaHistory = true; c->taaResolved = true; c->taaFrameSerial = c->spFrameSerial;
     PT_CHECK_HIP(c, hipStreamSynchronize(st)); PT_CHECK_HIP(c, hipGetLastError());
-    if (gpuMs) PT_CHECK_HIP(c, hipEventElapsedTime(gpuMs, c->taaEvents[0], c->taaEvents[1]));
+    PT_CHECK_HIP(c, c->taaEvents.read(gpuMs));
     return PT_OK;
 }
 
 int32_t pt_resolved_device_buffer(pt_context* c, void** devicePtr, size_t* pitch) {
     if (!c || !devicePtr) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
-    *devicePtr = c->dTaa[c->taaSide].p; if (pitch) *pitch = (size_t)c->width * 16u;
-    return PT_OK;
+    PictureView v; int32_t r = view_resolved(c, &v);
+    return r != PT_OK ? r : display_device_buffer(v, devicePtr, pitch);
 }
 
 int32_t pt_get_resolved(pt_context* c, float* rgba) {
     if (!c || !rgba) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
-    (void)hipSetDevice(c->device);
-    PT_CHECK_HIP(c, hipMemcpy(rgba, c->dTaa[c->taaSide].p, 16u * (size_t)c->width * c->height, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int32_t pt_tonemap_resolved(pt_context* c, const PtToneMapParams* params, uint8_t* rgba8, size_t bytes) {
-    if (!c || !params || !rgba8) return PT_ERROR_INVALID_ARGUMENT;
-    int32_t r = taa_resolved_ready(c); if (r != PT_OK) return r;
-    const size_t n = (size_t)c->width * c->height;
-    if (bytes < n * 4) return fail(c, PT_ERROR_INVALID_ARGUMENT, "rgba8 buffer too small");
-    if (params->toneMapOperator > 5u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "unknown tone map operator");
-    (void)hipSetDevice(c->device);
-    static_assert(sizeof(PtToneMapParams) == sizeof(ptk::ToneMapParams), "tone map parameter layout");
-    ptk::ToneMapParams p; memcpy(&p, params, sizeof(p));
-    DevBuf<uint> d; PT_CHECK_HIP(c, d.resize(n));
-    launch_tonemap(c->dTaa[c->taaSide].p, (uint)n, p, d.p, c->stream);      // pt_tonemap's kernel, pointed at the resolved picture
-    PT_CHECK_HIP(c, hipMemcpyAsync(rgba8, d.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    d.free();
-    return PT_OK;
+    PictureView v; int32_t r = view_resolved(c, &v);
+    return r != PT_OK ? r : display_read_back(c, v, rgba, nullptr);
 }
 
 int32_t pt_taa_jitter(uint32_t sequence, uint32_t frameIndex, float offset[2]) {
