@@ -247,60 +247,50 @@ class PtTransport(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p), ("send", SEND), ("recv", RECV), ("group_begin", GROUP), ("group_end", GROUP)]
 
 
-def gather_host(width, height, rank, world, rgba, send, recv):
-    """pt_gather_host: the library's gather protocol over host memory and the caller's point-to-point transport.
-    send(ptr, nbytes, peer) / recv(ptr, nbytes, peer) are Python callables taking raw addresses; rgba: (h, w, 4) float32, modified in place on rank 0."""
-    L = load_library()
-    assert rgba.dtype == np.float32 and rgba.flags["C_CONTIGUOUS"] and rgba.shape == (height, width, 4)
-
-    def _wrap(fn):
-        def cb(user, buf, nbytes, peer):
+def _transport(send, recv, group_begin=None, group_end=None):
+    """A PtTransport over Python callables: send(ptr, nbytes, peer) / recv(ptr, nbytes, peer) take raw addresses; group_begin() / group_end() are optional (NULL when not
+    given). Returns (the structure, what must stay alive for as long as it is used)."""
+    def guarded(fn):
+        def cb(user, *args):
             try:
-                fn(buf, nbytes, peer); return 0
+                fn(*args); return 0
             except Exception:      # an exception must not unwind through the C frames
                 import traceback; traceback.print_exc(); return 1
         return cb
-    t = PtTransport(None, PtTransport.SEND(_wrap(send)), PtTransport.RECV(_wrap(recv)), PtTransport.GROUP(), PtTransport.GROUP())
+    fns = (PtTransport.SEND(guarded(send)), PtTransport.RECV(guarded(recv)),
+           PtTransport.GROUP(guarded(group_begin)) if group_begin else PtTransport.GROUP(), PtTransport.GROUP(guarded(group_end)) if group_end else PtTransport.GROUP())
+    return PtTransport(None, *fns), fns
+
+
+def gather_host(width, height, rank, world, rgba, send, recv, group_begin=None, group_end=None):
+    """pt_gather_host: the library's gather protocol over host memory and the caller's point-to-point transport (_transport); rgba: (h, w, 4) float32, modified in place on rank 0."""
+    L = load_library()
+    assert rgba.dtype == np.float32 and rgba.flags["C_CONTIGUOUS"] and rgba.shape == (height, width, 4)
+    t, _keep = _transport(send, recv, group_begin, group_end)
     r = L.pt_gather_host(width, height, rank, world, _p(rgba), ctypes.byref(t))
     if r != 0:
         raise PtError(r, "pt_gather_host")
     return rgba
 
 
-def neeat_exchange_host(width, height, rank, world, total_weight, candidates, depth, send, recv):
+def neeat_exchange_host(width, height, rank, world, total_weight, candidates, depth, send, recv, group_begin=None, group_end=None):
     """pt_neeat_exchange_host: all ranks end up with all ranks' feedback reservoirs and exported depth; (h, w) float32 / uint32 / float32 planes, modified in place; send / recv as in gather_host"""
     L = load_library()
     assert total_weight.dtype == np.float32 and candidates.dtype == np.uint32 and depth.dtype == np.float32 and total_weight.shape == candidates.shape == depth.shape == (height, width)
-
-    def _wrap(fn):
-        def cb(user, buf, nbytes, peer):
-            try:
-                fn(buf, nbytes, peer); return 0
-            except Exception:
-                import traceback; traceback.print_exc(); return 1
-        return cb
-    t = PtTransport(None, PtTransport.SEND(_wrap(send)), PtTransport.RECV(_wrap(recv)), PtTransport.GROUP(), PtTransport.GROUP())
+    t, _keep = _transport(send, recv, group_begin, group_end)
     r = L.pt_neeat_exchange_host(width, height, rank, world, _p(total_weight), _p(candidates), _p(depth), ctypes.byref(t))
     if r != 0:
         raise PtError(r, "pt_neeat_exchange_host")
 
 
-def exchange_planes_host(width, height, rank, world, planes, send, recv, to_root=False):
+def exchange_planes_host(width, height, rank, world, planes, send, recv, to_root=False, group_begin=None, group_end=None):
     """pt_exchange_planes_host: `planes` = C-contiguous arrays of shape (height, width[, ...]) — any bytes per pixel; all-to-all (every rank ends up with every rank's pixels) or,
     with to_root, towards rank 0 only; modified in place; send / recv as in gather_host"""
     L = load_library()
     for a in planes: assert a.flags["C_CONTIGUOUS"] and a.shape[0] == height and a.shape[1] == width
     bpp = np.array([a.nbytes // (width * height) for a in planes], np.uint32)
     ptrs = (ctypes.c_void_p * len(planes))(*[a.ctypes.data for a in planes])
-
-    def _wrap(fn):
-        def cb(user, buf, nbytes, peer):
-            try:
-                fn(buf, nbytes, peer); return 0
-            except Exception:
-                import traceback; traceback.print_exc(); return 1
-        return cb
-    t = PtTransport(None, PtTransport.SEND(_wrap(send)), PtTransport.RECV(_wrap(recv)), PtTransport.GROUP(), PtTransport.GROUP())
+    t, _keep = _transport(send, recv, group_begin, group_end)
     f = L.pt_exchange_planes_host; f.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p]; f.restype = ctypes.c_int32
     r = f(width, height, rank, world, ptrs, _p(bpp), len(planes), 1 if to_root else 0, ctypes.byref(t))
     if r != 0:
@@ -1064,22 +1054,23 @@ class PathTracer:
         f = self.L.pt_stable_planes_shard_bytes; f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]; f.restype = ctypes.c_int32
         n = ctypes.c_size_t(0); self._chk(f(self.h, int(rank), ctypes.byref(n)), "pt_stable_planes_shard_bytes"); return int(n.value)
 
-    def pack_stable_planes(self, device_ptr, nbytes):
-        f = self.L.pt_pack_stable_planes; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes), "pt_pack_stable_planes")
+    # ---- the records of a tile-sharded frame as flat device buffers (device pointers come from torch tensors): the owned pixels' records in shard_layout order / rank `rank`'s into place
+    def _pack(self, name, device_ptr, nbytes):
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes), name)
 
-    def unpack_stable_planes(self, device_ptr, nbytes, rank):
-        f = self.L.pt_unpack_stable_planes; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes, int(rank)), "pt_unpack_stable_planes")
+    def _unpack(self, name, device_ptr, nbytes, rank):
+        f = getattr(self.L, name); f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]; f.restype = ctypes.c_int32
+        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes, int(rank)), name)
 
-    def pack_stable_plane_guides(self, device_ptr, nbytes):
-        """pt_pack_stable_plane_guides: depth | specular hit distance | motion vectors of this rank's pixels, 16 bytes each (what the other ranks' bakers need of the build pass)"""
-        f = self.L.pt_pack_stable_plane_guides; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes), "pt_pack_stable_plane_guides")
-
-    def unpack_stable_plane_guides(self, device_ptr, nbytes, rank):
-        f = self.L.pt_unpack_stable_plane_guides; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]; f.restype = ctypes.c_int32
-        self._chk(f(self.h, ctypes.c_void_p(device_ptr), nbytes, int(rank)), "pt_unpack_stable_plane_guides")
+    def pack_shard(self, device_ptr, nbytes): self._pack("pt_pack_shard", device_ptr, nbytes)      # the radiance, 16 bytes per pixel
+    def unpack_shard(self, device_ptr, nbytes, rank): self._unpack("pt_unpack_shard", device_ptr, nbytes, rank)
+    def neeat_pack_feedback(self, device_ptr, nbytes): self._pack("pt_neeat_pack_feedback", device_ptr, nbytes)      # reservoir weight | candidate | exported depth, 12 bytes
+    def neeat_unpack_feedback(self, device_ptr, nbytes, rank): self._unpack("pt_neeat_unpack_feedback", device_ptr, nbytes, rank)
+    def pack_stable_plane_guides(self, device_ptr, nbytes): self._pack("pt_pack_stable_plane_guides", device_ptr, nbytes)      # depth | specular hit distance | motion vectors, 16 bytes: what the other ranks' bakers need of the build pass
+    def unpack_stable_plane_guides(self, device_ptr, nbytes, rank): self._unpack("pt_unpack_stable_plane_guides", device_ptr, nbytes, rank)
+    def pack_stable_planes(self, device_ptr, nbytes): self._pack("pt_pack_stable_planes", device_ptr, nbytes)      # the whole record, stable_planes_shard_bytes
+    def unpack_stable_planes(self, device_ptr, nbytes, rank): self._unpack("pt_unpack_stable_planes", device_ptr, nbytes, rank)
 
     def neeat_update_begin(self):
         """pt_neeat_update_begin: LightsBaker::UpdateBegin on its own (the realtime frame in parts)"""
@@ -1334,14 +1325,6 @@ class PathTracer:
         self._chk(self.L.pt_get_neeat_tables(self.h, None, None, _p(t), t.size), "pt_get_neeat_tables")
         return t, (int(jxy[0]), int(jxy[1]))
 
-    def neeat_pack_feedback(self, device_ptr, nbytes):
-        self.L.pt_neeat_pack_feedback.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-        self._chk(self.L.pt_neeat_pack_feedback(self.h, ctypes.c_void_p(device_ptr), nbytes), "pt_neeat_pack_feedback")
-
-    def neeat_unpack_feedback(self, device_ptr, nbytes, rank):
-        self.L.pt_neeat_unpack_feedback.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
-        self._chk(self.L.pt_neeat_unpack_feedback(self.h, ctypes.c_void_p(device_ptr), nbytes, rank), "pt_neeat_unpack_feedback")
-
     def light_feedback(self, sample=0):
         """the feedback reservoirs sample `sample` of the last render() call filled: (total weight float32 [H, W], candidate uint32 [H, W])"""
         w = np.zeros((self.height, self.width), np.float32); c = np.zeros((self.height, self.width), np.uint32)
@@ -1563,12 +1546,6 @@ class PathTracer:
         n, b = ctypes.c_uint32(), ctypes.c_size_t()
         self._chk(self.L.pt_shard_info(self.h, ctypes.byref(n), ctypes.byref(b)), "pt_shard_info")
         return n.value, b.value
-
-    def pack_shard(self, device_ptr, nbytes):
-        self._chk(self.L.pt_pack_shard(self.h, ctypes.c_void_p(device_ptr), ctypes.c_size_t(nbytes)), "pt_pack_shard")
-
-    def unpack_shard(self, device_ptr, nbytes, rank):
-        self._chk(self.L.pt_unpack_shard(self.h, ctypes.c_void_p(device_ptr), ctypes.c_size_t(nbytes), rank), "pt_unpack_shard")
 
     # ---- probes
     def comm_init(self, unique_id, rank, world):

@@ -1,5 +1,5 @@
 // mi355pt — C-ABI implementation (include/mi355pt.h): context, scene upload, BVH build/refit orchestration, light baking and
-// read-back; the frame drivers (pt_render and the realtime passes) are in pt_frame.hip, the display tail (pt_tonemap, pt_average_luminance) in pt_display.hip. Host side of the seam `Sample` implements in the reference
+// read-back; the frame drivers (pt_render and the realtime passes) are in pt_frame.hip, the display tail (pt_tonemap, pt_average_luminance) in pt_display.hip. the tile shards and their exchanges in pt_shard.hip / pt_shard_host.cpp. Host side of the seam `Sample` implements in the reference
 // (Rtxpt/Sample.cpp:1891-2313 Render, :2438-2559 PathTrace, :1464-1556 UpdatePathTracerConstants, :2770-2778 accumulation).
 // There is NO CPU fallback: every entry point that needs the device fails with PT_ERROR_NO_DEVICE / PT_ERROR_HIP.
 #include <cstring>
@@ -9,7 +9,6 @@
 #include "../../include/mi355pt_testhooks.h"
 #endif
 #include "pt_denoiser.h"
-#include <dlfcn.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -49,70 +48,6 @@ size_t host_texture_bytes(const HostTexture& t) { size_t n = 0; for (auto& m : t
 
 // the accumulation starts again: no samples, uniform sample counts, and what was derived from the old one (the denoised picture) is gone. The callers clear dAccum.
 void reset_accumulation(pt_context* c) { c->accumCount = 0; c->adaptive.perPixel = false; accum_denoise_drop(c); }
-
-uint morton2(uint x, uint y) {
-    auto part = [](uint v) { v &= 0xFFFF; v = (v | (v << 8)) & 0x00FF00FF; v = (v | (v << 4)) & 0x0F0F0F0F; v = (v | (v << 2)) & 0x33333333; v = (v | (v << 1)) & 0x55555555; return v; };
-    return part(x) | (part(y) << 1);
-}
-// pixel ownership: 32x32 tiles, tile t -> rank morton(t) % shardCount; inside a tile pixels are listed in 8x8 blocks so that the
-// 64 lanes of a wave start as an 8x8 screen block (coherent primary rays)
-void shard_pixel_lists(uint width, uint height, uint world, std::vector<std::vector<uint>>& out) {
-    out.assign(world, std::vector<uint>());
-    uint tx = (width + TILE - 1) / TILE, ty = (height + TILE - 1) / TILE;
-    std::vector<std::pair<uint, uint>> tiles;
-    for (uint y = 0; y < ty; y++) for (uint x = 0; x < tx; x++) tiles.push_back({morton2(x, y), y * tx + x});
-    std::sort(tiles.begin(), tiles.end());
-    uint order = 0;
-    for (auto& t : tiles) {
-        uint tX = t.second % tx, tY = t.second / tx;
-        std::vector<uint>& dst = out[(order / PT_SHARD_TILE_GROUP) % world];
-        order++;
-        for (uint by = 0; by < TILE; by += 8) for (uint bx = 0; bx < TILE; bx += 8)
-            for (uint y = 0; y < 8; y++) for (uint x = 0; x < 8; x++) {
-                uint px = tX * TILE + bx + x, py = tY * TILE + by + y;
-                if (px < width && py < height) dst.push_back((px << 16) | py);
-            }
-    }
-}
-void build_shards(pt_context* c) {
-    shard_pixel_lists(c->width, c->height, c->shardCount, c->shardPixels);
-    c->owned = c->shardPixels[c->shardRank];
-    // pt_gather's (and the stable-plane guide exchange's) per-rank counts and pixel lists follow the shard lists, not only the frame size
-    c->gatherW = c->gatherH = 0; c->spGatherW = c->spGatherH = 0;
-}
-
-// ---- RCCL, bound at run time. One process may already hold a librccl.so (PyTorch ships its own): RTLD_NOLOAD finds that copy first, so that a single
-// RCCL runs on the single HIP runtime of the process; a plain C++ host gets the system library.
-struct RcclApi {
-    void* lib = nullptr; bool tried = false; std::string error;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool load() {
-        if (tried) return lib != nullptr;
-        tried = true;
-        const char* env = getenv("MI355PT_RCCL_LIB");
-        if (env && *env) lib = dlopen(env, RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);
-        if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-        if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) lib = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) { const char* e = dlerror(); error = std::string("librccl.so not found: ") + (e ? e : ""); return false; }
-#define PT_RCCL_SYM(field, name) field = reinterpret_cast<decltype(field)>(dlsym(lib, name)); if (!field) { error = std::string("librccl.so lacks ") + name; lib = nullptr; return false; }
-        PT_RCCL_SYM(GetUniqueId, "ncclGetUniqueId") PT_RCCL_SYM(CommInitRank, "ncclCommInitRank") PT_RCCL_SYM(CommDestroy, "ncclCommDestroy") PT_RCCL_SYM(Send, "ncclSend")
-        PT_RCCL_SYM(Recv, "ncclRecv") PT_RCCL_SYM(GroupStart, "ncclGroupStart") PT_RCCL_SYM(GroupEnd, "ncclGroupEnd") PT_RCCL_SYM(GetErrorString, "ncclGetErrorString")
-#undef PT_RCCL_SYM
-        return true;
-    }
-};
-RcclApi g_rccl;
-#define PT_CHECK_NCCL(c, expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); } while (0)
 
 // the host path: the texels the setters converted (HostTexture::mips) pooled and uploaded, with the tables pt_texture_ingest.h lays out. With PT_DEVICE_TEXTURES_ON_DEVICE the
 // material textures are on the device already (pt_texture_ingest.hip) and only the environment image is placed.
@@ -505,37 +440,6 @@ int prepare(pt_context* c) {
     return PT_OK;
 }
 
-// Tile-sharded frames (pt_create with shardCount > 1): a rank traces, and feeds back for, its own pixels only, but the baker's passes read whole
-// neighbourhoods. Between two frames every rank therefore receives the other ranks' reservoirs and exported depth (12 bytes per pixel: 100 MB for a 4K frame;
-// the depth is what the reprojection tests — a pixel another rank traced would otherwise read as depth 0, "valid" by NaN compare, whatever its owner sees) and
-// then runs the same deterministic passes on the same planes as everybody else: identical tables and proxy counts on all ranks, identical to the unsharded run.
-// With a communicator (pt_comm_init) the exchange is RCCL point-to-point inside one group, un-padded like pt_gather; without one the host moves the packed
-// buffers (pt_neeat_pack_feedback / pt_neeat_unpack_feedback).
-int neeat_exchange_feedback(pt_context* c) {
-    pt_context::NeeAt& st = c->neeat;
-    if (c->shardCount == 1 || !c->comm || !st.feedbackFilled || st.W != c->width || st.H != c->height) return PT_OK;
-    hipStream_t s = c->stream;
-    if (st.xW != c->width || st.xH != c->height) {
-        std::vector<uint> others; for (uint r = 0; r < c->shardCount; r++) if (r != c->shardRank) others.insert(others.end(), c->shardPixels[r].begin(), c->shardPixels[r].end());
-        PT_CHECK_HIP(c, st.xPixels.upload(others, s)); PT_CHECK_HIP(c, st.xRecv.resize(3 * others.size())); PT_CHECK_HIP(c, st.xSend.resize(3 * c->owned.size())); PT_CHECK_HIP(c, hipStreamSynchronize(s));
-        st.xW = c->width; st.xH = c->height;
-    }
-    const size_t n = c->owned.size();
-    launch_pack_feedback(st.fbW.p, st.fbC.p, st.depth.p, c->dOwned.p, (uint)n, c->width, st.xSend.p, s);
-    PT_CHECK_NCCL(c, g_rccl.GroupStart());
-    size_t off = 0; ncclResult_t bad = ncclSuccess;
-    for (uint r = 0; r < c->shardCount && bad == ncclSuccess; r++) {
-        if (r == c->shardRank) continue;
-        const size_t m = c->shardPixels[r].size();
-        if (n) bad = g_rccl.Send(st.xSend.p, 3 * n, ncclFloat, (int)r, c->comm, s);
-        if (m && bad == ncclSuccess) bad = g_rccl.Recv(st.xRecv.p + 3 * off, 3 * m, ncclFloat, (int)r, c->comm, s);
-        off += m;
-    }
-    ncclResult_t ge = g_rccl.GroupEnd();
-    if (bad != ncclSuccess || ge != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string("NEE-AT feedback exchange: ") + g_rccl.GetErrorString(bad != ncclSuccess ? bad : ge));
-    launch_unpack_feedback(st.fbW.p, st.fbC.p, st.depth.p, st.xPixels.p, (uint)off, c->width, st.xRecv.p, s);
-    return PT_OK;
-}
 // One frame of LightsBaker::UpdateBegin + UpdateEnd for the NEE-AT layer (LightsBaker.cpp:943-962, 985-1075, 1186-1213, 1335-1420) ahead of the frame's path
 // tracing; the order and the constants are spelled out in pt_neeat.h. The light set is the baked one; what changes per frame is the global proxy table, the
 // tile tables and the jitter. phases: NEEAT_BEGIN = LightsBaker::UpdateBegin (before the frame's G-buffer), NEEAT_END = UpdateEnd (after it, on the frame's
@@ -658,13 +562,13 @@ int32_t pt_create(const PtDeviceDesc* desc, pt_context** out) {
 int32_t pt_destroy(pt_context* c) {
     if (!c) return PT_ERROR_INVALID_ARGUMENT;
     (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream);
-    if (c->comm && g_rccl.lib) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-    c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free(); c->dSpGatherSend.free(); c->dSpGatherRecv.free(); c->dSpGatherPixels.free();
+    (void)pt_comm_destroy(c);
+    c->dSpHeader.free(); c->dSpThroughput.free(); c->dSpPlanes.free(); c->dSpRadiance.free(); c->dSpMotion.free(); c->dSpDepth.free(); c->dSpHitT.free(); c->dSpMark.free(); c->dSpNewL.free(); c->dSpScratch.free();
     c->dDnRRDiff.free(); c->dDnRRSpec.free(); c->dDnRRSpecMV.free(); c->dDnRRNormal.free(); c->dDnMotion.free(); c->dDnViewZ.free(); c->dDnRoughness.free(); c->dDnNormal.free(); c->dDnDiff.free(); c->dDnSpec.free(); c->dDnDisocclusion.free(); c->dDnHistoryClamp.free();
     relax_free(c); taa_free(c); bloom_free(c); taau_free(c); adaptive_free(c); accum_denoise_free(c);
     skin_drop(c); for (int e = 0; e < 2; e++) if (c->skinEvents[e]) (void)hipEventDestroy(c->skinEvents[e]);
     c->neeat.free(); c->dLocalTable.free(); c->dFbWeight.free(); c->dFbCand.free(); c->dSq3.free();
-    c->dGatherSend.free(); c->dGatherRecv.free(); c->dGatherPixels.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
+    c->staging.free(); c->dLightW.free(); c->dProxyOffsets.free(); if (c->dScanTemp) (void)hipFree(c->dScanTemp);
     if (c->bvhAllocated) bvh_free(c->bvh);
     c->dIndices.free(); c->dNormals.free(); c->dTangents.free(); c->dProxyCounters.free(); c->dProxyIndices.free(); c->dEnvLookup.free(); c->dOwned.free(); c->dQueue[0].free(); c->dQueue[1].free();
     c->dPrevPositions.free(); c->dPrevInstances.free(); c->dEmissiveList.free(); c->dEmissiveOffsets.free(); c->dPositions.free(); c->dUvs.free(); c->dGeometries.free(); c->dInstances.free(); c->dSubInstances.free(); c->dSubInstToInstGeom.free();
@@ -900,29 +804,6 @@ int32_t pt_set_neeat(pt_context* c, int32_t enable, float globalTemporalFeedback
     if (st.enabled != (enable != 0)) c->fbSamples = 0;      // the planes pt_get_light_feedback reads change hands: nothing is valid until the next pt_render
     st.enabled = enable != 0; st.globalFeedbackWeight = globalTemporalFeedbackWeight; st.localRatio = localToGlobalSampleRatio; st.sscThreshold = screenSpaceVsWorldSpaceThreshold; st.preFilter = preFilter != 0;
     refresh_scene_view(c);
-    return PT_OK;
-}
-// the owned pixels' reservoirs and exported depth as (weight bits, candidate, depth bits) triples, 12 bytes per pixel in the order of the rank's pixel list —
-// pt_pack_shard's order; device pointers
-int32_t pt_neeat_pack_feedback(pt_context* c, void* dst, size_t bytes) {
-    if (!c || !dst) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->neeat.enabled || !c->neeat.W || c->neeat.W != c->width || c->neeat.H != c->height) return fail(c, PT_ERROR_NOT_READY, "no NEE-AT frame yet: pt_set_neeat, then pt_render");
-    if (bytes < c->owned.size() * 12) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small (12 bytes per owned pixel)");
-    (void)hipSetDevice(c->device);
-    launch_pack_feedback(c->neeat.fbW.p, c->neeat.fbC.p, c->neeat.depth.p, c->dOwned.p, (uint)c->owned.size(), c->width, (uint*)dst, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
-}
-int32_t pt_neeat_unpack_feedback(pt_context* c, const void* src, size_t bytes, uint32_t rank) {
-    if (!c || !src || rank >= c->shardCount) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->neeat.enabled || !c->neeat.W || c->neeat.W != c->width || c->neeat.H != c->height) return fail(c, PT_ERROR_NOT_READY, "no NEE-AT frame yet: pt_set_neeat, then pt_render");
-    const std::vector<uint>& px = c->shardPixels[rank];
-    if (bytes < px.size() * 12) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small (12 bytes per pixel of that rank)");
-    (void)hipSetDevice(c->device);
-    DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_unpack_feedback(c->neeat.fbW.p, c->neeat.fbC.p, c->neeat.depth.p, tmp.p, (uint)px.size(), c->width, (const uint*)src, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    tmp.free();
     return PT_OK;
 }
 int32_t pt_set_view_projection(pt_context* c, const float* worldToClipRowMajor16) {
@@ -1289,60 +1170,8 @@ int32_t pt_stable_planes_plane_stride(uint32_t width, uint32_t height, uint32_t*
 // The realtime mode's frame with everything coupled (Sample.cpp:2438-2516; pt_set_neeat on): LightsBaker::UpdateBegin -> build pass -> LightsBaker::UpdateEnd
 // on THAT frame's depth and screen-space motion vectors -> the fill passes, which sample the tables just made and fill the reservoirs the next frame's
 // UpdateBegin reads.
-// ---- the realtime frame on tile shards (no reference analogue). The baker's passes read whole neighbourhoods of three things a rank only has for its own
-// tiles: last frame's reservoirs (UpdateBegin resolves them into the history), and this frame's depth and motion vectors (UpdateEnd reprojects through them).
-// So a sharded frame has two exchanges: the reservoirs before UpdateBegin (neeat_exchange_feedback, as between two reference-mode frames) and the build pass's
-// guides — depth and motion vectors, 16 bytes per pixel with the hit-distance word that lies between them — before UpdateEnd; every rank then runs the same
-// deterministic baker passes on the same planes. With a communicator pt_realtime_frame does both itself (RCCL point-to-point in one group, un-padded, like
-// pt_gather); without one the host drives the parts and moves the packed buffers: pt_neeat_pack / unpack_feedback -> pt_neeat_update_begin ->
-// pt_build_stable_planes -> pt_pack / unpack_stable_plane_guides -> pt_neeat_update_end -> pt_fill_stable_planes
-static int sp_exchange_guides(pt_context* c) {
-    if (c->shardCount == 1 || !c->comm) return PT_OK;
-    hipStream_t s = c->stream;
-    const size_t n = c->owned.size(), W = SP_GUIDE_WORDS;
-    // the other ranks' pixel list and the staging buffers: once per frame size, not per realtime frame (the shard layout is a function of the size)
-    if (c->spGatherW != c->width || c->spGatherH != c->height) {
-        std::vector<uint> others; for (uint r = 0; r < c->shardCount; r++) if (r != c->shardRank) others.insert(others.end(), c->shardPixels[r].begin(), c->shardPixels[r].end());
-        PT_CHECK_HIP(c, c->dSpGatherPixels.upload(others, s)); PT_CHECK_HIP(c, c->dSpGatherRecv.resize(others.size() * W)); PT_CHECK_HIP(c, c->dSpGatherSend.resize(n * W)); PT_CHECK_HIP(c, hipStreamSynchronize(s));
-        c->spGatherW = c->width; c->spGatherH = c->height;
-    }
-    const StablePlanesContext sp = sp_context(c, nullptr);
-    launch_sp_pack(sp, c->dOwned.p, (uint)n, c->dSpGatherSend.p, false, s, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
-    PT_CHECK_NCCL(c, g_rccl.GroupStart());
-    size_t off = 0; ncclResult_t bad = ncclSuccess;
-    for (uint r = 0; r < c->shardCount && bad == ncclSuccess; r++) {
-        if (r == c->shardRank) continue;
-        const size_t m = c->shardPixels[r].size();
-        if (n) bad = g_rccl.Send(c->dSpGatherSend.p, n * W, ncclFloat, (int)r, c->comm, s);
-        if (m && bad == ncclSuccess) bad = g_rccl.Recv(c->dSpGatherRecv.p + off * W, m * W, ncclFloat, (int)r, c->comm, s);
-        off += m;
-    }
-    ncclResult_t ge = g_rccl.GroupEnd();
-    if (bad != ncclSuccess || ge != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string("stable-plane guide exchange: ") + g_rccl.GetErrorString(bad != ncclSuccess ? bad : ge));
-    launch_sp_pack(sp, c->dSpGatherPixels.p, (uint)off, c->dSpGatherRecv.p, true, s, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
-    return PT_OK;
-}
-int32_t pt_pack_stable_plane_guides(pt_context* c, void* dst, size_t bytes) {
-    if (!c || !dst) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes");
-    if (bytes < c->owned.size() * (size_t)SP_GUIDE_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small (16 bytes per owned pixel)");
-    (void)hipSetDevice(c->device);
-    launch_sp_pack(sp_context(c, nullptr), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
-    return PT_OK;
-}
-int32_t pt_unpack_stable_plane_guides(pt_context* c, const void* src, size_t bytes, uint32_t rank) {
-    if (!c || !src || rank >= c->shardCount) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes (it allocates the buffers)");
-    const std::vector<uint>& px = c->shardPixels[rank];
-    if (bytes < px.size() * (size_t)SP_GUIDE_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small (16 bytes per pixel of that rank)");
-    (void)hipSetDevice(c->device);
-    DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_sp_pack(sp_context(c, nullptr), tmp.p, (uint)px.size(), (uint*)src, true, c->stream, SP_GUIDE_FIRST, SP_GUIDE_WORDS);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
-    tmp.free();
-    return PT_OK;
-}
+// On tile shards a frame has two exchanges (pt_shard.hip): the reservoirs before UpdateBegin (neeat_exchange_feedback) and the build pass's guides before UpdateEnd
+// (sp_exchange_guides).
 // LightsBaker::UpdateBegin / UpdateEnd as calls of their own (Rtxpt/Sample.cpp:1380-1412, 2491-2494): what pt_realtime_frame runs around the build pass, for a
 // host that puts something of its own in between (a tile-sharded frame without a communicator: the exchanges above)
 int32_t pt_neeat_update_begin(pt_context* c) {
@@ -1391,80 +1220,6 @@ int32_t pt_stable_planes_merge(pt_context* c) {
     // the buffer now holds one finished frame: pt_map_radiance / pt_tonemap / pt_gather read it, the next pt_render blends into it like into any first sample
     c->accumCount = 1;
     PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
-    return PT_OK;
-}
-// ---- the plane buffers of tile-sharded frames (no reference analogue): every rank builds and fills the planes of its own tiles; the rank that denoises or
-// shows the frame needs them all. 284 bytes per pixel (SP_SHARD_WORDS): header, three plane records, stable radiance, depth, specular hit distance, motion
-// vectors, throughput.
-int32_t pt_stable_planes_shard_bytes(pt_context* c, uint32_t rank, size_t* bytes) {
-    if (!c || !bytes || rank >= c->shardCount || !c->width) return PT_ERROR_INVALID_ARGUMENT;
-    *bytes = c->shardPixels[rank].size() * (size_t)SP_SHARD_WORDS * 4u; return PT_OK;
-}
-int32_t pt_pack_stable_planes(pt_context* c, void* dst, size_t bytes) {
-    if (!c || !dst) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes");
-    if (bytes < c->owned.size() * (size_t)SP_SHARD_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small (pt_stable_planes_shard_bytes)");
-    (void)hipSetDevice(c->device);
-    launch_sp_pack(sp_context(c, nullptr), c->dOwned.p, (uint)c->owned.size(), (uint*)dst, false, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
-    return PT_OK;
-}
-int32_t pt_unpack_stable_planes(pt_context* c, const void* src, size_t bytes, uint32_t rank) {
-    if (!c || !src || rank >= c->shardCount) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes (it allocates the buffers)");
-    const std::vector<uint>& px = c->shardPixels[rank];
-    if (bytes < px.size() * (size_t)SP_SHARD_WORDS * 4u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small (pt_stable_planes_shard_bytes)");
-    (void)hipSetDevice(c->device);
-    DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_sp_pack(sp_context(c, nullptr), tmp.p, (uint)px.size(), (uint*)src, true, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream)); PT_CHECK_HIP(c, hipGetLastError());
-    tmp.free();
-    c->spGathered = true;      // (the host says when all ranks are in: pt_denoise_spec_hit_t trusts it from here on)
-    return PT_OK;
-}
-// pt_gather for the plane buffers: every rank sends its tiles' records to rank 0 (RCCL point-to-point inside one group, un-padded, on the library's stream); a
-// world of one with a communicator runs the protocol as a loop-back with the buffers poisoned in between, like pt_gather
-int32_t pt_gather_stable_planes(pt_context* c) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->spW || c->spW != c->width || c->spH != c->height) return fail(c, PT_ERROR_NOT_READY, "no stable planes of this frame size yet: pt_build_stable_planes");
-    if (c->shardCount == 1 && !c->comm) return PT_OK;
-    if (!c->comm) return fail(c, PT_ERROR_NOT_READY, "pt_comm_init first");
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->stream;
-    const StablePlanesContext sp = sp_context(c, nullptr);
-    const size_t W = SP_SHARD_WORDS, n = c->owned.size();
-    if (c->shardCount == 1) {
-        if (!n) return PT_OK;
-        PT_CHECK_HIP(c, c->dSpGatherSend.resize(n * W)); PT_CHECK_HIP(c, c->dSpGatherRecv.resize(n * W));
-        launch_sp_pack(sp, c->dOwned.p, (uint)n, c->dSpGatherSend.p, false, st);
-        const size_t N = (size_t)c->width * c->height;
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpHeader.p, 0xEE, 16 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpPlanes.p, 0xEE, sizeof(ptk::StablePlane) * cStablePlaneCount * sp.C.genericTSPlaneStride, st));
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpRadiance.p, 0xEE, 8 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpDepth.p, 0xEE, 4 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpHitT.p, 0xEE, 4 * N, st));
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dSpMotion.p, 0xEE, 8 * N, st)); PT_CHECK_HIP(c, hipMemsetAsync(c->dSpThroughput.p, 0xEE, 4 * N, st));
-        PT_CHECK_NCCL(c, g_rccl.GroupStart());
-        ncclResult_t rs = g_rccl.Send(c->dSpGatherSend.p, n * W, ncclFloat, 0, c->comm, st);
-        ncclResult_t rr = (rs == ncclSuccess) ? g_rccl.Recv(c->dSpGatherRecv.p, n * W, ncclFloat, 0, c->comm, st) : rs;
-        ncclResult_t re = g_rccl.GroupEnd();
-        if (rr != ncclSuccess || re != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string("pt_gather_stable_planes loop-back: ") + g_rccl.GetErrorString(rr != ncclSuccess ? rr : re));
-        launch_sp_pack(sp, c->dOwned.p, (uint)n, c->dSpGatherRecv.p, true, st);
-        PT_CHECK_HIP(c, hipStreamSynchronize(st));
-        return PT_OK;
-    }
-    if (c->shardRank != 0) {
-        if (n) { PT_CHECK_HIP(c, c->dSpGatherSend.resize(n * W)); launch_sp_pack(sp, c->dOwned.p, (uint)n, c->dSpGatherSend.p, false, st); PT_CHECK_NCCL(c, g_rccl.Send(c->dSpGatherSend.p, n * W, ncclFloat, 0, c->comm, st)); }
-        PT_CHECK_HIP(c, hipStreamSynchronize(st));
-        return PT_OK;
-    }
-    std::vector<uint> others; for (uint r = 1; r < c->shardCount; r++) others.insert(others.end(), c->shardPixels[r].begin(), c->shardPixels[r].end());
-    PT_CHECK_HIP(c, c->dSpGatherPixels.upload(others, st)); PT_CHECK_HIP(c, c->dSpGatherRecv.resize(others.size() * W)); PT_CHECK_HIP(c, hipStreamSynchronize(st));
-    size_t off = 0; ncclResult_t bad = ncclSuccess;
-    PT_CHECK_NCCL(c, g_rccl.GroupStart());
-    for (uint r = 1; r < c->shardCount && bad == ncclSuccess; r++) { const size_t m = c->shardPixels[r].size(); if (m) bad = g_rccl.Recv(c->dSpGatherRecv.p + off * W, m * W, ncclFloat, (int)r, c->comm, st); off += m; }
-    ncclResult_t ge = g_rccl.GroupEnd();
-    if (bad != ncclSuccess || ge != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string("pt_gather_stable_planes: ") + g_rccl.GetErrorString(bad != ncclSuccess ? bad : ge));
-    launch_sp_pack(sp, c->dSpGatherPixels.p, (uint)off, c->dSpGatherRecv.p, true, st);
-    PT_CHECK_HIP(c, hipStreamSynchronize(st));
-    c->spGathered = true;
     return PT_OK;
 }
 int32_t pt_denoise_spec_hit_t(pt_context* c) {
@@ -1598,32 +1353,6 @@ int32_t pt_default_tonemap(PtToneMapParams* out, float exposureCompensation, flo
     out->colorTransform[0] = s; out->colorTransform[4] = s; out->colorTransform[8] = s;
     return PT_OK;
 }
-
-int32_t pt_shard_info(pt_context* c, uint32_t* numOwned, size_t* bytes) {
-    if (!c || !c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    if (numOwned) *numOwned = (uint32_t)c->owned.size(); if (bytes) *bytes = c->owned.size() * 16;
-    return PT_OK;
-}
-int32_t pt_pack_shard(pt_context* c, void* dst, size_t bytes) {
-    if (!c || !dst || !c->width) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
-    if (bytes < c->owned.size() * 16) return fail(c, PT_ERROR_INVALID_ARGUMENT, "destination too small");
-    (void)hipSetDevice(c->device);
-    launch_pack(c->dAccum.p, c->dOwned.p, (uint)c->owned.size(), c->width, (ptk::float4*)dst, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
-}
-int32_t pt_unpack_shard(pt_context* c, const void* src, size_t bytes, uint32_t rank) {
-    if (!c || !src || !c->width || rank >= c->shardCount) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
-    const std::vector<uint>& px = c->shardPixels[rank];
-    if (bytes < px.size() * 16) return fail(c, PT_ERROR_INVALID_ARGUMENT, "source too small");
-    (void)hipSetDevice(c->device);
-    DevBuf<uint> tmp; PT_CHECK_HIP(c, tmp.upload(px, c->stream));
-    launch_unpack(c->dAccum.p, tmp.p, (uint)px.size(), c->width, (const ptk::float4*)src, c->stream);
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    tmp.free();
-    return PT_OK;
-}
-int32_t pt_device_radiance(pt_context* c, void** p) { if (!c || !p || !c->width) return PT_ERROR_INVALID_ARGUMENT; *p = c->dAccum.p; return PT_OK; }
 
 static int trace_probe(pt_context* c, const float* rays, uint32_t n, float* outClosest, uint32_t* outVisible, double* kernelMs) {
     if (!c || !rays || !n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
@@ -1884,170 +1613,6 @@ int32_t pt_trace_route(pt_context* c, int32_t route, const float* rays, uint32_t
     return PT_OK;
 }
 #endif
-// ---- the frame gather (include/mi355pt.h "the frame gather itself")
-int32_t pt_shard_layout(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, uint32_t* pixels, uint32_t capacity, uint32_t* count) {
-    if (!width || !height || width > 65535 || height > 65535 || !world || rank >= world) return PT_ERROR_INVALID_ARGUMENT;
-    std::vector<std::vector<uint>> lists; shard_pixel_lists(width, height, world, lists);
-    const std::vector<uint>& mine = lists[rank];
-    if (count) *count = (uint32_t)mine.size();
-    if (pixels) { if (capacity < mine.size()) return PT_ERROR_INVALID_ARGUMENT; if (!mine.empty()) memcpy(pixels, mine.data(), 4 * mine.size()); }
-    return PT_OK;
-}
-int32_t pt_comm_unique_id(void* id128) {
-    if (!id128) return PT_ERROR_INVALID_ARGUMENT;
-    if (!g_rccl.load()) return PT_ERROR_HIP;
-    static_assert(sizeof(ncclUniqueId) == PT_COMM_ID_BYTES, "unique id size");
-    ncclUniqueId id; if (g_rccl.GetUniqueId(&id) != ncclSuccess) return PT_ERROR_HIP;
-    memcpy(id128, &id, sizeof(id));
-    return PT_OK;
-}
-int32_t pt_comm_init(pt_context* c, const void* id128, uint32_t rank, uint32_t world) {
-    if (!c || !id128) return fail(c, PT_ERROR_INVALID_ARGUMENT, "null argument");
-    if (rank != c->shardRank || world != c->shardCount) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_comm_init: rank / world must equal the context's shardRank / shardCount");
-    if (!g_rccl.load()) return fail(c, PT_ERROR_HIP, g_rccl.error);
-    (void)hipSetDevice(c->device);
-    if (c->comm) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
-    ncclUniqueId id; memcpy(&id, id128, sizeof(id));
-    PT_CHECK_NCCL(c, g_rccl.CommInitRank(&c->comm, (int)world, id, (int)rank));
-    c->commRank = rank; c->commWorld = world; c->gatherW = c->gatherH = 0;
-    return PT_OK;
-}
-int32_t pt_comm_destroy(pt_context* c) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    if (c->comm && g_rccl.lib) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); (void)g_rccl.CommDestroy(c->comm); }
-    c->comm = nullptr;
-    return PT_OK;
-}
-int32_t pt_gather(pt_context* c) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    if (!c->width) return fail(c, PT_ERROR_NOT_READY, "pt_resize first");
-    if (c->shardCount == 1 && !c->comm) return PT_OK;                           // nothing to gather
-    if (!c->comm) return fail(c, PT_ERROR_NOT_READY, "pt_comm_init first");
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->stream;
-    if (c->shardCount == 1) {
-        // a world of one WITH a communicator: the whole protocol as a loop-back — pack, ncclSend to self + ncclRecv from self inside one group, unpack — so
-        // that the run-time-bound RCCL path can be exercised (and checked) on a one-GPU box. The frame is poisoned between pack and unpack: what
-        // pt_map_radiance returns afterwards has been through RCCL.
-        const size_t n = c->owned.size();
-        if (!n) return PT_OK;
-        PT_CHECK_HIP(c, c->dGatherSend.resize(n)); PT_CHECK_HIP(c, c->dGatherRecv.resize(n));
-        launch_pack(c->dAccum.p, c->dOwned.p, (uint)n, c->width, c->dGatherSend.p, st);
-        PT_CHECK_HIP(c, hipMemsetAsync(c->dAccum.p, 0xFF, sizeof(ptk::float4) * (size_t)c->width * c->height, st));
-        PT_CHECK_NCCL(c, g_rccl.GroupStart());
-        ncclResult_t rs = g_rccl.Send(c->dGatherSend.p, 4 * n, ncclFloat, 0, c->comm, st);
-        ncclResult_t rr = (rs == ncclSuccess) ? g_rccl.Recv(c->dGatherRecv.p, 4 * n, ncclFloat, 0, c->comm, st) : rs;
-        ncclResult_t re = g_rccl.GroupEnd();
-        if (rr != ncclSuccess || re != ncclSuccess) return fail(c, PT_ERROR_HIP, std::string("pt_gather loop-back: ") + g_rccl.GetErrorString(rr != ncclSuccess ? rr : re));
-        launch_unpack(c->dAccum.p, c->dOwned.p, (uint)n, c->width, c->dGatherRecv.p, st);
-        return PT_OK;
-    }
-    // per-size state: counts of every rank; on rank 0 the other ranks' pixel lists on the device
-    if (c->gatherW != c->width || c->gatherH != c->height) {
-        c->gatherCounts.assign(c->shardCount, 0);
-        std::vector<uint> others;
-        for (uint r = 0; r < c->shardCount; r++) { c->gatherCounts[r] = c->shardPixels[r].size(); if (r != 0 && c->shardRank == 0) others.insert(others.end(), c->shardPixels[r].begin(), c->shardPixels[r].end()); }
-        if (c->shardRank == 0) { PT_CHECK_HIP(c, c->dGatherPixels.upload(others, st)); PT_CHECK_HIP(c, c->dGatherRecv.resize(others.size())); PT_CHECK_HIP(c, hipStreamSynchronize(st)); }
-        else PT_CHECK_HIP(c, c->dGatherSend.resize(c->owned.size()));
-        c->gatherW = c->width; c->gatherH = c->height;
-    }
-    if (c->shardRank != 0) {
-        const size_t n = c->owned.size();
-        if (n) {
-            launch_pack(c->dAccum.p, c->dOwned.p, (uint)n, c->width, c->dGatherSend.p, st);
-            PT_CHECK_NCCL(c, g_rccl.Send(c->dGatherSend.p, 4 * n, ncclFloat, 0, c->comm, st));
-        }
-        return PT_OK;
-    }
-    size_t off = 0, total = 0;
-    PT_CHECK_NCCL(c, g_rccl.GroupStart());
-    for (uint r = 1; r < c->shardCount; r++) {
-        const size_t n = c->gatherCounts[r];
-        if (n) { ncclResult_t rr = g_rccl.Recv(c->dGatherRecv.p + off, 4 * n, ncclFloat, (int)r, c->comm, st); if (rr != ncclSuccess) { (void)g_rccl.GroupEnd(); return fail(c, PT_ERROR_HIP, std::string("ncclRecv: ") + g_rccl.GetErrorString(rr)); } }
-        off += n;
-    }
-    PT_CHECK_NCCL(c, g_rccl.GroupEnd());
-    total = off;
-    if (total) launch_unpack(c->dAccum.p, c->dGatherPixels.p, (uint)total, c->width, c->dGatherRecv.p, st);
-    return PT_OK;
-}
-// The NEE-AT feedback exchange of tile-sharded frames (neeat_exchange_feedback) over HOST memory and the caller's transport: every rank sends the reservoirs
-// and the exported depth of its own pixels (12 bytes each) to every other rank and receives theirs. Pairs meet in rank order (the lower rank sends first), so
-// blocking transports cannot deadlock.
-int32_t pt_neeat_exchange_host(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, float* totalWeight, uint32_t* candidates, float* depth, const PtTransport* t) {
-    if (!totalWeight || !candidates || !depth || !t || !t->send || !t->recv || !width || !height || width > 65535 || height > 65535 || !world || rank >= world) return PT_ERROR_INVALID_ARGUMENT;
-    if (world == 1) return PT_OK;
-    try {
-        std::vector<std::vector<uint>> lists; shard_pixel_lists(width, height, world, lists);
-        auto slot = [&](uint px) { return (size_t)(px & 0xFFFFu) * width + (px >> 16); };
-        const std::vector<uint>& mine = lists[rank];
-        std::vector<uint> sendbuf(3 * mine.size()), recvbuf;
-        for (size_t i = 0; i < mine.size(); i++) { memcpy(&sendbuf[3 * i], &totalWeight[slot(mine[i])], 4); sendbuf[3 * i + 1] = candidates[slot(mine[i])]; memcpy(&sendbuf[3 * i + 2], &depth[slot(mine[i])], 4); }
-        for (uint p = 0; p < world; p++) {
-            if (p == rank) continue;
-            recvbuf.resize(3 * lists[p].size());
-            for (int step = 0; step < 2; step++) {
-                const bool sendNow = (rank < p) == (step == 0);
-                if (sendNow) { if (!mine.empty() && t->send(t->user, sendbuf.data(), 12 * mine.size(), p) != 0) return PT_ERROR_IO; }
-                else if (!lists[p].empty() && t->recv(t->user, recvbuf.data(), 12 * lists[p].size(), p) != 0) return PT_ERROR_IO;
-            }
-            for (size_t i = 0; i < lists[p].size(); i++) { memcpy(&totalWeight[slot(lists[p][i])], &recvbuf[3 * i], 4); candidates[slot(lists[p][i])] = recvbuf[3 * i + 1]; memcpy(&depth[slot(lists[p][i])], &recvbuf[3 * i + 2], 4); }
-        }
-        return PT_OK;
-    } catch (...) { return PT_ERROR_IO; }
-}
-// The general form over HOST memory: numPlanes row-major width x height planes of bytesPerPixel[k] bytes per pixel each (depth: 4, motion vectors: 8, a header
-// plane: 4 ...). toRoot = 0: every rank sends the records of its own pixels to every other rank and receives theirs (the guide exchange of a tile-sharded
-// realtime frame; pt_neeat_exchange_host is this with three 4-byte planes). toRoot = 1: every rank sends to rank 0 only (the plane-buffer gather). A record =
-// the planes' bytes of one pixel back to back, in the rank's pixel order (pt_shard_layout); transfers are un-padded; pairs meet in rank order, so blocking
-// transports cannot deadlock.
-int32_t pt_exchange_planes_host(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, void* const* planes, const uint32_t* bytesPerPixel, uint32_t numPlanes, int32_t toRoot, const PtTransport* t) {
-    if (!planes || !bytesPerPixel || !numPlanes || !t || !t->send || !t->recv || !width || !height || width > 65535 || height > 65535 || !world || rank >= world) return PT_ERROR_INVALID_ARGUMENT;
-    size_t rec = 0; for (uint32_t k = 0; k < numPlanes; k++) { if (!planes[k] || !bytesPerPixel[k]) return PT_ERROR_INVALID_ARGUMENT; rec += bytesPerPixel[k]; }
-    if (world == 1) return PT_OK;
-    try {
-        std::vector<std::vector<uint>> lists; shard_pixel_lists(width, height, world, lists);
-        auto slot = [&](uint px) { return (size_t)(px & 0xFFFFu) * width + (px >> 16); };
-        auto pack = [&](const std::vector<uint>& px, std::vector<unsigned char>& buf) { buf.resize(rec * px.size()); size_t o = 0; for (uint q : px) for (uint32_t k = 0; k < numPlanes; k++) { memcpy(&buf[o], (const unsigned char*)planes[k] + slot(q) * bytesPerPixel[k], bytesPerPixel[k]); o += bytesPerPixel[k]; } };
-        auto unpack = [&](const std::vector<uint>& px, const std::vector<unsigned char>& buf) { size_t o = 0; for (uint q : px) for (uint32_t k = 0; k < numPlanes; k++) { memcpy((unsigned char*)planes[k] + slot(q) * bytesPerPixel[k], &buf[o], bytesPerPixel[k]); o += bytesPerPixel[k]; } };
-        const std::vector<uint>& mine = lists[rank];
-        std::vector<unsigned char> sendbuf, recvbuf; pack(mine, sendbuf);
-        for (uint p = 0; p < world; p++) {
-            if (p == rank) continue;
-            const bool iSend = !toRoot || p == 0u, iRecv = !toRoot || rank == 0u;
-            recvbuf.resize(rec * lists[p].size());
-            for (int step = 0; step < 2; step++) {
-                const bool sendNow = (rank < p) == (step == 0);
-                if (sendNow) { if (iSend && !mine.empty() && t->send(t->user, sendbuf.data(), sendbuf.size(), p) != 0) return PT_ERROR_IO; }
-                else if (iRecv && !lists[p].empty() && t->recv(t->user, recvbuf.data(), recvbuf.size(), p) != 0) return PT_ERROR_IO;
-            }
-            if (iRecv) unpack(lists[p], recvbuf);
-        }
-        return PT_OK;
-    } catch (...) { return PT_ERROR_IO; }
-}
-int32_t pt_gather_host(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, float* rgba, const PtTransport* t) {
-    if (!rgba || !t || !t->send || !t->recv || !width || !height || width > 65535 || height > 65535 || !world || rank >= world) return PT_ERROR_INVALID_ARGUMENT;
-    if (world == 1) return PT_OK;
-    try {
-        std::vector<std::vector<uint>> lists; shard_pixel_lists(width, height, world, lists);
-        auto at = [&](uint px) { return rgba + 4 * ((size_t)(px & 0xFFFFu) * width + (px >> 16)); };
-        if (rank != 0) {
-            const std::vector<uint>& mine = lists[rank];
-            std::vector<float> sendbuf(4 * mine.size());
-            for (size_t i = 0; i < mine.size(); i++) memcpy(&sendbuf[4 * i], at(mine[i]), 16);
-            if (!mine.empty() && t->send(t->user, sendbuf.data(), 16 * mine.size(), 0) != 0) return PT_ERROR_IO;
-            return PT_OK;
-        }
-        std::vector<std::vector<float>> recvbuf(world);
-        if (t->group_begin && t->group_begin(t->user) != 0) return PT_ERROR_IO;
-        for (uint r = 1; r < world; r++) { recvbuf[r].resize(4 * lists[r].size()); if (!lists[r].empty() && t->recv(t->user, recvbuf[r].data(), 16 * lists[r].size(), r) != 0) return PT_ERROR_IO; }
-        if (t->group_end && t->group_end(t->user) != 0) return PT_ERROR_IO;
-        for (uint r = 1; r < world; r++) for (size_t i = 0; i < lists[r].size(); i++) memcpy(at(lists[r][i]), &recvbuf[r][4 * i], 16);
-        return PT_OK;
-    } catch (...) { return PT_ERROR_IO; }
-}
-
 int32_t pt_get_build_stats(pt_context* c, double* b, double* r, double* l) { if (!c) return PT_ERROR_INVALID_ARGUMENT; if (b) *b = c->buildMs; if (r) *r = c->refitMs; if (l) *l = c->lightBakeMs; return PT_OK; }
 int32_t pt_get_bvh_info(pt_context* c, PtBvhInfo* out) {
     if (!c || !out) return PT_ERROR_INVALID_ARGUMENT;

@@ -1,5 +1,5 @@
 // mi355pt — what the translation units behind include/mi355pt.h share: the context, its device buffers, the error helpers, the tuning
-// defines and the few functions of pt_api.hip that the frame drivers (pt_frame.hip) call. Private: nothing here is exported.
+// defines and the few functions of pt_api.hip and pt_shard.hip that the other translation units call. Private: nothing here is exported.
 #pragma once
 #include "../../include/mi355pt.h"
 #include "pt_wavefront.h"
@@ -8,6 +8,7 @@
 #include "pt_denoiser.h"
 #include "pt_build.h"
 #include "pt_adaptive.h"
+#include "pt_shard.h"
 #include <rccl/rccl.h>      // types only: the functions are bound at run time (dlopen), see pt_comm_init
 #include <string>
 #include <vector>
@@ -66,11 +67,15 @@ struct BloomState {
 
 struct HostTexture { uint w, h, mipLevels; std::vector<std::vector<ptk::float4>> mips; };
 
-static const uint TILE = 32;
+// the staging of a shard exchange (pt_shard.hip shard_exchange), one for the four records: the packed records of the own pixels, the records received, and the pixel list the
+// latter are unpacked by — every other rank's pixels in rank order, which serves both routes on every rank (a sender to rank 0 needs none). Grow-only, sized in words;
+// w x h: the frame size `pixels` is of (0: none; build_shards drops it with the shard lists).
+struct ShardStaging {
+    DevBuf<uint> send, recv, pixels; uint w = 0, h = 0;
+    void free() { send.free(); recv.free(); pixels.free(); w = h = 0; }
+};
+
 static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per queue (2 queues per pipelined batch, 16 B each)
-#ifndef PT_SHARD_TILE_GROUP
-#define PT_SHARD_TILE_GROUP 1      // consecutive Morton-ordered 32x32 tiles dealt to the same rank (locality vs load balance)
-#endif
 #ifndef PT_PIPELINE_FULL_AT
 // paths per pt_render call from which all PT_PIPELINE_BATCHES are used (one rank of an 8-way sharded 4K frame has 4.1 M)
 #define PT_PIPELINE_FULL_AT (1u << 21)
@@ -219,15 +224,13 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
         DevBuf<float> fbW, scW, blW, snapW, curW, histW; DevBuf<uint> fbC, scC, blC, snapC, local, counters;
         // the exported depth of the last traced frame / of the one before; columns 2 and 3 of pt_set_view_projection's matrix
         DevBuf<float> depth, histDepth; bool haveClip = false; float clipZ[4] = {0, 0, 0, 0}, clipW[4] = {0, 0, 0, 0};
-        // tile-sharded frames: the exchange of the owned pixels' reservoirs between frames
-        DevBuf<uint> xSend, xRecv; DevBuf<uint> xPixels; uint xW = 0, xH = 0;
         void reset() {
             W = H = 0; updateCounter = 0; jitterF[0] = jitterF[1] = 0; jitter[0] = jitter[1] = prevJitter[0] = prevJitter[1] = 0;
             feedbackFilled = lastFeedbackAvailable = false; frameOpen = false; exportDepth = true; historicTotalLightCount = 0; nHist = 0;
         }
         void free() {
             fbW.free(); scW.free(); blW.free(); snapW.free(); curW.free(); histW.free(); fbC.free(); scC.free(); blC.free(); snapC.free();
-            local.free(); counters.free(); xSend.free(); xRecv.free(); xPixels.free(); depth.free(); histDepth.free();
+            local.free(); counters.free(); depth.free(); histDepth.free();
         }
     } neeat;
     // the path pool (ensure_pool). ...b: the second array set of a compacted pool (pt_render)
@@ -255,7 +258,7 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
     DevBuf<uint> dSpHeader, dSpThroughput; DevBuf<ptk::StablePlane> dSpPlanes; DevBuf<ptk::uint2> dSpRadiance, dSpMotion;
     DevBuf<float> dSpDepth, dSpHitT; uint spW = 0, spH = 0; bool spGathered = false;
     DevBuf<ptk::uint4> dSpMark; DevBuf<ptk::float4> dSpNewL;      // scratch of the fill passes
-    DevBuf<float> dSpScratch; DevBuf<uint> dSpGatherSend, dSpGatherRecv, dSpGatherPixels; uint spGatherW = 0, spGatherH = 0;
+    DevBuf<float> dSpScratch;
     // the denoiser buffers (pt_denoiser_prepare_dlss_rr / _nrd, pt_denoiser.h), allocated zeroed for a frame size by the first prepare call
     DevBuf<uint> dDnRRDiff, dDnRRSpec, dDnRRSpecMV; DevBuf<ptk::uint2> dDnRRNormal, dDnMotion; DevBuf<float> dDnViewZ, dDnRoughness;
     DevBuf<ptk::float4> dDnNormal, dDnDiff, dDnSpec;
@@ -301,9 +304,8 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
         DevBuf<ptk::float4> dOut, dStageH, dStageO, dVar, dInA, dInH; uint w = 0, h = 0; bool ready = false;
         EventBracket events;
     } accumDenoise;
-    // frame gather (pt_comm_init / pt_gather)
-    ncclComm_t comm = nullptr; uint commRank = 0, commWorld = 0; DevBuf<ptk::float4> dGatherSend, dGatherRecv; DevBuf<uint> dGatherPixels;
-    std::vector<size_t> gatherCounts; uint gatherW = 0, gatherH = 0;
+    // the exchanges of tile shards (pt_shard.hip): the communicator of pt_comm_init, of shardRank / shardCount
+    ncclComm_t comm = nullptr; ShardStaging staging;
 };
 
 #pragma GCC visibility push(hidden)
@@ -312,9 +314,12 @@ inline int fail(pt_context* c, int code, const std::string& msg) { if (c) c->las
 #define PT_CHECK_HIP(c, expr) \
     do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
+// ---- pt_shard.hip
+void build_shards(pt_context* c);                    // the shard lists of the frame size (pt_resize)
+int neeat_exchange_feedback(pt_context* c);          // tile shards with a communicator: the other ranks' reservoirs and depth, before UpdateBegin
+int sp_exchange_guides(pt_context* c);               // ... and the build pass's depth and motion vectors, before UpdateEnd
 // ---- pt_api.hip, for the frame drivers
 int prepare(pt_context* c);                          // whatever is dirty — textures, environment cube, geometry, lights — brought up to date
-int neeat_exchange_feedback(pt_context* c);          // tile shards with a communicator: the other ranks' reservoirs and depth
 // One frame of LightsBaker::UpdateBegin (NEEAT_BEGIN) / UpdateEnd (NEEAT_END) for the NEE-AT layer; see the definition
 enum { NEEAT_BEGIN = 1, NEEAT_END = 2, NEEAT_BOTH = 3 };
 int neeat_frame(pt_context* c, int phases = NEEAT_BOTH, const float* depth = nullptr, const ptk::uint2* motion = nullptr);

@@ -589,15 +589,6 @@ __global__ void __launch_bounds__(T8_BLOCK) k_trace_probe(DeviceScene sc, const 
     }
 }
 
-__global__ void __launch_bounds__(256) k_pack(const float4* __restrict__ accum, const uint* __restrict__ pixels, uint num, uint width, float4* __restrict__ dst) {
-    uint i = blockIdx.x * 256u + threadIdx.x; if (i >= num) return;
-    uint px = pixels[i]; dst[i] = accum[(px & 0xFFFFu) * width + (px >> 16)];
-}
-__global__ void __launch_bounds__(256) k_unpack(float4* __restrict__ accum, const uint* __restrict__ pixels, uint num, uint width, const float4* __restrict__ src) {
-    uint i = blockIdx.x * 256u + threadIdx.x; if (i >= num) return;
-    uint px = pixels[i]; accum[(px & 0xFFFFu) * width + (px >> 16)] = src[i];
-}
-
 // ---- EnvMapBaker on the device (EnvMapBaker.hlsl:194-246, 268-371; pt_envcube.h): BaseLayerCS makes four texels of mip 0 and their mip-1 texel per thread,
 // MIPReduceCS the further levels from the stored (fp16) texels; solid-angle weighted, summation order of the shader
 __device__ __forceinline__ float4 env_generate_texel(const DeviceScene& sc, const EnvDirectionalLight* __restrict__ lights, uint nLights, uint px, uint py, uint face, uint dim) {
@@ -1023,31 +1014,6 @@ void launch_accumulate(PathPool pool, const uint* ownedPixels, uint numOwned, ui
 }
 void launch_trace_probe(const DeviceScene& sc, const float4* rays, uint n, float4* outClosest, uint* outVisible, uint* overflow, hipStream_t st) {
     hipLaunchKernelGGL(k_trace_probe, dim3(grid_for(n, T8_BLOCK, T8_MAX_BLOCKS)), dim3(T8_BLOCK), 0, st, sc, rays, n, outClosest, outVisible, overflow);
-}
-// the NEE-AT feedback of a list of pixels as (weight bits, candidate, exported depth bits) triples, 12 bytes per pixel: what the ranks of a tile-sharded frame
-// exchange between frames — the reservoirs AND the depth the baker's reprojection tests (neeat_reproject): a neighbourhood crosses shard borders, so every rank
-// needs every pixel's depth
-__global__ void __launch_bounds__(256) k_pack_feedback(const float* __restrict__ fbW, const uint* __restrict__ fbC, const float* __restrict__ depth, const uint* __restrict__ pixels, uint num, uint width, uint* __restrict__ dst) {
-    uint i = blockIdx.x * 256u + threadIdx.x; if (i >= num) return;
-    const uint px = pixels[i], slot = (px & 0xFFFFu) * width + (px >> 16);
-    dst[3u * i] = __float_as_uint(fbW[slot]); dst[3u * i + 1u] = fbC[slot]; dst[3u * i + 2u] = depth ? __float_as_uint(depth[slot]) : 0u;
-}
-__global__ void __launch_bounds__(256) k_unpack_feedback(float* __restrict__ fbW, uint* __restrict__ fbC, float* __restrict__ depth, const uint* __restrict__ pixels, uint num, uint width, const uint* __restrict__ src) {
-    uint i = blockIdx.x * 256u + threadIdx.x; if (i >= num) return;
-    const uint px = pixels[i], slot = (px & 0xFFFFu) * width + (px >> 16);
-    fbW[slot] = __uint_as_float(src[3u * i]); fbC[slot] = src[3u * i + 1u]; if (depth) depth[slot] = __uint_as_float(src[3u * i + 2u]);
-}
-void launch_pack_feedback(const float* fbW, const uint* fbC, const float* depth, const uint* pixels, uint num, uint width, uint* dst, hipStream_t st) {
-    if (num) hipLaunchKernelGGL(k_pack_feedback, dim3((num + 255) / 256), dim3(256), 0, st, fbW, fbC, depth, pixels, num, width, dst);
-}
-void launch_unpack_feedback(float* fbW, uint* fbC, float* depth, const uint* pixels, uint num, uint width, const uint* src, hipStream_t st) {
-    if (num) hipLaunchKernelGGL(k_unpack_feedback, dim3((num + 255) / 256), dim3(256), 0, st, fbW, fbC, depth, pixels, num, width, src);
-}
-void launch_pack(const float4* accum, const uint* pixels, uint num, uint width, float4* dst, hipStream_t st) {
-    hipLaunchKernelGGL(k_pack, dim3((num + 255) / 256), dim3(256), 0, st, accum, pixels, num, width, dst);
-}
-void launch_unpack(float4* accum, const uint* pixels, uint num, uint width, const float4* src, hipStream_t st) {
-    hipLaunchKernelGGL(k_unpack, dim3((num + 255) / 256), dim3(256), 0, st, accum, pixels, num, width, src);
 }
 void launch_env_importance(const DeviceScene& sc, uint dim, uint sx, uint sy, float4* out, hipStream_t st) {
     hipLaunchKernelGGL(k_env_importance, dim3((dim * dim + 255) / 256), dim3(256), 0, st, sc, dim, sx, sy, out);

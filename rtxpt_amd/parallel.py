@@ -4,7 +4,7 @@ traces only its tiles; ONE collective per frame — a gather of the packed RGBA3
 backend is "nccl", gloo in the CPU tests). The RNG is keyed on absolute pixel coordinates + sample index, so the image is
 bit-identical for any world size.
 
-`shard_pixels` mirrors build_shards() in rtxpt_amd/csrc/pt_api.hip exactly (same tile order, same in-tile 8x8 block order).
+`shard_pixels` mirrors build_shards() in rtxpt_amd/csrc/pt_shard.hip (the lists of shard_pixel_lists(), pt_shard_host.cpp) exactly (same tile order, same in-tile 8x8 block order).
 """
 import numpy as np
 

@@ -177,3 +177,61 @@ def test_plane_exchange_through_the_c_entry_point(size, world, to_root):
                 want = np.full_like(b, 0xEE); want[yy, xx] = b[yy, xx]; assert np.array_equal(a, want), "rank %d" % rank
         else:
             for a, b in zip(planes, full): assert np.array_equal(a, b), "rank %d" % rank
+
+
+def _ranks_as_threads(world, call):
+    """call(rank, send, recv) for every rank, the ranks as threads of this process over one queue per (sender, receiver); returns (results, the (peer, nbytes) sends of every rank)"""
+    import ctypes, queue, threading
+    boxes = {(a, b): queue.Queue() for a in range(world) for b in range(world)}
+    sent = [[] for _ in range(world)]; out = [None] * world; errors = []
+
+    def work(r):
+        def send(ptr, nbytes, peer):
+            sent[r].append((peer, nbytes)); boxes[(r, peer)].put(ctypes.string_at(ptr, nbytes))
+
+        def recv(ptr, nbytes, peer):
+            b = boxes[(peer, r)].get(timeout=60); assert len(b) == nbytes; ctypes.memmove(ptr, b, nbytes)
+        try:
+            out[r] = call(r, send, recv)
+        except Exception as e:      # noqa: BLE001 — reported by the caller's assert
+            errors.append((r, repr(e)))
+    threads = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    for t in threads: t.start()
+    for t in threads: t.join(120)
+    assert not errors and not any(t.is_alive() for t in threads), errors
+    return out, sent
+
+
+@pytest.mark.parametrize("which,size,world", [("gather", (97, 61), 3), ("gather", (70, 45), 8), ("neeat", (97, 61), 3), ("neeat", (70, 45), 8)])
+def test_the_named_exchanges_are_the_general_one(which, size, world):
+    """pt_gather_host is pt_exchange_planes_host with one 16-byte plane towards rank 0, pt_neeat_exchange_host the same with three 4-byte planes all-to-all: the same bytes on
+    every rank afterwards and the same (peer, nbytes) sends in the same order. (70 x 45 has six tiles: two ranks of eight own nothing.)"""
+    import rtxpt_amd as pt
+    w, h = size
+    yy, xx = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    if which == "gather":
+        full = [fake_radiance(((xx.astype(np.uint32) << 16) | yy.astype(np.uint32)).reshape(-1)).reshape(h, w, 4)]
+    else:
+        full = [(xx * 0.25 + yy).astype(np.float32), (xx * 7919 + yy * 104729).astype(np.uint32), (0.5 + xx * 0.001 + yy * 0.37).astype(np.float32)]
+
+    def mine(rank):      # the rank's own tiles, poison elsewhere
+        px = pt.shard_layout(w, h, rank, world); py, pxx = (px & 0xFFFF).astype(np.int64), (px >> 16).astype(np.int64)
+        out = [np.frombuffer(bytearray(b"\xEE" * a.nbytes), a.dtype).reshape(a.shape) for a in full]
+        for a, b in zip(out, full): a[py, pxx] = b[py, pxx]
+        return out
+
+    def named(rank, send, recv):
+        p = mine(rank)
+        if which == "gather": pt.gather_host(w, h, rank, world, p[0], send, recv)
+        else: pt.neeat_exchange_host(w, h, rank, world, p[0], p[1], p[2], send, recv)
+        return p
+
+    def general(rank, send, recv):
+        p = mine(rank); pt.exchange_planes_host(w, h, rank, world, p, send, recv, to_root=which == "gather"); return p
+    a, sent_a = _ranks_as_threads(world, named)
+    b, sent_b = _ranks_as_threads(world, general)
+    assert sent_a == sent_b
+    for rank in range(world):
+        for x, y in zip(a[rank], b[rank]): assert x.tobytes() == y.tobytes(), "rank %d" % rank
+        if which == "neeat" or rank == 0:
+            for x, y in zip(a[rank], full): assert x.tobytes() == y.tobytes(), "rank %d" % rank
