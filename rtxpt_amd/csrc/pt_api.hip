@@ -5,9 +5,6 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>      // before pt_context.h: its `using namespace ptk` makes rocprim's own uint2 / uint4 ambiguous
 #include "pt_context.h"
-#ifdef MI355PT_TEST_HOOKS
-#include "../../include/mi355pt_testhooks.h"
-#endif
 #include "pt_denoiser.h"
 #include <algorithm>
 #include <cmath>
@@ -1462,157 +1459,6 @@ int32_t pt_get_scene_info(pt_context* c, uint32_t* nTris, uint32_t* nNodes, uint
     if (nTris) *nTris = c->numTris; if (nNodes) *nNodes = c->numTris ? c->bvh.numNodes8 : 0;      /* BVH8 nodes */ if (nInst) *nInst = (uint32_t)c->instances.size(); if (nMat) *nMat = (uint32_t)c->materials.size();
     return PT_OK;
 }
-#ifdef MI355PT_TEST_HOOKS      // include/mi355pt_testhooks.h: exported by libmi355pt_testhooks.so only
-int32_t pt_probe(pt_context* c, int32_t kind, const void* in, size_t inBytes, void* out, size_t outBytes, uint32_t n) {
-    if (!c || !in || !out || !n) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
-    (void)hipSetDevice(c->device);
-    // the surface, environment and alpha-test probes read the scene
-    if (kind == 8 || kind == 9 || kind == 10 || kind == 11 || kind == 12) { int r = prepare(c); if (r != PT_OK) return r; }
-    if (kind == 12) {      // the stochastic-filter probe indexes the texture table with what its rows say, and knows three filters
-        if (inBytes < (size_t)n * 48u || outBytes < (size_t)n * 32u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "stochastic texture probe: 12 words in and 8 words out per row");
-        const uint32_t* a = (const uint32_t*)in;
-        for (uint32_t i = 0; i < n; i++, a += 12)
-            if (a[0] > 1u || (a[0] == 0u && ((a[1] & 0xFFFFu) >= c->textures.size() || a[5] > PT_STF_FILTER_CUBIC))) return fail(c, PT_ERROR_INVALID_ARGUMENT, "stochastic texture probe: mode, texture or filter out of range");
-    }
-    if (kind == 11) {      // the texture probe indexes the texture table and a texture's mip offsets with what its rows say: hold both to the scene here, the kernel does not
-        if (inBytes < (size_t)n * 32u || outBytes < (size_t)n * 16u) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture probe: 8 words in and 4 floats out per row");
-        const uint32_t* a = (const uint32_t*)in;
-        for (uint32_t i = 0; i < n; i++, a += 8) {
-            const uint32_t tex = a[0] == 0u ? (a[1] & 0xFFFFu) : a[1];
-            if (a[0] > 2u || tex >= c->textures.size() || (a[0] == 1u && a[4] >= c->textures[tex].mipLevels)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "texture probe: mode, texture or mip out of range");
-        }
-    }
-    DevBuf<unsigned char> di, dout;
-    PT_CHECK_HIP(c, di.upload((const unsigned char*)in, inBytes, c->stream)); PT_CHECK_HIP(c, dout.resize(outBytes));
-    PathKernelContext k; k.sc = c->dsc; k.S = c->S; k.cam = c->cam;
-    launch_probe(k, kind, di.p, dout.p, n, c->stream);
-    PT_CHECK_HIP(c, hipMemcpyAsync(out, dout.p, outBytes, hipMemcpyDeviceToHost, c->stream));
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    PT_CHECK_HIP(c, hipGetLastError());
-    di.free(); dout.free();
-    return PT_OK;
-}
-int32_t pt_get_inert_terminal(pt_context* c, uint32_t* numPrims, uint32_t* words, uint32_t capacityWords, uint64_t* lastDropped) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    if (numPrims) *numPrims = c->numTris;
-    if (lastDropped) *lastDropped = c->droppedTerminal;
-    if (words && c->numTris) {
-        if (capacityWords < inert_words(c->numTris)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "inert-terminal table: (numPrims + 15) / 16 words");
-        PT_CHECK_HIP(c, hipMemcpy(words, c->dInertBits.p, 4 * (size_t)inert_words(c->numTris), hipMemcpyDeviceToHost));
-    }
-    return PT_OK;
-}
-// the wide tree as the traversal reads it: nodes8, triSorted, the scene bounds the pads were formed from and the level table the refit walks. Nothing else: after a fast refit
-// (pt_build.h bvh2Stale) the BVH2 nodes, triWorld and the range tables hold an older pose
-int32_t pt_get_bvh8(pt_context* c, uint32_t* numNodes, void* nodes, uint32_t capacityNodes, uint32_t* numTris, void* tris, uint32_t capacityTris, float* bounds,
-                    uint32_t* collapseLevels, uint32_t* wideLevelStart, uint32_t capacityLevels) {
-    if (!c) return PT_ERROR_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    const uint32_t nt = c->numTris, nn = nt ? c->bvh.numNodes8 : 0u, nl = nt ? c->bvh.collapseLevels : 0u, stored = (nl < BVH_MAX_WIDE_LEVELS ? nl : BVH_MAX_WIDE_LEVELS) + 1u;
-    if (numNodes) *numNodes = nn; if (numTris) *numTris = nt; if (collapseLevels) *collapseLevels = nl;
-    if ((nodes && capacityNodes < nn) || (tris && capacityTris < nt) || (wideLevelStart && capacityLevels < stored)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_get_bvh8: a buffer is smaller than its count");
-    PT_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    if (nodes && nn) PT_CHECK_HIP(c, hipMemcpy(nodes, c->bvh.nodes8, sizeof(Bvh8Node) * (size_t)nn, hipMemcpyDeviceToHost));
-    if (tris && nt) PT_CHECK_HIP(c, hipMemcpy(tris, c->bvh.triSorted, sizeof(TriRecord) * (size_t)nt, hipMemcpyDeviceToHost));
-    if (bounds) {
-        uint32_t enc[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-        if (nt) PT_CHECK_HIP(c, hipMemcpy(enc, c->bvh.sceneBounds, sizeof(enc), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 6; k++) { const uint32_t b = nt ? ((enc[k] & 0x80000000u) ? (enc[k] & 0x7FFFFFFFu) : ~enc[k]) : 0u; memcpy(bounds + k, &b, 4); }      // (pt_build.hip dec_float)
-    }
-    if (wideLevelStart) for (uint32_t l = 0; l < stored; l++) wideLevelStart[l] = nt ? c->bvh.wideLevelStart[l] : 0u;
-    return PT_OK;
-}
-// pt_trace_route: the caller's rays through launch_extend / launch_shadow / the packet launch, on buffers of the call's own (freed whichever way it returns)
-namespace {
-struct RouteBuffers {
-    DevBuf<ptk::uint4> s0, s1, s2, hit; DevBuf<ptk::float4> q0, q1, q2; DevBuf<uint> queue, words, resolveList, leftover;
-    DevBuf<TravTask> taskQ; DevBuf<unsigned long long> bestKey; DevBuf<WaveCounters> wc;
-    ~RouteBuffers() { s0.free(); s1.free(); s2.free(); hit.free(); q0.free(); q1.free(); q2.free(); queue.free(); words.free(); resolveList.free(); leftover.free(); taskQ.free(); bestKey.free(); wc.free(); }
-};
-// the call's counter words: a traversal launch's TRAV_COUNTERS from word 0, the leftover count at PASS_LEFTOVER (as in a pass's block), then the launch's ray count and the packets' commits
-const uint ROUTE_WORD_COUNT = PASS_COUNTERS, ROUTE_WORD_COMMITTED = PASS_COUNTERS + 1u, ROUTE_WORDS = PASS_COUNTERS + 2u;
-}
-int32_t pt_trace_route(pt_context* c, int32_t route, const float* rays, uint32_t n, const PtRouteOptions* options, void* out, PtRouteStats* stats) {
-    if (!c || !rays || !n || !out) return fail(c, PT_ERROR_INVALID_ARGUMENT, "bad argument");
-    if (route != PT_ROUTE_EXTEND && route != PT_ROUTE_EXTEND_RANGED && route != PT_ROUTE_SHADOW && route != PT_ROUTE_PACKETS) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_route: unknown route " + std::to_string(route));
-    const bool fixed = route == PT_ROUTE_EXTEND || route == PT_ROUTE_PACKETS;
-    for (uint32_t i = 0; i < n; i++) {      // (trace_probe's rule first: the traversal orders children by the bit pattern of an entry distance >= +0)
-        const float tmin = rays[8 * (size_t)i + 3], tmax = rays[8 * (size_t)i + 7];
-        if (!(tmin >= 0.0f) || std::signbit(tmin)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_route: ray " + std::to_string(i) + " has tmin < 0 (or -0, or NaN); tmin must be >= +0");
-        if (fixed && (tmin != 0.0f || tmax != kMaxRayTravel)) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_route: ray " + std::to_string(i) + " of a fixed-interval route must have tmin = 0 and tmax = 1e15f");
-        if (route == PT_ROUTE_SHADOW && tmin != 0.0f) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_route: ray " + std::to_string(i) + " of the shadow route must have tmin = 0 (a shadow-queue entry carries no lower bound)");
-    }
-    const PtRouteOptions opt = options ? *options : PtRouteOptions{0u, 0u, 0u, 0u};
-    if (opt.taskCap > TASK_QUEUE_CAPACITY) return fail(c, PT_ERROR_INVALID_ARGUMENT, "pt_trace_route: taskCap above TASK_QUEUE_CAPACITY");
-    (void)hipSetDevice(c->device);
-    int r = prepare(c); if (r != PT_OK) return r;
-    const hipStream_t st = c->stream;
-    RouteBuffers B;
-    std::vector<uint> words(ROUTE_WORDS, 0u); words[ROUTE_WORD_COUNT] = n;
-    PT_CHECK_HIP(c, B.words.upload(words, st));
-    PT_CHECK_HIP(c, B.wc.resize(1)); PT_CHECK_HIP(c, hipMemsetAsync(B.wc.p, 0, sizeof(WaveCounters), st));      // (the overflow word with it)
-    TravAux aux;
-    aux.taskCap = opt.taskCap ? opt.taskCap : TASK_QUEUE_CAPACITY; aux.maxBlocks = opt.maxBlocks;
-    PT_CHECK_HIP(c, B.taskQ.resize(2 * (size_t)aux.taskCap)); PT_CHECK_HIP(c, B.bestKey.resize(n)); PT_CHECK_HIP(c, B.resolveList.resize(n));
-    // (zeroed: an entry that no launch wrote names ray 0 and the root. The task rounds do not read such entries — t8_extend_tasks_body — and a call on a machine that
-    // others share must not depend on that)
-    PT_CHECK_HIP(c, hipMemsetAsync(B.taskQ.p, 0, sizeof(TravTask) * 2 * (size_t)aux.taskCap, st));
-    PT_CHECK_HIP(c, hipMemsetAsync(B.bestKey.p, 0xFF, sizeof(unsigned long long) * (size_t)n, st)); PT_CHECK_HIP(c, hipMemsetAsync(B.resolveList.p, 0, 4 * (size_t)n, st));
-    aux.taskQ[0] = B.taskQ.p; aux.taskQ[1] = B.taskQ.p + aux.taskCap; aux.counts = B.words.p; aux.bestKey = B.bestKey.p; aux.resolveList = B.resolveList.p; aux.primToSlot = c->bvh.primToSlot;
-    const uint* countPtr = B.words.p + ROUTE_WORD_COUNT;
-    std::vector<ptk::float4> hostQ2;
-    if (route == PT_ROUTE_SHADOW) {
-        std::vector<ptk::float4> q0(n), q1(n);
-        for (uint32_t i = 0; i < n; i++) {
-            const float* y = rays + 8 * (size_t)i; float tag; memcpy(&tag, &i, 4);
-            q0[i] = ptk::make_float4(y[0], y[1], y[2], y[7]); q1[i] = ptk::make_float4(y[4], y[5], y[6], tag);
-        }
-        PT_CHECK_HIP(c, B.q0.upload(q0, st)); PT_CHECK_HIP(c, B.q1.upload(q1, st));
-        PT_CHECK_HIP(c, B.q2.resize(n)); PT_CHECK_HIP(c, hipMemsetAsync(B.q2.p, 0, sizeof(ptk::float4) * (size_t)n, st));
-        PT_CHECK_HIP(c, B.s2.resize(n)); PT_CHECK_HIP(c, hipMemsetAsync(B.s2.p, 0, sizeof(ptk::uint4) * (size_t)n, st));      // (entry i names path i: what k_resolve_nee folds the marks into)
-        PT_CHECK_HIP(c, hipStreamSynchronize(st));      // (the uploads read host vectors of this block)
-        PathPool pool{}; pool.s2 = B.s2.p;
-        const ShadowQueue sq{B.q0.p, B.q1.p, B.q2.p, 1u, nullptr, nullptr, nullptr, 0u, 0u, 0u};
-        launch_shadow(c->dsc, pool, sq, countPtr, n, B.wc.p, false, aux, st);
-        hostQ2.resize(n);
-        PT_CHECK_HIP(c, hipMemcpyAsync(hostQ2.data(), B.q2.p, sizeof(ptk::float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-    } else {
-        std::vector<ptk::uint4> s0(n), s1(n), hit(n);
-        std::vector<uint> queue(n);
-        for (uint32_t i = 0; i < n; i++) {
-            uint w[8]; memcpy(w, rays + 8 * (size_t)i, 32);
-            s0[i] = ptk::make_uint4(w[0], w[1], w[2], i); s1[i] = ptk::make_uint4(w[4], w[5], w[6], 0u);      // origin | id, direction | scene length 0
-            hit[i] = route == PT_ROUTE_EXTEND_RANGED ? ptk::make_uint4(w[3], w[7], 0u, 0u) : ptk::make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);      // (a record no launch writes stays recognisable)
-            queue[i] = i;
-        }
-        PT_CHECK_HIP(c, B.s0.upload(s0, st)); PT_CHECK_HIP(c, B.s1.upload(s1, st)); PT_CHECK_HIP(c, B.hit.upload(hit, st)); PT_CHECK_HIP(c, B.queue.upload(queue, st));
-        PT_CHECK_HIP(c, hipStreamSynchronize(st));
-        PathPool pool{}; pool.s0 = B.s0.p; pool.s1 = B.s1.p; pool.hit = B.hit.p;      // (home == nullptr: every array is indexed by the queue's entries)
-        if (route == PT_ROUTE_PACKETS) {
-            PT_CHECK_HIP(c, B.leftover.resize(n));
-            const FirstPackets pk{B.leftover.p, B.words.p + PASS_LEFTOVER, n, opt.stepCap ? opt.stepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), opt.stackBound ? opt.stackBound : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u, c->packetPrecull ? 1u : 0u};      // (the traverser of the context's mode)
-            launch_route_packets(c->dsc, pool, countPtr, n, B.wc.p, pk, B.words.p + ROUTE_WORD_COMMITTED, aux.maxBlocks, st);
-            launch_extend(c->dsc, pool, pk.leftover, pk.leftoverCount, n, B.wc.p, false, aux, st);      // (n: the host's bound of the list's length, as launch_extend_first sizes k_extend_first_listed)
-        } else launch_extend(c->dsc, pool, B.queue.p, countPtr, n, B.wc.p, false, aux, st, route == PT_ROUTE_EXTEND_RANGED);
-        PT_CHECK_HIP(c, hipMemcpyAsync(out, B.hit.p, sizeof(ptk::uint4) * (size_t)n, hipMemcpyDeviceToHost, st));
-    }
-    uint overflow = 0u;
-    PT_CHECK_HIP(c, hipMemcpyAsync(words.data(), B.words.p, 4 * (size_t)ROUTE_WORDS, hipMemcpyDeviceToHost, st));
-    PT_CHECK_HIP(c, hipMemcpyAsync(&overflow, &B.wc.p->overflow, 4, hipMemcpyDeviceToHost, st));
-    PT_CHECK_HIP(c, hipStreamSynchronize(st));
-    PT_CHECK_HIP(c, hipGetLastError());
-    if (route == PT_ROUTE_SHADOW) for (uint32_t i = 0; i < n; i++) ((uint32_t*)out)[i] = hostQ2[i].w == 1.0f ? 1u : 0u;
-    if (stats) {
-        stats->splitRays = words[TRAV_RESOLVE]; for (int q = 0; q < 4; q++) stats->taskCounts[q] = words[q];
-        stats->packetRays = words[ROUTE_WORD_COMMITTED]; stats->leftoverRays = words[PASS_LEFTOVER]; stats->overflow = overflow;
-    }
-    if (overflow) return fail(c, PT_ERROR_HIP, "pt_trace_route: BVH8 traversal: stack tail, straggler task queue or leftover list overflow (word " + std::to_string(overflow) + ")");
-    return PT_OK;
-}
-#endif
 int32_t pt_get_build_stats(pt_context* c, double* b, double* r, double* l) { if (!c) return PT_ERROR_INVALID_ARGUMENT; if (b) *b = c->buildMs; if (r) *r = c->refitMs; if (l) *l = c->lightBakeMs; return PT_OK; }
 int32_t pt_get_bvh_info(pt_context* c, PtBvhInfo* out) {
     if (!c || !out) return PT_ERROR_INVALID_ARGUMENT;

@@ -3,6 +3,8 @@
 #pragma once
 #include "../../include/mi355pt.h"
 #include "pt_wavefront.h"
+#include "pt_trace.h"
+#include "pt_bake.h"
 #include "pt_texture_ingest.h"
 #include "pt_stableplanes_launch.h"
 #include "pt_denoiser.h"
@@ -106,7 +108,7 @@ static const uint TASK_QUEUE_CAPACITY = 1u << 22;      // sub-tree tasks per que
 #endif
 #ifndef PT_FUSED_TRAVERSAL
 // pt_set_fused_traversal (default: on — it pays at every size, profiles/r06b_fused_traversal_ab.txt): 0 = every bounce traces its
-// visibility rays in a launch of their own, 1 = together with the closest-hit rays of the next bounce (k_trace_pair, pt_wavefront.hip),
+// visibility rays in a launch of their own, 1 = together with the closest-hit rays of the next bounce (k_trace_pair, pt_trace.hip),
 // 2 = by the size of the call (PT_FUSED_BELOW)
 #define PT_FUSED_TRAVERSAL 1u
 #endif
@@ -313,6 +315,10 @@ struct pt_context {      // (the type include/mi355pt.h names: default visibilit
 inline int fail(pt_context* c, int code, const std::string& msg) { if (c) c->lastError = msg; return code; }
 #define PT_CHECK_HIP(c, expr) \
     do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, PT_ERROR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+// the packets of the context's settings (ptk::FirstPackets): the traverser of c->firstVertexPackets (2: 64-ray packets) with or without the interval test; stepCap / stackBound 0: that traverser's default
+inline FirstPackets first_packets(const pt_context* c, uint* leftover, uint* leftoverCount, uint capacity, uint stepCap, uint stackBound) {
+    const bool wide = c->firstVertexPackets == 2u;
+    return FirstPackets{leftover, leftoverCount, capacity, stepCap ? stepCap : (wide ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), stackBound ? stackBound : (uint)T8_PACKET_STACK, wide ? 1u : 0u, c->packetPrecull ? 1u : 0u}; }
 
 // ---- pt_shard.hip
 void build_shards(pt_context* c);                    // the shard lists of the frame size (pt_resize)

@@ -1,5 +1,5 @@
 // mi355pt — the frame drivers: pt_render (reference mode) and the realtime mode's build and fill passes (pt_build_stable_planes,
-// pt_fill_stable_planes). Host code only: each composes a frame out of the launches pt_wavefront.h and pt_stableplanes_launch.h declare.
+// pt_fill_stable_planes). Host code only: each composes a frame out of the launches pt_wavefront.h, pt_trace.h and pt_stableplanes_launch.h declare.
 // What the three share — the slicing of the owned pixels into batches, the frame's events, the harvest of the counters, the checks at the
 // end of a frame — exists once, at the top of the file.
 #include "pt_context.h"
@@ -282,9 +282,7 @@ struct RenderFrame {
         PT_CHECK_HIP(c, c->dFirstLeftover.resize(c->poolCapacity));
         for (uint b = 0; b < numBatches; b++) {
             RenderBatch& t = B[b]; if (!t.firstInPlace) continue;
-            t.packets = FirstPackets{c->dFirstLeftover.p + t.base, t.aux.counts + PASS_LEFTOVER, t.total,
-                                     c->packetStepCap ? c->packetStepCap : (c->firstVertexPackets == 2u ? (uint)T8_PACKET64_STEP_CAP : (uint)T8_PACKET_STEP_CAP), c->packetStack ? c->packetStack : (uint)T8_PACKET_STACK, c->firstVertexPackets == 2u ? 1u : 0u,
-                                     c->packetPrecull ? 1u : 0u};
+            t.packets = first_packets(c, c->dFirstLeftover.p + t.base, t.aux.counts + PASS_LEFTOVER, t.total, c->packetStepCap, c->packetStack);
         }
         return PT_OK;
     }
@@ -544,7 +542,7 @@ struct FillFrame {
         numBatches = batch_count(c, (uint)c->owned.size());
         ShadowQueue sq = frame_shadow_queue(c, 0u);
         // feedback: the fourth word group of an entry and the reservoir planes; the reference mode's shadow kernels then apply the reservoir update
-        // and the roulette fix-up of a visible entry themselves (pt_wavefront.hip shadow_visible; one slot per pixel: plane stride 0)
+        // and the roulette fix-up of a visible entry themselves (pt_trace.hip shadow_visible; one slot per pixel: plane stride 0)
         if (feedback) {
             sq.q3 = c->dSq3.p; sq.fbTotalWeight = c->neeat.fbW.p; sq.fbCandidates = c->neeat.fbC.p;
             sq.fbWidth = c->width; sq.fbPlane = 0u; sq.fbSampleFirst = 0u;

@@ -1,7 +1,7 @@
 // mi355pt device/host leaf library — NEE-AT, the light baker's feedback passes: last frame's per-pixel feedback reservoirs -> this frame's screen-tile local samplers
 // and the usage counts that re-weight the global sampler.
 // Shared, as one text, by the PRODUCT path (libmi355pt.so) and the CPU oracle the tests use; written to the arithmetic contract stated in pt_vec.h.
-// pt_wavefront.hip runs these functions as kernels (k_neeat_*), one thread per pixel / low-res pixel / tile; the CPU oracle runs them in loops, and
+// pt_bake.hip runs these functions as kernels (k_neeat_*), one thread per pixel / low-res pixel / tile; the CPU oracle runs them in loops, and
 // tests/test_neeat_baker.py pins them to the reference's own passes, run thread by thread.
 // Reference anchors (paths relative to /root/reference/Rtxpt/): Lighting/LightsBaker.hlsl:1062-1855 (the ProcessFeedbackHistory passes, FillTile, ClearFeedbackHistory),
 // :753-762 (ResetLightProxyCounters), :880-948 (ComputeProxyCounts' feedback term), :118-162 (ImportanceBooster's intensity-delta term), Lighting/LightsBaker.cpp:943-962,
@@ -12,7 +12,7 @@
 //          -> light weights (+ intensity-delta boost against last frame's weights) -> proxy counts (lerp towards the usage counts) -> global proxy table
 //   end    P1a (half-resolution "blended" reservoirs), P1b (one candidate per pixel: feedback, else blended, else last frame's tile, else the global sampler),
 //          P2 (a tile = its 8 x 8 pixels' candidates + 64 blended candidates from a wider disc), P3 (sort by light, count duplicates), Clear (keep 0.5 % of the past)
-//   trace  the frame; visible NEE samples fill the feedback reservoirs again (pt_path.h ShadowRequest, pt_wavefront.hip shadow_visible)
+//   trace  the frame; visible NEE samples fill the feedback reservoirs again (pt_path.h ShadowRequest, pt_trace.hip shadow_visible)
 // What differs from the reference, by necessity:
 //   * nothing about reprojection: Reproject (:1348-1375) is restated with its motion vectors (neeat_reproject). In REFERENCE mode they are zero (Sample.cpp:2494), history is
 //     read at the same pixel, and the depth test compares what the path tracer itself exported in the last two frames — the clip depth of every path's last vertex

@@ -241,7 +241,7 @@ template <bool LP16, int STF> struct PathKernelContextStfT {
     }
     // Bridge::computeCameraRay (BridgeDonut:543-564) for a pixel and sample index: origin on the near plane and direction
     void computeCameraRay(uint px, uint py, uint sampleIndex, float3& o, float3& d) const { cameraRay(cam, S.perPixelJitterAAScale, px, py, sampleIndex, o, d); }
-    // (the text itself, as a function of the two inputs it has besides the pixel and the sample: k_extend_first, pt_wavefront.hip, reads them from memory where it forms a ray)
+    // (the text itself, as a function of the two inputs it has besides the pixel and the sample: k_extend_first, pt_trace.hip, reads them from memory where it forms a ray)
     static void cameraRay(const PathTracerCameraData& cam, float perPixelJitterAAScale, uint px, uint py, uint sampleIndex, float3& o, float3& d) {
         SampleGeneratorVertexBase vb = SampleGeneratorVertexBase::make((px << 16) | py, 0, sampleIndex);
         SampleSequenceGenerator sg = SampleSequenceGenerator::make(vb);

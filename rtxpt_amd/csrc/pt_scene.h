@@ -13,6 +13,7 @@
 #include "pt_lights.h"
 #include "pt_envcube.h"
 #include "pt_sky.h"
+#include "pt_trace_plan.h"      // the traversal launch geometry (T8_BLOCK, T8_CHUNK, T8_LANES, T8_MAX_BLOCKS ...)
 
 namespace ptk {
 #pragma clang force_cuda_host_device begin
@@ -68,7 +69,6 @@ static inline void tri_bounds(const TriRecord& t, float3& mn, float3& mx) {     
 static_assert(sizeof(TriRecord) == 48, "TriRecord must be 48 bytes");
 struct BvhNode { float3 lmin, lmax, rmin, rmax; uint left, right, _pad0, _pad1; };           // child ref: bit31 = leaf (first<<3 | count-1)
 static_assert(sizeof(BvhNode) == 64, "BvhNode must be 64 bytes");
-#define PT_T8_LANES 2             // lanes per ray in the traversal kernels (pt_traverse8p.h; the four-lane kernel of rounds 1-3 is in the history)
 #ifndef PT_BVH_MAX_LEAF
 #define PT_BVH_MAX_LEAF 2         // triangles per leaf = lanes per ray: a leaf is tested in one round. With pairs, 2 instead of 4: k_extend 48.3 -> 43.6 ms, k_shadow 14.0 -> 12.2 ms
 #endif                                                  // (1: 50.6 / 13.6 ms; 3: 46.1 / 13.3; 6: 51.9 / 15.3 — profiles/r03u_leafsize_ab*.txt)
@@ -84,23 +84,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));   // v_pk_*_f32 operand
 struct __attribute__((packed, aligned(4))) u32x3p { uint x, y, z; };   // 12-byte child slot load (global_load_dwordx3)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 static_assert(sizeof(Bvh8Node) == 128, "Bvh8Node must be 128 bytes");
-#ifndef PT_T8_CHUNK
-#define PT_T8_CHUNK 32      // rays a wave parks in LDS per chunk fetch (one per lane pair)
-#endif
 #ifndef PT_BVH8_STACK
 #define PT_BVH8_STACK 13         // (7 blocks of 256 threads per CU: 14 x 8 B x 128 pairs + the chunk parking lot per block; 12 entries: -0.6 %, 8: -6 %)
 #endif
-// traversal launch geometry (pt_traverse8p.h): 256-thread blocks, 2 lanes per ray -> 128 rays in flight per block, each with an LDS stack of
-// BVH8_STACK entries (odd stride: quads land on different banks) and a T8_SPILL_DEPTH-entry tail in global memory (DeviceScene::travSpill)
 static const uint BVH8_STACK = PT_BVH8_STACK, BVH8_STACK_STRIDE = PT_BVH8_STACK + 1;
-static const uint T8_BLOCK = 256, T8_CHUNK = PT_T8_CHUNK, T8_LANES = PT_T8_LANES, T8_GROUPS_PER_WAVE = 64 / PT_T8_LANES, T8_GROUPS_PER_BLOCK = T8_BLOCK / T8_LANES, T8_SPILL_DEPTH = 96;
-#ifndef PT_T8_MAX_BLOCKS
-#define PT_T8_MAX_BLOCKS (256 * 7 * 3)  // upper bound of a traversal grid (sizes the stack-tail memory). The GPU holds 256 x 7 blocks (LDS). A frame
-                                                                          // of several pipelined batches launches exactly that many per batch — 2x / 3x / 4x were 0.2 / 1.7 / 3.7 % slower on the full frame and
-                                                                          // 4-7 % on one rank of an 8-way shard (profiles/r03w_maxblocks_ab.txt): the other batches fill the gaps —, a launch that has the GPU to
-                                                                          // itself three times that: the blocks that finish early are replaced (TravAux::maxBlocks)
-#endif
-static const uint T8_MAX_BLOCKS = PT_T8_MAX_BLOCKS;     // persistent waves stride over 64-ray chunks
 
 // per leaf-order triangle slot: what the alpha test needs, resolved at build time (texture coordinates of the 3 vertices, alpha texture, cutoff);
 // tex == ~0: not alpha tested. Saves the primInfo -> subInstance -> index -> uv chain (7 dependent loads) inside the traversal loop.

@@ -43,38 +43,11 @@ struct WaveCounters {           // device-resident counters / stats (one 256 B b
     FirstVertexCamera firstCamera;
 };
 
-// straggler splitting (pt_traverse8.h): per pipelined batch, two task queues (ping-pong), the per-ray merge keys and the list of rays to resolve.
-// bestKey: closest hit = float bits of t << 32 | primitive (atomicMin = min t, ties to the
-// lower primitive id); occlusion = 0 visible so far / 1 occluded.
-// counts: TRAV_COUNTERS words per traversal launch, one counter per producer so that nothing has to be reset between the launches of a pass —
-//   [0] sub-trees split off by k_extend / k_shadow (task queue 0), [1..3] by task rounds 0..2 (queues 1, 0, 1), [TRAV_RESOLVE] rays to resolve.
 // pt_render keeps one PASS_COUNTERS block per batch — {extend launch, shadow launch, k_classify's three class counts and its count of dropped hits} — and zeroes it once per pass.
 static const uint TRAV_COUNTERS = 5, TRAV_RESOLVE = 4, PASS_COUNTERS = 16, PASS_SHADOW_OFFSET = 5, PASS_CLASS_OFFSET = 10, PASS_LEFTOVER = 14;      // PASS_LEFTOVER: the rays the vertex-0 packets left to the per-ray kernel (FirstPackets)
-struct TravAux { TravTask* taskQ[2]; uint* counts; uint taskCap; unsigned long long* bestKey; uint* resolveList; const uint* primToSlot; uint maxBlocks; };      // maxBlocks: grid bound of the traversal launches (0: T8_MAX_BLOCKS)
 
 // paths [first, first + n) of the pool region -> queue[0 .. n); countPtr (may be null): the counter of the queue `queue` is the end of, incremented by n (k_generate)
 void launch_generate(const PathKernelContext& k, PathPool pool, const uint* ownedPixels, uint numOwned, uint sampleFirst, uint spp, uint first, uint n, uint* queue, uint* countPtr, hipStream_t st);
-void launch_extend(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st, bool ranged = false);      // ranged: the rays' intervals wait in pool.hit[p].xy (k_extend)
-// launch_extend for the first pass of a batch whose paths were NOT generated: ray i is the camera ray of path i of `fv` (no queue, no read of pool.s0 / s1). The rays that are cut into
-// sub-trees get their origin | id and direction | length written to pool.s0 / s1 [i] by a launch over the resolve list (k_first_split_rays), for the task rounds and the resolve pass behind it. The camera: wc->firstCamera. Composed frames only (no counters).
-// pk.leftover != null: the rays are traced as packets on one shared stack per wave (pt_traverse8k.h: k_extend_first_packets64, 64 rays, or k_extend_first_packets, 32); the packets that exceed pk.stepCap steps or
-// pk.stackBound stack entries leave their rays on pk.leftover (count: *pk.leftoverCount, zero on entry; capacity >= count), which the per-ray kernel traces behind them. Same hits.
-#ifndef T8_PACKET_STACK
-#define T8_PACKET_STACK 64        // entries of a wave's stack in LDS (a node pushes at most seven)
-#endif
-#ifndef T8_PACKET_STEP_CAP
-#define T8_PACKET_STEP_CAP 128    // node + leaf steps after which a packet is handed to the per-ray kernel (environment MI355PT_PACKET_STEP_CAP overrides)
-#endif
-#ifndef T8_PACKET64_STEP_CAP
-#define T8_PACKET64_STEP_CAP 192  // the same for the 64-ray packets, which take a few more steps: the first launch of a 4K step alone on the GPU 7.05 / 6.68 / 6.71 ms at 128 / 192 / 256 (profiles/r21a_packet64_ab.txt)
-#endif
-static const uint T8_PACKET_RAYS = 32, T8_PACKET64_RAYS = 64;
-// wide != 0: 64-ray packets, one lane per ray (k_extend_first_packets64, traverse8_packets64); 0: the 32-ray pair packets
-// precull != 0 (64-ray packets only): a node step first tests each child against the packet's interval of origins and reciprocals, and runs the per-ray slab tests only for
-// the children that test keeps (pt_packet_precull.h; environment MI355PT_PACKET_PRECULL)
-struct FirstPackets { uint* leftover; uint* leftoverCount; uint capacity, stepCap, stackBound, wide, precull; };
-static const uint T8_PACKET_INTERVAL_WORDS = 16;      // a wave's LDS words for its packet's interval (twelve floats, read as three 16-byte groups)
-void launch_extend_first(const PathKernelContext& k, PathPool pool, FirstVertex fv, const uint* countPtr, uint count, WaveCounters* wc, TravAux aux, FirstPackets pk, hipStream_t st);
 // classScratch (2 x countIn words: memory that is free between the extend and the shadow launches of a bounce) + classCount (4 words, zero on entry: three classes and the dropped hits): k_classify's output; null = shade in queue order
 // launch_extend / launch_shade / launch_shadow expect the pass's counter block zeroed by the caller (launch_pass_reset)
 void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr,
@@ -83,32 +56,10 @@ void launch_shade(const PathKernelContext& k, PathPool pool, const uint* queueIn
 // a compacted pool's live paths back to their home slots: out.s0 / s1 / s3 / s4 [home[i]] = in...[i] for the *countPtr positions (out: another array set than in's); the queue `in.home` is then an ordinary extend queue
 void launch_uncompact(PathPool in, PathPool out, const uint* countPtr, uint count, hipStream_t st);
 void launch_classify(PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* classScratch, uint* classCount, hipStream_t st);      // k_classify: {continuing hit, terminating hit, miss} made contiguous
-void launch_shadow(const DeviceScene& sc, PathPool pool, ShadowQueue sq, const uint* countPtr, uint count, WaveCounters* wc, bool counters, TravAux aux, hipStream_t st);
-// the closest-hit rays of the extend queue and the visibility rays of the previous vertex (shadow queue) in ONE traversal launch, their task rounds and resolve passes in shared launches
-// too (k_trace_pair; sq.group == 0 only). auxE / auxS must not share task queues, counters, keys or resolve lists; *shCountPtr is zero afterwards
-void launch_trace_pair(const DeviceScene& sc, PathPool pool, const uint* queue, const uint* extCountPtr, uint extCount, ShadowQueue sq, uint* shCountPtr, uint shCount, WaveCounters* wc, TravAux auxE, TravAux auxS, hipStream_t st);
 // the late bounces of a batch in one launch: every wave runs 32 paths of queueIn to their end (at most maxBounces bounces each); stragglers and paths beyond the bound come back through
 // queueOut / countOutPtr (and, for visibility rays, the shadow queue / wc->shadowCount). NEEFullSamples 1 only (sq.group == 0); the pass's counters zeroed by the caller as for launch_shade
 void launch_tail(const PathKernelContext& k, PathPool pool, const uint* queueIn, const uint* countInPtr, uint countIn, uint* queueOut, uint* countOutPtr, ShadowQueue sq, WaveCounters* wc, uint maxBounces, uint deferIters /* 0: T8_TAIL_DEFER */, uint maxBlocks, hipStream_t st);
 void launch_pass_reset(uint* passCounters, uint* nextCount, uint* shadowCount, hipStream_t st);      // one launch: the batch's PASS_COUNTERS words and the two queue counters the pass refills
 void launch_accumulate(PathPool pool, const uint* ownedPixels, uint numOwned, uint spp, float4* accum, uint accumCountBase, uint width, hipStream_t st);
-void launch_trace_probe(const DeviceScene& sc, const float4* rays, uint n, float4* outClosest, uint* outVisible, uint* overflow, hipStream_t st);
-// EnvMapBaker: lat-long source (sc.envTex) + directional lights -> RGBA16F cube with mips (cube.mipOffset / dim / mipLevels filled by the caller)
-void launch_env_cube_bake(const DeviceScene& sc, const EnvDirectionalLight* lights, uint nLights, uint2* texels, const EnvCube& cube, hipStream_t st);
-void launch_env_cube_compress(uint2* texels, const EnvCube& cube, uint quality, hipStream_t st);      // every level through BC6UCompress.hlsl's encoder (quality 1: EncodeP1; 2: + the two-region modes) and the BC6H decode, in place
-void launch_env_importance(const DeviceScene& sc, uint dim, uint sx, uint sy, float4* out, hipStream_t st);
-void launch_bake_emissive(const DeviceScene& sc, const uint* subInstList, const uint* subInstTriOffset, uint numEmissiveSubInst, uint totalTris, uint lightBase,
-                          PolymorphicLightInfo* lights, PolymorphicLightInfoEx* lightsEx, hipStream_t st);
-// light weights (power^0.8), their in-order sum, proxy counts; then (after an exclusive scan of the counts by the caller) the proxy index fill
-void launch_light_weights(const PolymorphicLightInfo* lights, const PolymorphicLightInfoEx* lightsEx, uint n, float* w, const LightFrustumBoost& boost, hipStream_t st);      // ComputeWeight (+ the frustum boost) per light
-// weight sum (in light order) + ComputeProxyCounts; usage != null: NEE-AT's feedback term (n + 1 usage counts, the last one = pixels without valid feedback)
-void launch_light_proxy_counts(const float* w, uint n, float* sum, uint budget, bool uniform, uint maxPerLight, uint* counts, const uint* usage, uint totalMaxFeedbackCount, float globalFeedbackUseWeight, hipStream_t st);
-void launch_neeat_boost_weights(const float* base, const float* hist, uint nHist, uint n, float mul, float* cur, hipStream_t st);
-void launch_neeat_begin(const NeeAtFrame& F, float* snapW, uint* snapC, bool preFilter, uint totalThreads, hipStream_t st);
-void launch_neeat_end(const NeeAtFrame& F, hipStream_t st);
-void launch_light_proxy_fill(const uint* counts, const uint* offsets, uint n, uint* proxies, uint capacity, hipStream_t st);
-void launch_probe(const PathKernelContext& k, int kind, const void* dIn, void* dOut, uint n, hipStream_t st);
-// (test hooks: pt_trace_route's packet route) the `count` rays stored in pool.s0 / s1 as packets, hits to pool.hit; *committed counts the rays the packets reported themselves
-void launch_route_packets(const DeviceScene& sc, PathPool pool, const uint* countPtr, uint count, WaveCounters* wc, FirstPackets pk, uint* committed, uint maxBlocks, hipStream_t st);
 
 } // namespace ptk

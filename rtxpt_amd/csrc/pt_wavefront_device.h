@@ -1,4 +1,4 @@
-// mi355pt — device-side helpers shared by the wavefront kernels (pt_wavefront.hip) and the tail kernel (pt_tail.hip): wave-level queue appends,
+// mi355pt — device-side helpers shared by the wavefront kernels (pt_wavefront.hip, pt_trace.hip) and the tail kernel (pt_tail.hip): wave-level queue appends,
 // the path pool's SoA load / store, traversal counter set-up.
 #pragma once
 #include "pt_wavefront.h"

@@ -1,4 +1,4 @@
-"""The deferred radiance update of visible visibility rays on the device (run with -m gpu; rtxpt_amd/csrc/pt_wavefront.hip t8_shadow_body, t8_resolve_shadow_body): the
+"""The deferred radiance update of visible visibility rays on the device (run with -m gpu; rtxpt_amd/csrc/pt_trace.hip t8_shadow_body, t8_resolve_shadow_body): the
 traversal loop only marks a visibility ray that ends visible (q2[i].w = 1), and the resolve pass behind every visibility launch — k_resolve_shadow, the visibility half of
 k_resolve_pair — sweeps the launch's queue entries and adds the marked contributions to their paths (with the NEE-AT reservoir update and roulette fix-up, and into the
 stable-plane fill pass's mark pool). Where the sum is made must not change anything: every comparison here is bit for bit against the CPU oracle rendering the same frame, ray

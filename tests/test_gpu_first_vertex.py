@@ -1,4 +1,4 @@
-"""Vertex 0 in place on the device (run with -m gpu; rtxpt_amd/csrc/pt_frame.hip RenderFrame::enable_first_vertex_in_place, pt_wavefront.hip k_extend_first, k_first_split_rays,
+"""Vertex 0 in place on the device (run with -m gpu; rtxpt_amd/csrc/pt_frame.hip RenderFrame::enable_first_vertex_in_place, pt_trace.hip k_extend_first, k_first_split_rays,
 k_classify<UNIFORM>, k_shade<..., FIRST>): a compacted batch of pt_render whose first pass is a wavefront pass starts without k_generate, and that pass's launches form the vertex-0
 state — the camera ray, the pixel id, the sample index, constants of the frame — where they use it. Same operations on the same operands: every comparison here is bit for bit against
 the CPU oracle rendering the same frame, ray and hit counts included (the batch cases: a band of rows, the whole frame and the counts against the same build's serial-kernel frame; the

@@ -1,4 +1,4 @@
-"""Fused traversal launches (pt_set_fused_traversal; rtxpt_amd/csrc/pt_wavefront.hip k_trace_pair, pt_frame.hip pt_render) on the device (run with -m gpu): the visibility rays of
+"""Fused traversal launches (pt_set_fused_traversal; rtxpt_amd/csrc/pt_trace.hip k_trace_pair, pt_frame.hip pt_render) on the device (run with -m gpu): the visibility rays of
 path vertex k are traced in the launch that traces the closest-hit rays of vertex k + 1, block by block, with shared straggler rounds and resolve passes. Launch composition must
 not change anything: the frame, the ray counts and the hit count equal the frame of separate launches, bit for bit — on one, two and four pipelined batches, with and without the
 tail kernel (which makes a batch trace its pending visibility rays first), when nearly every ray goes through the straggler rounds, for a call that continues an accumulation, with

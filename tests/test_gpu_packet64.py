@@ -1,4 +1,4 @@
-"""Vertex 0 as 64-ray packets, one lane per ray (run with -m gpu; rtxpt_amd/csrc/pt_traverse8k.h traverse8_packets64, pt_wavefront.hip k_extend_first_packets64 and
+"""Vertex 0 as 64-ray packets, one lane per ray (run with -m gpu; rtxpt_amd/csrc/pt_traverse8k.h traverse8_packets64, pt_trace.hip k_extend_first_packets64 and
 k_route_packets64, MI355PT_FIRST_VERTEX_PACKETS=2): lane L of a wave holds ray 64 p + L of packet p, tests all eight children of the shared node and both triangles of a
 leaf for it, and reports its own hit; a packet over its step cap or stack bound commits nothing and leaves its up to 64 rays to the per-ray kernel. The closest hit is the
 minimum of (t, primitive) over the triangles a ray accepts, whatever the order in which they are looked at, so every case holds radiance bits, extendRays, shadowRays and

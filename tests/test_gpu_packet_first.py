@@ -1,4 +1,4 @@
-"""Vertex 0 as 32-ray packets (run with -m gpu; rtxpt_amd/csrc/pt_traverse8k.h traverse8_packets, pt_wavefront.hip k_extend_first_packets, k_extend_first_listed, pt_frame.hip
+"""Vertex 0 as 32-ray packets (run with -m gpu; rtxpt_amd/csrc/pt_traverse8k.h traverse8_packets, pt_trace.hip k_extend_first_packets, k_extend_first_listed, pt_frame.hip
 RenderFrame::enable_first_vertex_packets): the first traversal launch of a compacted batch walks the camera rays of 32 consecutive paths on one shared stack per wave; a packet over
 its step cap or stack bound commits nothing and leaves its rays to the per-ray kernel behind it. The closest hit is the minimum of (t, primitive) over the triangles a ray accepts,
 whatever the order in which they are looked at, so every case here holds radiance bits, extendRays, shadowRays and hits to the CPU oracle AND to the same context with

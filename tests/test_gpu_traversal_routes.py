@@ -32,7 +32,7 @@ lowers the merge key first decides what the others still visit):
 Packets, committed | left over: the quad, box, fan, grid and tiny cases 8000 | 0 resp. 3000 | 0; ico-origin 2936 | 64 (step cap 8: 256 | 2744, stack bound 2: 160 | 2840);
 ico-1e5-size10 2648 | 352; box-1e3-all-verts at stack bound 2 800 | 7200; both tube cases 0 | 2048 at every setting (their leftover launch is the extend column).
 A task queue of half the needed size: PT_ERROR_HIP, overflow word 2, task round 0 fed 12409 (extend) / 11499 (shadow, 2048 rays) and round 1 nothing — the task rounds
-do not read a queue that overflowed (pt_wavefront.hip t8_extend_tasks_body: before, they read the unwritten entries below the capacity)."""
+do not read a queue that overflowed (pt_trace.hip t8_extend_tasks_body: before, they read the unwritten entries below the capacity)."""
 import copy
 import os
 import sys

@@ -35,7 +35,7 @@ def test_exports_every_declared_symbol(lib):
 
 
 def test_shipped_library_carries_no_test_hooks(lib):
-    """include/mi355pt_testhooks.h: the evaluation hooks live in libmi355pt_testhooks.so (same sources, -DMI355PT_TEST_HOOKS), the shipped library exports none of them."""
+    """include/mi355pt_testhooks.h: the evaluation hooks live in libmi355pt_testhooks.so (the shipped library's objects plus pt_hooks.hip), the shipped library exports none of them."""
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mi355pt_testhooks.h")).read(), flags=re.S)
     hooks = sorted(set(re.findall(r"\b(pt_[a-z_0-9]+)\s*\(", src)))
     assert hooks == sorted(pt.TEST_HOOK_EXPORTS) and hooks
