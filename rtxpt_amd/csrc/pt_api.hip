@@ -182,7 +182,7 @@ int finalize_geometry(pt_context* c) {
             for (uint t = 0; t < gd.numIndices / 3; t++) c->primInfo.push_back(ptk::make_uint2(subInst, t));
         }
     }
-    // traversal addresses triangles with 32-bit byte offsets (48 B records) and 28-bit leaf references
+    // traversal addresses triangles, and the alpha records parallel to them (alpha_test_slot), with 32-bit byte offsets (48 B records: slot * 48 < 2^32) and 28-bit leaf references
     if (c->primInfo.size() > 0x7FFFFFFull / 3ull * 2ull)
         return fail(c, PT_ERROR_UNSUPPORTED, "more than 89 M triangles per scene are not supported by the traversal kernels");
     c->numTris = (uint)c->primInfo.size();

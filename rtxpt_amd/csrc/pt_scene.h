@@ -349,19 +349,34 @@ static inline bool alpha_test(const DeviceScene& sc, uint prim, float u, float v
     return opacity >= si.AlphaCutoff();
 }
 
-#ifndef PT_ALPHA_LUT
-#define PT_ALPHA_LUT 1      // 1: the opacity k / 255 of a byte plane comes from a 256-entry constant table, 0: from a division (A/B: the four divisions cost 4 % of k_extend)
-#endif
-#if PT_ALPHA_LUT
-// k / 255.0f for k = 0..255 as a table (the quotients are formed by the compiler: IEEE division, the same floats the upload computes)
-struct Unorm8Table { float v[256]; constexpr Unorm8Table() : v() { for (int k = 0; k < 256; k++) v[k] = (float)k / 255.0f; } };
-__device__ __constant__ const Unorm8Table kUnorm8Table{};
-static inline float unorm8_to_float(unsigned char k) { return kUnorm8Table.v[k]; }
-#endif
+// The opacity k / 255.0f of a byte of an alpha plane, formed in registers: the product with the rounded reciprocal r = fl(1 / 255), then one correction step on the exact
+// residual e = k - 255 q (an fma has no rounding but its own). The result is the correctly rounded quotient — the float the texture upload and the oracle form by division —
+// for every byte (tests/unorm8_exact_check.cpp compares all 256 bit for bit); the plain product is not (126 of 256 differ). Explicit fmaf: the build has -ffp-contract=off.
+// PT_ALPHA_LUT, the A/B this ends (profiles/r29a_traversal_issue_diet.txt): 0 = four divisions (about 48 instructions, 4 % of k_extend when the table came), 1 = a 256-entry
+// __constant__ table (a GOT load, a scalar wait and four dependent loads behind the opacity bytes: a memory hop of its own), 2 = this. With the other cuts of round 29 in
+// place 2 beat 1 by 0.6 ms of the 4K frame (57.01 -> 56.4 ms) and is the only text left; the macro is no longer read (host builds of the tests still pass it).
+static inline float unorm8_to_float(unsigned char k) {
+    const float kf = (float)k, r = asfloat(0x3B808081u), q = kf * r, e = fmaf(-255.0f, q, kf);
+    return fmaf(e, r, q);
+}
 // the same test from the build-time record of triangle slot `slot` (identical arithmetic on identical operands: only the .w channel of
 // sample_bilinear at mip 0 is evaluated; the texture coordinates, cutoff and the place of the opacities come from the AlphaRec instead of the vertex streams / TexInfo)
 static inline bool alpha_test_slot(const DeviceScene& sc, uint slot, float u, float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // ONE fetch of the record: its 48 bytes as three 16-byte loads from the scene's (wave-uniform) base and a 32-bit byte offset, all three issued before the first use and
+    // all three waited for before `tex` is looked at. Left to itself the compiler fetches (tex, cutoff) alone, waits, branches and only then asks for the rest of the same
+    // line: two memory latencies for one record. The opacity fetch stays under the branch: a record without a texture never forms an address from its plane word.
+    // slot * 48 fits 32 bits for every slot of a scene (finalize_geometry, pt_api.hip). The host build reads the record as a struct: same fields, no alignment to promise.
+    const char* recBase = reinterpret_cast<const char*>(sc.alphaRecs);
+    const uint recOff = slot * 48u;
+    u32x4 ra = *reinterpret_cast<const u32x4*>(recBase + recOff), rb = *reinterpret_cast<const u32x4*>(recBase + (recOff + 16u)), rc = *reinterpret_cast<const u32x4*>(recBase + (recOff + 32u));
+    asm volatile("" : "+v"(ra), "+v"(rb), "+v"(rc));      // (all twelve words are in registers here: nothing of the fetch can sink below the branch)
+    AlphaRec r;
+    r.t0 = make_float2(asfloat(ra.x), asfloat(ra.y)); r.t1 = make_float2(asfloat(ra.z), asfloat(ra.w)); r.t2 = make_float2(asfloat(rb.x), asfloat(rb.y));
+    r.tex = rb.z; r.cutoff = asfloat(rb.w); r.wh = rc.x; r.plane = rc.y; r.fmt = rc.z; r._pad = rc.w;
+#else
     const AlphaRec r = sc.alphaRecs[slot];
+#endif
     if (r.tex == 0xFFFFFFFFu) return true;
     float b0 = 1.0f - (u + v);
     float2 uv = (r.t0 * b0 + r.t1 * u) + r.t2 * v;
@@ -385,11 +400,7 @@ static inline bool alpha_test_slot(const DeviceScene& sc, uint slot, float u, fl
     float w00, w10, w01, w11;
     if (r.fmt == 0u) {          // opacities k / 255: the quotient the texture upload formed (correctly rounded division on both sides)
         const unsigned char* a = sc.alphaPool + r.plane;
-#if PT_ALPHA_LUT
         w00 = unorm8_to_float(a[r0 + (uint)x0]); w10 = unorm8_to_float(a[r0 + (uint)x1]); w01 = unorm8_to_float(a[r1 + (uint)x0]); w11 = unorm8_to_float(a[r1 + (uint)x1]);
-#else
-        w00 = (float)a[r0 + (uint)x0] / 255.0f; w10 = (float)a[r0 + (uint)x1] / 255.0f; w01 = (float)a[r1 + (uint)x0] / 255.0f; w11 = (float)a[r1 + (uint)x1] / 255.0f;
-#endif
     } else {
         const float* a = reinterpret_cast<const float*>(sc.alphaPool + r.plane);
         w00 = a[r0 + (uint)x0]; w10 = a[r0 + (uint)x1]; w01 = a[r1 + (uint)x0]; w11 = a[r1 + (uint)x1];

@@ -161,13 +161,14 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
 // issue-slot probes (developer builds; tools/valu_ceiling): T8_PROBE_FILL_N independent filler instructions per wave iteration — 1: of the class that issues
 // every
 #ifdef T8_PROBE_FILL
-        // 2 cycles per SIMD (v_add_u32), 2: of the class that issues every 4 (v_max_f32), 3: v_cndmask_b32_e64. Outputs are dead; no register lives across the
-        // loop.
+        // 2 cycles per SIMD (v_add_u32), 2: of the class that issues every 4 (v_max_f32), 3: v_cndmask_b32_e64, 4: scalar (s_and_b64 of the exec mask into a dead
+        // SGPR pair, no memory operand). Outputs are dead; no register lives across the loop.
         {
             uint f0_, f1_;
 #pragma unroll
             for (int k_ = 0; k_ < T8_PROBE_FILL_N / 2; k_++) {
-                if (T8_PROBE_FILL == 1) asm volatile("v_add_u32 %0, %2, %2\n v_add_u32 %1, %2, %2" : "=v"(f0_), "=v"(f1_) : "v"(lane));
+                if (T8_PROBE_FILL == 4) { unsigned long long s0_, s1_; asm volatile("s_and_b64 %0, exec, exec\n s_and_b64 %1, exec, exec" : "=s"(s0_), "=s"(s1_) : : "scc"); }
+                else if (T8_PROBE_FILL == 1) asm volatile("v_add_u32 %0, %2, %2\n v_add_u32 %1, %2, %2" : "=v"(f0_), "=v"(f1_) : "v"(lane));
                 else if (T8_PROBE_FILL == 2) asm volatile("v_max_f32 %0, %2, %2\n v_max_f32 %1, %2, %2" : "=v"(f0_), "=v"(f1_) : "v"(lane));
                 else asm volatile("v_cndmask_b32_e64 %0, %2, %2, s[0:1]\n v_cndmask_b32_e64 %1, %2, %2, s[0:1]" : "=v"(f0_), "=v"(f1_) : "v"(lane));
             }
@@ -248,7 +249,19 @@ __device__ __forceinline__ void traverse8_pairs(const DeviceScene& sc, uint coun
 #pragma unroll
             for (int k = 0; k < 4; k++) next = (hit[k] && rank[k] == 0u) ? ref[k] : next;
             next &= dpp_u<DPP_QP_XOR1>(next);
-            if (nhit > 1u) {
+            // The pushes, far to near (nearest on top). One ballot chooses between two texts. Common: no ray of the wave leaves the LDS part of its stack with this
+            // node — every child slot is ONE unconditional store: a child that is not pushed (not hit, or the nearest: rank 0) writes to entry BVH8_STACK of the pair's
+            // own row, the spare entry behind the BVH8_STACK that are used (BVH8_STACK_STRIDE = BVH8_STACK + 1; no pop, no split and no store of the other text touches
+            // it: each of them tests its index < BVH8_STACK first). A compare, a select, a shift-add and the store per slot, no exec-mask change; as four guarded
+            // stores the same region was four mask save / branch / restore groups. Rare: some ray goes into, or over, its tail in global memory — the guarded text.
+            const bool deep = nhit > 1u && sp + nhit - 1u > BVH8_STACK;
+            if (t8_ballot(deep) == 0ull) {
+                uint2* sb = stack_base();
+                const uint top = sp + nhit - 1u;
+#pragma unroll
+                for (int k = 0; k < 4; k++) sb[(hit[k] && rank[k] > 0u) ? top - rank[k] : BVH8_STACK] = make_uint2(ref[k], key[k] & ~7u);
+                sp = (nhit > 1u) ? top : sp;
+            } else if (nhit > 1u) {
                 if (sp + nhit - 1u > BVH8_STACK + T8_SPILL_DEPTH) { if (h == 0u) atomicOr(overflowFlag, 1u); }
                 else {      // far to near: nearest on top
                     uint2* sb = stack_base();
